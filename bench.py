@@ -1,8 +1,14 @@
 """Throughput of the MPQE R-GCN query-graph encoder hot path (forward + backward) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, runs W warm-up steps, times exactly K steps (one block; --repeats R times R blocks of K and
+reports the median), writes what the last timed step computed when --dump-outputs DIR is given (the loss vector and
+every parameter gradient, float32 .npy; inputs are seeded, so two builds can be compared output for output), and
+prints the line. --full adds everything else: the pre-timing checks against the module path, the secondary figures
+(replay, pack_ms, dropin_loop), the per-kernel timings and rooflines, roofline_scatter and the CPU baseline.
 
 Workload (BASELINE.json configs[1]): the reference's post-burn-in training step on an
 AIFB-shaped synthetic KG -- 11 batches of B=512 query graphs (1x 1/2/3-chain, 2x each of
@@ -28,6 +34,7 @@ import socket
 import subprocess
 import sys
 import time
+import zlib
 
 import numpy as np
 import torch
@@ -45,10 +52,19 @@ def parse():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=20)
-    ap.add_argument('--repeats', type=int, default=0,
-                    help='the timed block of --steps steps is repeated this many times; the median block is reported. '
-                         '0 = as many blocks as make ~0.6 s of timed steps (a few steps are timed first), at least 25 '
-                         '(5 when a block takes more than 50 ms), at most 500')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline figure too: the pre-timing checks against the module path (and, '
+                         'N > 1, of the exchange against a dense all-reduce), the replay figure, pack_ms, per-kernel '
+                         'timings and rooflines, roofline_scatter, dropin_loop, the CPU baseline; the --no-* switches '
+                         'below drop single records of these')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed -- the loss vector and every '
+                         'parameter gradient -- as DIR/<name>.npy (float32; at most 64 MB in all: beyond that the largest '
+                         'arrays are replaced by a fixed, seeded sample of their elements, with <name>.index.npy)')
+    ap.add_argument('--repeats', type=int, default=1,
+                    help='the timed block of --steps steps is repeated this many times; the median block is reported '
+                         '(default 1: exactly --steps timed steps). 0 = as many blocks as make ~0.6 s of timed steps (a '
+                         'few steps are timed first), at least 25 (5 when a block takes more than 50 ms), at most 500')
     ap.add_argument('--kg', default='aifb')
     ap.add_argument('--embed-dim', type=int, default=128)
     ap.add_argument('--batch-size', type=int, default=512)
@@ -60,7 +76,7 @@ def parse():
                     help='skip the pack_ms record (host-side loops with ids in host memory): profiler runs, so that the per-kernel averages are those of the timed loop')
     ap.add_argument('--no-scatter', action='store_true', help='skip the roofline_scatter record (general-graph scatter-aggregate)')
     ap.add_argument('--no-self-check', action='store_true',
-                    help='skip the pre-timing comparison with the module path (timing experiments with builds that are wrong on purpose)')
+                    help='--full: skip the pre-timing comparison with the module path (timing experiments with builds that are wrong on purpose)')
     ap.add_argument('--cpu-seconds', type=float, default=12.0)
     ap.add_argument('--path', default='auto', choices=['auto', 'modules', 'fused'])
     ap.add_argument('--lanes', type=int, default=1, help='HIP streams one fused step is spread over (level form only)')
@@ -559,6 +575,44 @@ def cpu_baseline(args, schema, model_state, node_maps, rel_ids, mode_ids, cfg, s
                           ', '.join('%d: %.2f' % (c, t) for c, t in sorted(timing.items()))))
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """arrays: name -> tensor, written as out_dir/<name>.npy in float32. When they come to more than `limit` bytes in all,
+    the smallest go whole and each of the rest is replaced by a fixed, seeded sample of its elements (flattened, in index
+    order) with their flat indices beside it (<name>.index.npy, float64: exact below 2^53), within an equal share of what
+    is left of the budget. Returns the names written whole and the names sampled."""
+    os.makedirs(out_dir, exist_ok=True)
+    items = sorted(arrays.items(), key=lambda kv: (kv[1].numel(), kv[0]))
+    left, whole, sampled = limit, [], []
+    for k, (name, t) in enumerate(items):
+        flat = t.detach().reshape(-1).float()
+        share = left // (len(items) - k)
+        if flat.numel() * 4 <= share:
+            np.save(os.path.join(out_dir, name + '.npy'), flat.cpu().numpy().reshape(tuple(t.shape)))
+            left -= flat.numel() * 4
+            whole.append(name)
+            continue
+        rng = np.random.RandomState(zlib.crc32(name.encode()))
+        idx = np.unique(rng.randint(0, flat.numel(), size=max(1, share // 12), dtype=np.int64))
+        vals = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy()
+        np.save(os.path.join(out_dir, name + '.npy'), vals)
+        np.save(os.path.join(out_dir, name + '.index.npy'), idx.astype(np.float64))
+        left -= vals.nbytes + idx.size * 8
+        sampled.append(name)
+    return whole, sampled
+
+
+def step_outputs(model, loss):
+    """What a caller of the timed step receives: the loss (fused path: [1 + nb], the weighted step loss then the mean hinge
+    of every batch) and d loss / d p of every parameter (p.grad; the fused step binds them to its flat gradient buffer)."""
+    out = {'loss': loss.reshape(-1)}
+    for k, p in model.named_parameters():
+        out['grad.' + k] = torch.zeros_like(p) if p.grad is None else p.grad
+    return out
+
+
 def spawn_ranks(args):
     """`python bench.py --gpus N` (N > 1) without a launcher: start the N ranks as a child `torch.distributed.run` -- this
     process has not touched a GPU (counting devices does not) and only relays the child's exit status."""
@@ -616,7 +670,7 @@ def main():
     adaptive = args.readout == 'mp'
     model = RGCNEncoderDecoder(graph, DirectEncoder(None, fm, node_maps), readout=args.readout, num_layers=3,
                                shared_layers=False, adaptive=adaptive, weight_decay=0)
-    cpu_state = {k: v.detach().clone() for k, v in model.state_dict().items()}
+    cpu_state = {k: v.detach().clone() for k, v in model.state_dict().items()} if args.full else None     # (cpu_baseline)
     model = model.to(device)
     model.validate = False                                # no per-call D2H flag read in the timed loop
     rng = np.random.RandomState(1000 + rank)
@@ -708,14 +762,15 @@ def main():
 
     # (learned readouts: mlp rides on the chain form -- csrc/step_chain.h --, targetmlp / concat on the level form)
     level_form = bool(learned and use_fused and (fstep.flags & 2))      # (MPQE_STEP_NO_CHAIN)
-    if use_fused and not args.no_self_check and not args.sparse_tables:      # (the check compares DENSE gradients)
+    # --full: the pre-timing checks (a plain run only sets up, warms up and times)
+    if args.full and use_fused and not args.no_self_check and not args.sparse_tables:      # (the check compares DENSE gradients)
         self_check(model, fstep, packed[0], pool[0], world)
         if fresh:
             fresh_check(fstep, descs[0], fresh_ids[0][0], pool[0], exact=not level_form)
     xnote = None
     if exchange is not None and exchange.transport_note:
         xnote = exchange.transport_note
-    if exchange is not None:
+    if args.full and exchange is not None:
         # the exchange against the literal dense all-reduce on one step (N-rank hardware is not available to the tests):
         # a mismatch falls back to the dense form, and says so
         xcheck = exchange_check(fstep, exchange, xplans[0], packed[0])
@@ -731,11 +786,12 @@ def main():
     # repeated `--repeats` times (each one bracketed the same way, each step on the next fresh id set) and the MEDIAN
     # block is the reported one, with min and max beside it. Per block the time is the max over ranks.
     blocks = []
+    loss = None
     for r in range(max(1, args.repeats)):
         barrier()
         t0 = time.perf_counter()
         for i in range(args.steps):
-            one_step(step_no + i)
+            loss = one_step(step_no + i)
         barrier()
         blocks.append(time.perf_counter() - t0)
         step_no += args.steps
@@ -745,8 +801,11 @@ def main():
             exchange.check()
         else:
             fstep.check()
+    if args.dump_outputs and rank == 0 and loss is not None:
+        # before anything else runs a step: the gradients are still those of the last timed step
+        dump_outputs(args.dump_outputs, step_outputs(model, loss))
     split_us = None
-    if world > 1 and use_fused:
+    if args.full and world > 1 and use_fused:
         # where an N-rank step's time goes (outside the timed region): events around the step's own launches and around the
         # gradient exchange, on the stream both run on, over the same fresh-id steps
         evs = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(min(20, max(4, args.steps)))]
@@ -782,10 +841,10 @@ def main():
         blocks = [float(v) for v in t.tolist()]
     elapsed = float(np.median(blocks))
     replay_ms = None
-    if fresh and rank == 0 and world == 1:
+    if args.full and fresh and rank == 0 and world == 1:
         # secondary figure: the replay of 4 pre-packed steps (round 2's headline; nothing id-dependent left in the loop)
         rb = []
-        for r in range(max(1, min(args.repeats, 9))):
+        for r in range(min(args.repeats, 9) if args.repeats > 1 else 9):
             barrier()
             t0 = time.perf_counter()
             for i in range(args.steps):
@@ -849,7 +908,7 @@ def main():
                                                 'not in use: %s' % (xnote or 'fell back'))
         if split_us is not None:
             out['exchange']['us_per_step'] = split_us[1]
-    if rank == 0 and use_fused and world == 1 and not args.no_pack_ms:
+    if args.full and rank == 0 and use_fused and world == 1 and not args.no_pack_ms:
         # host side of a step whose ids arrive from the HOST (a data loader's numpy arrays): packing = descriptors (cached
         # per formula) + ids into the packed step's pinned buffer, which the kernels read in place (--host-ids copy: one host-to-device copy per
         # pack, in stream order). Outside `value` (SURVEY.md 8d excludes collation;
@@ -908,7 +967,7 @@ def main():
                           'flat_host_ids_loop_per_step': None if t_flat is None else t_flat * 1e3,
                           'note': 'pack_and_run_loop_per_step: per-batch host arrays [B, A] / [B] -> layout conversion + copy '
                                   '+ step; flat_host_ids_loop_per_step: host ids already in the library layout -> copy + step'}
-    if rank == 0:
+    if args.full and rank == 0:
         flops_fwd, flops_all, bytes_all, launches = layer_work(pool[0], model)
         executed = None
         default_workload = args.readout == 'mp' and args.batch_size == 512 and D == 128 and args.kg == 'aifb'
@@ -976,6 +1035,7 @@ def main():
             cfg = dict(readout=args.readout, scatter_op='add', num_layers=3, adaptive=adaptive, weight_decay=0)
             out['cpu_baseline'] = cpu_baseline(args, schema, cpu_state, node_maps, model.rel_ids, model.mode_ids,
                                                cfg, args.cpu_seconds)
+    if rank == 0:
         print(json.dumps(out))
     if world > 1:
         import torch.distributed as dist

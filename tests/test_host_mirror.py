@@ -123,6 +123,35 @@ def test_bench_refuses_more_ranks_than_gpus():
     assert q.returncode != 0 and b'WORLD_SIZE' in q.stderr
 
 
+def test_bench_dump_outputs_within_budget(tmp_path):
+    """bench.py --dump-outputs: arrays that fit the byte budget are written whole (float32, their own shape); past it the
+    largest is a fixed, seeded sample of its elements with their flat indices beside it -- the same files every time."""
+    import bench
+    g = torch.Generator().manual_seed(0)
+    arrays = {'loss': torch.rand(12, generator=g), 'grad.a': torch.rand(64, 32, generator=g),
+              'grad.b': torch.rand(300, 128, generator=g)}
+    whole, sampled = bench.dump_outputs(str(tmp_path / 'all'), arrays)
+    assert sorted(whole) == sorted(arrays) and sampled == []
+    for k, v in arrays.items():
+        x = np.load(str(tmp_path / 'all' / (k + '.npy')))
+        assert x.dtype == np.float32
+        np.testing.assert_array_equal(x, v.numpy())
+    limit = 64 << 10
+    for run in ('s1', 's2'):
+        whole, sampled = bench.dump_outputs(str(tmp_path / run), arrays, limit=limit)
+        assert sorted(whole) == ['grad.a', 'loss'] and sampled == ['grad.b']
+    files = sorted(os.listdir(str(tmp_path / 's1')))
+    assert files == ['grad.a.npy', 'grad.b.index.npy', 'grad.b.npy', 'loss.npy']
+    assert files == sorted(os.listdir(str(tmp_path / 's2')))
+    loaded = {f: np.load(str(tmp_path / 's1' / f)) for f in files}
+    assert sum(a.nbytes for a in loaded.values()) <= limit
+    idx = loaded['grad.b.index.npy']
+    assert idx.dtype == np.float64 and len(idx) > 1000 and np.all(np.diff(idx) > 0)
+    np.testing.assert_array_equal(loaded['grad.b.npy'], arrays['grad.b'].reshape(-1).numpy()[idx.astype(np.int64)])
+    for f in files:
+        assert open(str(tmp_path / 's1' / f), 'rb').read() == open(str(tmp_path / 's2' / f), 'rb').read(), f
+
+
 def test_graft_entry_expects_this_abi():
     """__graft_entry__.build() asserts the library's ABI version: keep the number there in step with the library's."""
     import os

@@ -116,8 +116,9 @@ def test_bench_gpus_flag_starts_its_ranks(backend='gloo'):
     root = os.path.dirname(HERE)
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env['HSA_ENABLE_IPC_MODE_LEGACY'] = '0'
+    # (--full: the exchange is checked against the dense all-reduce before timing, which exchange_note reports on)
     p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--backend', backend, '--steps', '2',
-                        '--warmup', '1', '--repeats', '1', '--no-cpu-baseline', '--no-scatter'], env=env, cwd=root,
+                        '--warmup', '1', '--repeats', '1', '--full', '--no-cpu-baseline', '--no-scatter'], env=env, cwd=root,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.startswith('{')]

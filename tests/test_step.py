@@ -388,6 +388,15 @@ def test_step_with_device_batch_weights_and_query_out(be, D, readout, adaptive, 
         q_ref = np.concatenate([ref_cpu.encode_queries(params, cfg, node_map, b['formula'], b['col']).detach().numpy()
                                 for b in batches])
         np.testing.assert_allclose(qs[0], q_ref, rtol=1e-5, atol=1e-6)
+
+    def assert_same_grads(a, b):
+        # (level form: the entity-table gradient rows are added with fp32 atomics -- include/mpqe_amd.h, touch plan: equal
+        # up to the order of the additions -- so two runs may differ there by a few fp32 ulps of the table's largest entry)
+        for k in a:
+            atol = 1e-7
+            if not chain and k.startswith('enc.feat-'):
+                atol += 8 * float(np.finfo(np.float32).eps) * float(np.abs(b[k]).max())
+            np.testing.assert_allclose(a[k], b[k], rtol=1e-5, atol=atol, err_msg=k)
     # the same step with HOST weights: identical gradients (regulariser included), and once more with extras first and a
     # plain call last on the same resident table (the library writes the host weights back)
     for p in params.values():
@@ -395,8 +404,7 @@ def test_step_with_device_batch_weights_and_query_out(be, D, readout, adaptive, 
     for b in batches:
         b['weight'] = float(np.float32(b['weight']))
     l_h, _, _, g_h, _ = run_step(be, schema, mode_ids, params, node_map, cfg, batches, 1.0, flags=_capi.STEP_ZERO_GRADS)
-    for k in grads:
-        np.testing.assert_allclose(grads[k], g_h[k], rtol=1e-5, atol=1e-7, err_msg=k)
+    assert_same_grads(grads, g_h)
     saved = [b['weight'] for b in batches]
     l2, _, _, g2, _ = run_step(be, schema, mode_ids, params, node_map, cfg, batches, 1.0, flags=_capi.STEP_ZERO_GRADS,
                                dev_weights=True, repeat=2, then_plain=True)
@@ -406,8 +414,7 @@ def test_step_with_device_batch_weights_and_query_out(be, D, readout, adaptive, 
     l3, _, _, g3, _ = run_step(be, schema, mode_ids, params, node_map, cfg, batches, 1.0, flags=_capi.STEP_ZERO_GRADS)
     for b, w in zip(batches, saved):
         b['weight'] = w
-    for k in g2:
-        np.testing.assert_allclose(g2[k], g3[k], rtol=1e-5, atol=1e-7, err_msg=k)
+    assert_same_grads(g2, g3)
 
 
 @pytest.mark.parametrize('readout,adaptive,D', [('mp', True, 64), ('mlp', False, 64), ('sum', False, 128)])

@@ -30,17 +30,17 @@ for v in "$@"; do
   case $mode in
     tests)
       [ $rep = 1 ] && { timeout -k 10 400 python3 -m pytest tests/test_step.py -m gpu -x -q > $out/t_$v.log 2>&1 || { echo "TESTS FAILED for $v"; tail -5 $out/t_$v.log; exit 1; }; }
-      timeout -k 10 200 python3 bench.py --no-cpu-baseline --no-scatter $flags > $out/b_$v$rep.json 2> $out/b_$v$rep.err; summ $out/b_$v$rep.json "$v $rep";;
+      timeout -k 10 200 python3 bench.py --full --repeats 0 --no-cpu-baseline --no-scatter $flags > $out/b_$v$rep.json 2> $out/b_$v$rep.err; summ $out/b_$v$rep.json "$v $rep";;
     bench)
-      timeout -k 10 200 python3 bench.py --no-cpu-baseline --no-scatter $flags > $out/b_$v$rep.json 2> $out/b_$v$rep.err; summ $out/b_$v$rep.json "$v $rep";;
+      timeout -k 10 200 python3 bench.py --full --repeats 0 --no-cpu-baseline --no-scatter $flags > $out/b_$v$rep.json 2> $out/b_$v$rep.err; summ $out/b_$v$rep.json "$v $rep";;
     timeline)
       timeout -k 10 200 python3 tools/chain_timeline.py > $out/tl_$v$rep.txt 2>&1
       timeout -k 10 200 python3 tools/chain_timeline.py --tail >> $out/tl_$v$rep.txt 2>&1
       echo "== $v $rep"; grep -h "makespan\|BWD:\|shader clock" $out/tl_$v$rep.txt | head -8
-      timeout -k 10 200 python3 bench.py --no-cpu-baseline --no-scatter $flags > $out/b_$v$rep.json 2> $out/b_$v$rep.err; summ $out/b_$v$rep.json "$v $rep";;
+      timeout -k 10 200 python3 bench.py --full --repeats 0 --no-cpu-baseline --no-scatter $flags > $out/b_$v$rep.json 2> $out/b_$v$rep.err; summ $out/b_$v$rep.json "$v $rep";;
     prof)
       [ $rep = 1 ] || continue
-      (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_$v -o p -- python3 $root/bench.py --no-cpu-baseline --no-scatter --steps 50 --repeats 3 $flags > $out/prof_$v.log 2>&1)
+      (cd "$TMPDIR" && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_$v -o p -- python3 $root/bench.py --full --no-cpu-baseline --no-scatter --steps 50 --repeats 3 $flags > $out/prof_$v.log 2>&1)
       summ $out/prof_$v.log "$v"
       python3 - <<P
 import csv

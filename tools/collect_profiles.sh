@@ -6,7 +6,7 @@
 out=$(realpath -m $1); mkdir -p $out
 root=$(pwd)
 export TMPDIR=/tmp
-B="python3 $root/bench.py --steps 20 --warmup 3 --repeats 10 --no-cpu-baseline --no-scatter --no-pack-ms --no-dropin-loop"
+B="python3 $root/bench.py --steps 20 --warmup 3 --repeats 10 --full --no-cpu-baseline --no-scatter --no-pack-ms --no-dropin-loop"
 cd /tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o s -- $B > $out/stats.log 2>&1
 timeout -k 10 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES --output-format csv -d $out/pmc_sq -- $B > $out/pmc_sq.log 2>&1
@@ -17,7 +17,7 @@ cd $root
 python3 tools/pmc_summary.py $out/pmc_sq $out/pmc_fetch $out/pmc_write $out/pmc_tcc > $out/pmc.json 2> $out/pmc.err
 timeout -k 10 200 python3 tools/chain_timeline.py > $out/timeline.txt 2>&1
 timeout -k 10 200 python3 tools/chain_timeline.py --tail >> $out/timeline.txt 2>&1
-timeout -k 10 400 python3 bench.py > $out/bench.json 2> $out/bench.err
+timeout -k 10 400 python3 bench.py --full --repeats 0 > $out/bench.json 2> $out/bench.err
 cp $out/stats/s_kernel_stats.csv $out/kernel_stats.csv 2>/dev/null
 rm -rf $out/pmc_sq $out/pmc_fetch $out/pmc_write $out/pmc_tcc $out/stats/*trace* 
 ls $out

@@ -4,7 +4,7 @@ On the MI355X box (counters go in SEPARATE passes: FETCH_SIZE takes 3 of the 4 T
 never together with --sys-trace and friends):
 
     export TMPDIR=/tmp
-    B="python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline"
+    B="python3 bench.py --steps 20 --warmup 3 --repeats 0 --full --no-cpu-baseline"
     rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES \
         --output-format csv -d gpurun_out/pmc_sq -- $B
     rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_fetch -- $B
