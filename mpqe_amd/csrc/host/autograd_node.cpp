@@ -11,12 +11,14 @@
 //   out = make_loss(p, call_id, buf)       0-dim tensor over buf's first element (its own tensor, not an autograd view: the
 //                                          reference adds into the first loss in place), grad_fn = the node
 //   p.take_dead() -> list[int]             call ids whose nodes have been destroyed (their graphs freed) since the last call
+//   p.pending() -> int                     calls whose nodes have run and wait for the pass' callback
 //   storage_use_count(t) -> int            holders of t's storage
 //
 // No arithmetic of the data path lives here.
 #include <torch/extension.h>
 #include <torch/csrc/autograd/engine.h>
 #include <torch/csrc/autograd/function.h>
+#include <torch/csrc/autograd/graph_task.h>
 #include <torch/csrc/autograd/variable.h>
 
 #include <mutex>
@@ -30,11 +32,16 @@ struct Pass {
     std::vector<at::Tensor> grads;
     std::vector<int64_t> dead;
     bool scheduled = false;
+    int task = -1;                 // the graph task (backward pass) whose callback will take ids / grads
     py::object flush;
     explicit Pass(py::object f) : flush(std::move(f)) {}
     ~Pass() {
         py::gil_scoped_acquire gil;
         flush = py::object();
+    }
+    int64_t pending() {
+        std::lock_guard<std::mutex> lock(mu);
+        return static_cast<int64_t>(ids.size());
     }
     std::vector<int64_t> take_dead() {
         std::lock_guard<std::mutex> lock(mu);
@@ -50,12 +57,21 @@ struct MarginLossNode : public torch::autograd::Node {
 
     torch::autograd::variable_list apply(torch::autograd::variable_list &&grads) override {
         bool schedule = false;
+        const int task = torch::autograd::get_current_graph_task_id();
         {
             std::lock_guard<std::mutex> lock(pass->mu);
+            if (pass->scheduled && pass->task != task) {
+                // the pass that queued the callback raised before it ran (the engine drops final callbacks on error):
+                // its calls are dropped with it, and this pass queues its own
+                pass->ids.clear();
+                pass->grads.clear();
+                pass->scheduled = false;
+            }
             pass->ids.push_back(id);
             pass->grads.push_back(grads.empty() ? at::Tensor() : grads[0]);
             if (!pass->scheduled) {
                 pass->scheduled = true;
+                pass->task = task;
                 schedule = true;
             }
         }
@@ -103,7 +119,8 @@ int64_t storage_use_count(const at::Tensor &t) { return static_cast<int64_t>(t.s
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     py::class_<Pass, std::shared_ptr<Pass>>(m, "Pass")
         .def(py::init<py::object>())
-        .def("take_dead", &Pass::take_dead);
+        .def("take_dead", &Pass::take_dead)
+        .def("pending", &Pass::pending);
     m.def("storage_use_count", &storage_use_count, "number of holders of the tensor's storage");
     m.def("make_loss", &make_loss, "0-dim loss tensor over buf[0] whose grad_fn defers to the pass' flush");
 }

@@ -157,11 +157,17 @@ class FormulaIds(object):
 
 
 class BatchIds(object):
-    """The window of a FormulaIds one collated batch covers; rides on the batch's query-graph object (`q_graphs.ids`)."""
-    __slots__ = ('fi', 'start', 'end', 'anchor_ref')
+    """The window of a FormulaIds one collated batch covers; rides on the batch's query-graph object (`q_graphs.ids`).
+    anchor_ref: the batch's own anchor_ids tensor (a copy of the window), anchor_ver: its version when collated."""
+    __slots__ = ('fi', 'start', 'end', 'anchor_ref', 'anchor_ver')
 
     def __init__(self, fi, start, end, anchor_ref=None):
         self.fi, self.start, self.end, self.anchor_ref = fi, start, end, anchor_ref
+        self.anchor_ver = None if anchor_ref is None else anchor_ref._version
+
+    def holds(self, anchor_ids):
+        """True when `anchor_ids` is the batch's tensor, not edited in place since collation: the window's ids."""
+        return anchor_ids is self.anchor_ref and anchor_ids._version == self.anchor_ver
 
 
 class QueryDataset(Dataset):
@@ -243,7 +249,7 @@ class RGCNQueryDataset(QueryDataset):
         if tmpl is None:        # (immutable: one per formula and batch size)
             tmpl = templates[end - start] = ops.Template(formula.query_type, end - start, edge_type)
         graph = QueryGraphBatch(tmpl)
-        anchor_ids = torch.from_numpy(fi.anchors[start:end])
+        anchor_ids = torch.from_numpy(fi.anchors[start:end].copy())      # (the batch's own: edits stay in it)
         graph.ids = BatchIds(fi, start, end, anchor_ids)
         return formula, all_queries[start:end], anchor_ids, torch.from_numpy(var_ids.copy()), graph
 

@@ -186,6 +186,7 @@ class DropIn(object):
         self._arena = None
         self._free = []
         self._pending = []         # calls whose nodes ran in the current backward pass
+        self._pending_task = -1    # (the graph task of that pass: torch._C._current_graph_task_id())
         self._seq = 0
         self._full_lists = {}
         self._grb = self._rng = None
@@ -397,8 +398,11 @@ class DropIn(object):
                 break
         else:
             ar = _Arena(max(need, 1 << 14))
-            if len(self._free) > 16:               # (arenas whose nodes never ran: let them go with their graphs)
-                self._free = [c for c in self._free if c.live > 0][-16:]
+            if len(self._free) > 16:
+                # arenas whose nodes never ran go with their graphs (their calls hold them); one without nodes whose last
+                # reader has not reported stays: its pinned block must not be handed out again while the device reads it
+                busy = [c for c in self._free if c.live == 0 and not self._done(c)]
+                self._free = busy + [c for c in self._free if c.live > 0][-16:]
         self._arena = ar
         return ar
 
@@ -443,7 +447,7 @@ class DropIn(object):
         oa, og = ar.na, ar.ng
         fast = ids is not None and ids.end - ids.start == B and ids.fi.A == A
         # anchors, slot-major
-        if fast and (anchor_ids is None or anchor_ids is ids.anchor_ref):
+        if fast and (anchor_ids is None or ids.holds(anchor_ids)):
             sm, lo, hi = ids.fi.anchors_sm, ids.start, ids.end
             for i in range(A):
                 ar.a_np[oa + i * B: oa + (i + 1) * B] = sm[i, lo:hi]
@@ -545,7 +549,7 @@ class DropIn(object):
         rng = self._mt()
         if (ids is not None and rng is not None and r.P_seen is step.P and r.ws_seen is (step._ws if lane is None else lane.ws)
                 and ids.end - ids.start == B
-                and ids.fi.A == A and (anchor_ids is None or anchor_ids is ids.anchor_ref)
+                and ids.fi.A == A and (anchor_ids is None or ids.holds(anchor_ids))
                 and torch._C._cuda_getDevice() == self.dev_index):
             # the batch is a window of its formula's id arrays and this record has run before: ONE host call copies the
             # window into the arena, draws the negatives and launches (csrc/host/pyhost.c: margin_call)
@@ -598,7 +602,15 @@ class DropIn(object):
     # ------------------------------------------------------------------------------------------- backward
     def _on_backward(self, call, g):
         pending = self._pending
+        task = torch._C._current_graph_task_id()
+        if pending and task != self._pending_task:
+            # the pass that queued the callback raised before it ran (the engine drops final callbacks on error): its calls
+            # are dropped with it
+            for c in pending:
+                c.g = None
+            pending.clear()
         if not pending:
+            self._pending_task = task
             torch.autograd.Variable._execution_engine.queue_callback(self._flush)
         if g.dtype != torch.float32 or g.device != self.device:
             g = g.to(device=self.device, dtype=torch.float32)
@@ -641,20 +653,17 @@ class DropIn(object):
         step = self.step
         # p.grad: None everywhere (optimizer.zero_grad()) -> the step's own zero fill; otherwise added to what is there
         params, views = step.params, step._views
-        if step.zero_next:                     # (FlatOptimizer.zero_grad(): every p.grad is still its view)
-            zero, step.zero_next = True, False
-        else:
-            zero = True
-            for p in params:
-                if p.grad is not None:
-                    zero = False
-                    break
-            if not zero:
-                for p, v in zip(params, views):
-                    if p.grad is None:
-                        v.zero_()
-                    elif p.grad is not v:
-                        v.copy_(p.grad)
+        zero = True
+        for p in params:
+            if p.grad is not None:
+                zero = False
+                break
+        if not zero:
+            for p, v in zip(params, views):
+                if p.grad is None:
+                    v.zero_()
+                elif p.grad is not v:
+                    v.copy_(p.grad)
         step.bind_grads()
         # groups the library can run as one step: consecutive calls of one arena with one margin, at most MAX_CALLS
         groups, cur, nids = [], [], 0

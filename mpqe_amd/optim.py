@@ -113,10 +113,11 @@ class FlatOptimizer(object):
         _capi.check(ops.lib(), st, 'optimiser step')
 
     def zero_grad(self, set_to_none=True):
-        """torch.optim's call (reference train_helpers.py:78) for the drop-in entry points (mpqe_amd/dropin.py): the next
-        backward pass's fused step zero-fills the flat gradient buffer itself -- nothing is written here, and no p.grad is
-        touched (re-binding ~30 parameters' .grad costs more interpreter time than the step's call)."""
-        self.fused.zero_next = True
+        """torch.optim's call (reference train_helpers.py:78) for the drop-in entry points (mpqe_amd/dropin.py): one zero fill
+        of the flat gradient buffer on the current stream -- every p.grad is a view of it and stays bound (re-binding ~30
+        parameters' .grad costs more interpreter time than the fill). The next pass adds into it, whatever path its terms
+        take: drop-in calls, module-path terms, or both."""
+        self.fused.flat_grad.zero_()
 
     def state_dict(self):
         return {'t': self.t, 'exp_avg': self.exp_avg, 'exp_avg_sq': self.exp_avg_sq}
@@ -134,7 +135,7 @@ class FlatOptimizer(object):
 #     optimizer = optim.Adam([p for p in enc_dec.parameters() if p.requires_grad], lr=args.lr)
 # `from mpqe_amd import optim` in place of `from torch import optim` keeps those lines as they are: when the parameters are
 # exactly those of ONE model on the fused step (mpqe_amd/dropin.py) the update is FlatOptimizer's one launch over the flat
-# buffers (and zero_grad() a flag), otherwise the torch optimiser itself.
+# buffers (and zero_grad() one zero fill of them), otherwise the torch optimiser itself.
 import weakref
 
 _OWNERS = weakref.WeakValueDictionary()           # id(parameter) -> its model (mpqe_amd/model.py registers them)

@@ -213,16 +213,14 @@ def encode_queries(params, cfg, node_map, formula, col, layer_fn=rgcn_layer_refs
     dict from collate(). Returns the query embeddings [B, D]; fills `keep`
     (a dict) with x0, every layer output and the readout when given."""
     B, A, N = col['B'], col['A'], col['N']
-    D = params['mode_embeddings.weight'].shape[1]
     anchor_ids = torch.as_tensor(col['anchor_ids'])
-    x = torch.empty(B, N, D)
     cols = []
     for i, mode in enumerate(formula.anchor_modes):
         cols.append(direct_encode(params['enc.feat-%s.weight' % mode], node_map,
                                   anchor_ids[:, i]))
     var = params['mode_embeddings.weight'][torch.as_tensor(col['var_ids'])]
     x = torch.cat([c[:, None, :] for c in cols] + [var[None].expand(B, -1, -1)], dim=1)
-    x = x.reshape(B * N, D)
+    x = x.reshape(B * N, -1)
     ei = torch.as_tensor(col['edge_index'])
     et = torch.as_tensor(col['edge_type'])
     if keep is not None:

@@ -388,7 +388,7 @@ def test_python_autograd_node_fallback_gives_the_same(monkeypatch):
 
 def test_torch_optim_shaped_constructors_switch_to_the_flat_update():
     """`from mpqe_amd import optim` in place of `from torch import optim` (reference train.py:83-88): optim.Adam / optim.SGD
-    over exactly one fused model's parameters are FlatOptimizer's one launch (zero_grad a flag); anything else is the torch
+    over exactly one fused model's parameters are FlatOptimizer's one launch (zero_grad one zero fill); anything else is the torch
     optimiser. Three iterations of the reference loop give the parameters torch.optim.Adam gives on the same model."""
     from mpqe_amd import optim
     from mpqe_amd.data_utils import get_queries_iterator

@@ -306,6 +306,76 @@ def test_collate_fn_ids_are_the_query_objects_ids():
     assert seen > 0
 
 
+def test_collate_fn_batches_own_their_anchor_ids():
+    """collate_fn's anchor_ids are the batch's own copy of the formula's window: an in-place edit of one batch stays in it
+    (later batches of the formula, the same window included, are as the queries say; FormulaIds is untouched), and the
+    batch's BatchIds stops vouching for the window once its tensor was edited (the drop-in's fast path reads the window)."""
+    from mpqe_amd import synthetic
+    from mpqe_amd.data_utils import get_queries_iterator
+    schema = synthetic.make_schema(*synthetic.KG_SHAPES['tiny'], seed=1)
+    rng = np.random.RandomState(3)
+    f = synthetic.sample_formula(schema, '3-inter', rng)
+    queries = {f: synthetic.sample_queries(schema, f, 24, rng, n_neg=5, n_hard=2)}
+
+    class M(object):
+        mode_ids = {m: i for i, m in enumerate(schema.modes)}
+        rel_ids = {}
+    for m in schema.relations:
+        for (to, name) in schema.relations[m]:
+            M.rel_ids[(m, name, to)] = len(M.rel_ids)
+            M.rel_ids.setdefault((to, name, m), len(M.rel_ids))
+    want = np.array([q.anchor_nodes for q in queries[f]], dtype=np.int64)
+    np.random.seed(5)
+    it = get_queries_iterator(queries, 8, M)                      # windows 0, 8, 16, then 0 again
+    formula, qs, anchor_ids, var_ids, g = next(it)
+    fi = g.ids.fi
+    assert g.ids.holds(anchor_ids) and not g.ids.holds(anchor_ids.clone())
+    anchor_ids[2, 1] = anchor_ids[6, 1]
+    anchor_ids.add_(0)
+    assert not g.ids.holds(anchor_ids)
+    assert anchor_ids[2, 1].item() == want[6, 1]
+    np.testing.assert_array_equal(fi.anchors, want)
+    np.testing.assert_array_equal(fi.anchors_sm, want.T)
+    for k in range(1, 6):
+        _, qs, a, _, g = next(it)
+        lo = (8 * k) % 24
+        assert g.ids.start == lo and g.ids.holds(a)
+        np.testing.assert_array_equal(a.numpy(), want[lo:lo + 8])
+        a[0, 0] = -1                                             # (each batch's edit stays its own)
+
+
+def test_oracle_runs_in_float64():
+    """oracle/ref_cpu.py keeps the dtype of the parameters it is given: float64 parameters give a float64 loss, node states
+    and gradients (the float64 reference of tests/dropin_oracle.py relies on it)."""
+    from mpqe_amd import synthetic
+    from mpqe_amd.data_utils import make_feature_modules
+    from mpqe_amd.encoders import DirectEncoder
+    from mpqe_amd.model import RGCNEncoderDecoder
+    from oracle import ref_cpu
+    torch.manual_seed(0)
+    D = 16
+    schema = synthetic.make_schema(*synthetic.KG_SHAPES['tiny'], seed=3)
+    graph = synthetic.SchemaGraph(schema, D)
+    fm, node_maps = make_feature_modules(schema.ids, D, schema.num_entities)
+    rng = np.random.RandomState(1)
+    for readout in ('mp', 'mlp', 'max', 'concat', 'targetmlp'):
+        model = RGCNEncoderDecoder(graph, DirectEncoder(None, fm, node_maps), readout=readout, num_layers=3,
+                                   shared_layers=False, adaptive=readout == 'mp', weight_decay=1e-3)
+        params = {k: v.detach().double().clone().requires_grad_(True) for k, v in model.state_dict().items()}
+        cfg = dict(readout=readout, scatter_op='add', num_layers=3, adaptive=readout == 'mp', weight_decay=1e-3)
+        formula = synthetic.sample_formula(schema, '3-inter_chain', rng)
+        qs = synthetic.sample_queries(schema, formula, 9, rng)
+        col = ref_cpu.collate(formula, qs, model.rel_ids, model.mode_ids)
+        for layer_fn in (ref_cpu.rgcn_layer_refseq, ref_cpu.rgcn_layer_grouped):
+            keep = {}
+            q = ref_cpu.encode_queries(params, cfg, node_maps, formula, col, layer_fn, keep)
+            loss = ref_cpu.margin_loss(params, cfg, node_maps, formula, col, [x.target_node for x in qs],
+                                       [x.neg_samples[0] for x in qs], layer_fn=layer_fn, encode_twice=False)
+            loss.backward()
+            got = [keep['x0'], q, loss] + keep['layers'] + [p.grad for p in params.values() if p.grad is not None]
+            assert {t.dtype for t in got} == {torch.float64}, (readout, layer_fn.__name__)
+
+
 def test_queries_iterator_equals_the_dataloader_form():
     """get_queries_iterator (reference data_utils.py:412-426) without torch's DataLoader: the same batches (formula draws,
     windows across epoch ends, Query objects, id tensors) and the same numpy AND torch random streams as
