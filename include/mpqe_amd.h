@@ -60,8 +60,7 @@ extern "C" {
                                         bits 8.. say which (diagnostics: 0x100 a pre-pass
                                         vector, 0x200 the transposed copies, 0x400 a
                                         completion counter, 0x800 a vector op's inputs,
-                                        0x1000 the fused tail's arrivals, 0x2000 the
-                                        touch plan's sort)                                 */
+                                        0x2000 the touch plan's sort)                      */
 
 /* query templates, reference data_utils.py:325-362 */
 enum {
@@ -662,16 +661,10 @@ void mpqe_debug_tail_stamps(void *device_buffer, size_t num_blocks);
 /* Named diagnostics switches (timing experiments; tests that force a rarely taken path, e.g. "TOUCH_MULTI_LAUNCH" = the
  * multi-launch sort (csrc/radix_sort.h) instead of the one-launch sort, "TSORT_FAIL" = the in-step sort gives up as if its workgroups were not
  * co-resident, "GEN_SLOTS" = grid size of the persistent gather-GEMMs, "PROLOGUE_LAST" = 1 / 0: the chain launch's prologue
- * items behind / in front of its chain workgroups whatever their number, "POST_IN_CHAIN" = the backward post-pass as roles of
- * the chain launch with the tiles a launch of their own, "NO_RUNS" = the reduction's table workgroups take every sorted
- * position of the touch plan instead of its compacted run starts, "DUMP_PLAN" = the step's plan and launch shape on stderr). set != 0
- * stores `value` under `name`, set == 0 removes it. Process-global (see Conventions).                    */
+ * items behind / in front of its chain workgroups whatever their number, "NO_RUNS" = the reduction's table workgroups take
+ * every sorted position of the touch plan instead of its compacted run starts, "DUMP_PLAN" = the step's plan and launch shape
+ * on stderr). set != 0 stores `value` under `name`, set == 0 removes it. Process-global (see Conventions).      */
 void mpqe_debug_option(const char *name, int value, int set);
-/* The launch forms of the fused step that were built, proven bit-equal and measured SLOWER (the post-pass as closures
- * "CLOSURE", the loss + table rows as roles of the weight-gradient launch "EARLY_ROWS", the reduction fused into it
- * "FUSE_TAIL", range-per-workgroup table sums "ROWS_MULTI", the post-pass alone in the chain launch "POST_IN_CHAIN") are NOT
- * in the shipped library: they compile with -DMPQE_EXPERIMENTS only (tools/build_variant.sh). 1 = this build has them. */
-int mpqe_debug_has_experiments(void);
 
 #ifdef __cplusplus
 }

@@ -184,8 +184,6 @@ struct UOp {
     int u_vec[UOP_MAX_TERMS];          // R1
     int r1_layer, r1_rel;
     unsigned wait_mask;                // merged launch: bit b = the op reads rows the chain workgroups of batch b write
-    int through;                       // fused tail: the op's output is read by the reduction (a rank-1 term's v, a row of
-                                       // `parts`): written through, so that the same launch's reduction workgroups see it
 };
 
 struct Blob {
@@ -258,16 +256,6 @@ __device__ __forceinline__ float *pick_grad(float *const *arr, int li) {
 
 #include "step_chain.h"
 #include "step_uniform.h"
-#if MPQE_HAS_EXPERIMENTS
-#include "step_closure.h"
-#else
-struct ClosureArgs {       // (the post-pass as closures: an experiment, not in this build -- csrc/step_closure.h)
-    int ncl;
-};
-struct ClBlock {
-    int batch;
-};
-#endif
 #include "step_touch.h"
 #include "grad_w_reg.h"
 #include "step_readout.h"
@@ -389,7 +377,6 @@ struct PrepArgs {
     int strail;               // != 0: the launch's LAST strail workgroups instead (diagnostics switch TSORT_TRAIL)
     int late;                 // diagnostics ("HANDOFF_LATE"): the first transpose workgroup counts itself in ~1 s late -- a producer
                               // that lost its CU to another process: its consumers' bounded waits run out (MPQE_FLAG_INTERNAL)
-    unsigned *tail_arrive;    // fused tail: the arrival counter of the step's weight-gradient launch, zeroed here; or NULL
     int *runs_count;          // the number of run starts the weight-gradient launch will compact (touch_runs_block), zeroed here; or NULL
     int ublocks, tblocks;     // vector-op workgroups, transpose workgroups
     int lead;                 // prologue workgroups in front of the chain workgroups: sblocks + ublocks + tblocks rounded
@@ -1600,12 +1587,6 @@ static int step_ex(const mpqe_step_params_t *P, const mpqe_step_batch_t *B, int 
     // workgroups and queue behind them. Hence: merged up to 9/8 x CUs chain workgroups unless a flag says otherwise.
     const bool merged = use_chain && backward && NL == 1 && !(P->flags & MPQE_STEP_SPLIT_TAIL) &&
                         ((P->flags & MPQE_STEP_MERGE_TAIL) || hp.blk_off[nb] <= STEP_CUS + STEP_CUS / 8);
-    // ... or only the POST-PASS (its vector ops are few, light, and a three-level dependence chain: it then runs while the
-    // slower batches' chain workgroups are still at work, and the weight-gradient launch is its tiles alone). Experiment:
-    // mpqe_debug_option POST_IN_CHAIN
-    const bool post_only = use_chain && backward && NL == 1 && !merged && D % 64 == 0 && !hp.uops_b.empty() &&
-                           hp.closures.empty() && exp_on("POST_IN_CHAIN") && !exp_on("FUSE_TAIL");
-    const bool pic = merged || post_only;          // the post-pass rides in the chain launch
     {
         ZeroSegs &zs = pa.zs;
         if (backward && !phase_bwd && !phase_score && (P->flags & MPQE_STEP_ZERO_GRADS)) {     // (step in several calls: the first one fills)
@@ -1613,7 +1594,7 @@ static int step_ex(const mpqe_step_params_t *P, const mpqe_step_batch_t *B, int 
                 if (!ptr || n <= 0) return;
                 // (merged launch: a root matrix that tiles / a rank-1 op of the SAME launch write whole is not zero-filled
                 // -- the fill would race with its writers, who store instead of adding)
-                for (size_t k = 0; pic && k < hp.whole_roots.size(); ++k)
+                for (size_t k = 0; merged && k < hp.whole_roots.size(); ++k)
                     if (gp.root[hp.whole_roots[k]] == ptr) return;
                 for (int k = 0; k < zs.count; ++k)
                     if (zs.p[k] == ptr) return;                  // shared layers repeat their buffers
@@ -1766,10 +1747,9 @@ static int step_ex(const mpqe_step_params_t *P, const mpqe_step_batch_t *B, int 
             pa.slots = reinterpret_cast<const WtSlot *>(db + hp.o_wtslots);
             pa.WT = WT;
             pa.wt_count = epoch_f + 32;
-            pa.tail_arrive = nullptr;      // (set below once the launch form is known)
             pa.late = dbg_on("HANDOFF_LATE") ? 1 : 0;
-            pa.fwd_done = pic && pa.ublocks > 0 ? epoch_f + 33 : nullptr;
-            pa.ua.vt_through = pic ? 1 : 0;
+            pa.fwd_done = merged && pa.ublocks > 0 ? epoch_f + 33 : nullptr;
+            pa.ua.vt_through = merged ? 1 : 0;
         } else if (zblocks > 0) {
             hipLaunchKernelGGL(step_zero_kernel, dim3((unsigned)zblocks), dim3(256), 0, s, zs);
         }
@@ -1804,12 +1784,8 @@ static int step_ex(const mpqe_step_params_t *P, const mpqe_step_batch_t *B, int 
     ta.D = D;
     ta.tile_n = hp.tile_n;
     ta.ux = 0;
-    memset(&ta.ca, 0, sizeof(ta.ca));
-    ta.clpad = 0;
-    ta.extra0 = -1;
     ta.runs_front = ta.runs_n = 0;
     ta.runs_out = nullptr;
-    ta.tm_blocks = 0;
     ta.node_map = nm;
     ta.map_len = (long long)P->node_map_len;
     ta.anchor_ids = ids;
@@ -1825,20 +1801,15 @@ static int step_ex(const mpqe_step_params_t *P, const mpqe_step_batch_t *B, int 
     ub.ops = reinterpret_cast<const UOp *>(db + hp.o_uopb);
     ub.nops = (int)hp.uops_b.size();
     ub.epoch = epoch_b;
-    // the step's reduction: a launch of its own, or (chain form, split tail, switch FUSE_TAIL) trailing workgroups of the
-    // weight-gradient launch
+    // the step's reduction: a launch of its own
     ReduceArgs ra;
     memset(&ra, 0, sizeof(ra));
     ra.nmat = -1;
     const long long r_elems = (long long)D * D;
     const unsigned r_gx = (unsigned)((r_elems + 255) / 256);
     unsigned r_trows = 0;         // entity-table gradient rows: 256 / (D / 4) sorted positions per workgroup
-    // (mpqe_debug_option ROWS_MULTI: a range of sorted positions per table workgroup, 344 instead of 2 752 workgroups for the
-    // AIFB step -- measured 3 us SLOWER per step: a range is 3 - 4 dependent round trips per lane group where 2 752
-    // independent one-run workgroups, two rounds of the chip at 6 waves per SIMD, need two each)
-    const bool rows_multi = use_touch && D % 4 == 0 && 256 % (D / 4) == 0 && D >= 64 && exp_on("ROWS_MULTI");
     if (use_touch && !(STEP_DBG & 1)) {
-        const long long per = rows_multi ? (256 / (D / 4)) * TSM_OWN : 256 / (D / 4), tblk = (hp.touch_M + per - 1) / per;
+        const long long per = 256 / (D / 4), tblk = (hp.touch_M + per - 1) / per;
         r_trows = (unsigned)((tblk + r_gx - 1) / r_gx);
     }
     ra.groups = reinterpret_cast<const RGroup *>(db + hp.o_groups);
@@ -1862,31 +1833,20 @@ static int step_ex(const mpqe_step_params_t *P, const mpqe_step_batch_t *B, int 
     ra.touch_perm = touch_layout(hp.touch_M, 0).perm;
     ra.DG = reinterpret_cast<const float *>(wb + hp.o_DG);
     ra.tabs = tabs;
-    ra.table_store = ((sparse_tables || (P->flags & MPQE_STEP_ZERO_GRADS)) ? 1 : 0) | (pic ? 2 : 0);
+    ra.table_store = ((sparse_tables || (P->flags & MPQE_STEP_ZERO_GRADS)) ? 1 : 0) | (merged ? 2 : 0);
     ra.touch_M = (long long)hp.touch_M;
     ra.touch_row_bits = touch_row_bits;
-    ra.rows_multi = rows_multi ? 1 : 0;
     ra.err = err;
     ra.notify = notify;
     ra.notify_value = notify_value;
-    const bool fuse_tail = use_chain && backward && !pic && NL == 1 && D % 64 == 0 && exp_on("FUSE_TAIL");
-    // split tail launch of the chain form: the loss and the entity-table rows depend on the chain launch alone -- they run as
-    // trailing workgroups of the weight-gradient launch, beside its tiles (136 of 256 CUs busy on the AIFB step), instead of
-    // in the reduction launch behind it (mpqe_debug_option LATE_ROWS = 1: as before)
-    const bool can_early = use_chain && backward && !pic && !fuse_tail && NL == 1 && D % 4 == 0 && 256 % (D / 4) == 0;
-    // (as trailing workgroups of the weight-gradient launch itself, mpqe_debug_option EARLY_ROWS = 1: measured slower -- that
-    // launch's 230 VGPRs allow two workgroups per CU, a table workgroup took 8.6 us and the launch 6 us longer)
-    const bool early_roles = can_early && exp_on("EARLY_ROWS");
-    // (as a light launch of their own beside the weight-gradient launch -- enqueued behind it with hipExtAnyOrderLaunch, i.e.
-    // without the queue's barrier bit -- was tried too: the flag is not honoured on gfx9 boards (hip_ext.h says so): the
-    // launch ran in order and the step took 4.4 us longer)
-    ra.early = early_roles ? 1 : 0;
-    if (early_roles) r_trows = 0;
+    // (the loss and the entity-table rows of the split tail as a light launch of their own beside the weight-gradient launch
+    // -- enqueued behind it with hipExtAnyOrderLaunch, i.e. without the queue's barrier bit -- was tried: the flag is not
+    // honoured on gfx9 boards (hip_ext.h says so): the launch ran in order and the step took 4.4 us longer)
     // The table workgroups of the reduction launch take the plan's RUN STARTS, compacted by one workgroup of the weight-gradient
     // launch (touch_runs_block), instead of every sorted position: a step's distinct rows are at most the tables' rows -- the
     // launch is sized for that bound (AIFB step: 326 workgroups instead of 2 752). mpqe_debug_option NO_RUNS = 1: as before.
-    const bool use_runs = use_touch && !pic && !fuse_tail && !early_roles && !rows_multi && NL == 1 && D % 4 == 0 &&
-                          256 % (D / 4) == 0 && !(STEP_DBG & 1) && !dbg_on("NO_RUNS");
+    const bool use_runs = use_touch && !merged && NL == 1 && D % 4 == 0 && 256 % (D / 4) == 0 && !(STEP_DBG & 1) &&
+                          !dbg_on("NO_RUNS");
     if (use_runs) {
         long long total_rows = 0;
         for (int m = 0; m < P->num_modes; ++m) total_rows += P->table_rows[m];
@@ -1895,45 +1855,25 @@ static int step_ex(const mpqe_step_params_t *P, const mpqe_step_batch_t *B, int 
         ra.runs = reinterpret_cast<const int *>(wb + hp.o_runs);
         pa.runs_count = reinterpret_cast<int *>(wb + hp.o_runs) + hp.touch_M;
     }
-    pa.tail_arrive = fuse_tail ? epoch_f + 41 : nullptr;
-    bool reduced = false;
     bool zmats_done_in_chain = false;
     auto launch_grad_w = [&](hipStream_t on, int first, int count) {
         TailArgs tl = ta;
         tl.wblock = ta.wblock + first;
         tl.wblocks = count;
         if (first == 0 && (P->flags & MPQE_STEP_ZERO_GRADS) && !zmats_done_in_chain) tl.zblocks = (int)hp.zmats.size() * ta.zper;
-        if (first == 0 && !post_only) tl.ublocks = ub.nops * ub.chunks;
+        if (first == 0) tl.ublocks = ub.nops * ub.chunks;
         int nblocks = tl.ublocks + count + tl.zblocks;
-#if MPQE_HAS_EXPERIMENTS
-        const bool closures = use_chain && first == 0 && !hp.closures.empty() && !fuse_tail;
-        if (closures) {
-            tl.ublocks = 0;
-            tl.ca.blocks = reinterpret_cast<const int *>(db + hp.o_closures);
-            tl.ca.ncl = (int)hp.closures.size();
-            tl.clpad = (tl.ca.ncl + 7) / 8 * 8;
-            nblocks = tl.clpad + count + tl.zblocks;
-        } else
-#endif
-        {
-            // chain form: two of the eight XCDs for the post-pass' vector ops, six for the tiles (AIFB step, same box,
-            // three runs each: 64.95 / 65.15 / 65.04 us against 65.70 / 65.60 / 65.47 with both kinds everywhere; one
-            // or three XCDs: 65.8 / 66.0). mpqe_debug_option TAIL_UX overrides (0 = everywhere).
-            const int uxv = mpqe_dbg_value("TAIL_UX", 2);
-            // (only while the tiles are all resident at once on the other XCDs -- two per CU: with more of them the vector
-            // ops' XCDs would stand idle for most of the launch. AIFB step with the MLP readout, 988 tiles: 64.3 -> 52.9 us)
-            if (use_chain && first == 0 && tl.ublocks >= 4 && uxv > 0 && uxv < 8 &&
-                (count <= (8 - uxv) * 2 * (STEP_CUS / STEP_XCDS) || mpqe_dbg_value("TAIL_UX", -1) > 0)) {
-                tl.ux = uxv;
-                const int ra = (tl.ublocks + tl.ux - 1) / tl.ux, rb = (count + tl.zblocks + (8 - tl.ux) - 1) / (8 - tl.ux);
-                nblocks = 8 * (ra > rb ? ra : rb);
-            }
-        }
-        if (early_roles && first == 0 && count == hp.wblocks_total) {
-            const int lpr = D / 4, pos = (256 / lpr) * TSM_OWN;
-            tl.extra0 = (nblocks + 7) / 8 * 8;
-            tl.tm_blocks = use_touch ? (int)((hp.touch_M + pos - 1) / pos) : 0;
-            nblocks = tl.extra0 + 1 + tl.tm_blocks;
+        // chain form: two of the eight XCDs for the post-pass' vector ops, six for the tiles (AIFB step, same box,
+        // three runs each: 64.95 / 65.15 / 65.04 us against 65.70 / 65.60 / 65.47 with both kinds everywhere; one
+        // or three XCDs: 65.8 / 66.0). mpqe_debug_option TAIL_UX overrides (0 = everywhere).
+        const int uxv = mpqe_dbg_value("TAIL_UX", 2);
+        // (only while the tiles are all resident at once on the other XCDs -- two per CU: with more of them the vector
+        // ops' XCDs would stand idle for most of the launch. AIFB step with the MLP readout, 988 tiles: 64.3 -> 52.9 us)
+        if (use_chain && first == 0 && tl.ublocks >= 4 && uxv > 0 && uxv < 8 &&
+            (count <= (8 - uxv) * 2 * (STEP_CUS / STEP_XCDS) || mpqe_dbg_value("TAIL_UX", -1) > 0)) {
+            tl.ux = uxv;
+            const int ra = (tl.ublocks + tl.ux - 1) / tl.ux, rb = (count + tl.zblocks + (8 - tl.ux) - 1) / (8 - tl.ux);
+            nblocks = 8 * (ra > rb ? ra : rb);
         }
         if (use_runs && first == 0 && count == hp.wblocks_total) {       // a few workgroups in front: the touch plan's run starts
             tl.runs_n = (int)((hp.touch_M + TRUNS_PER - 1) / TRUNS_PER);
@@ -1945,43 +1885,20 @@ static int step_ex(const mpqe_step_params_t *P, const mpqe_step_batch_t *B, int 
         if (nblocks <= 0) return;
         dim3 tgrid((unsigned)nblocks);
         const int zeroed = (P->flags & MPQE_STEP_ZERO_GRADS) ? 1 : 0;
-        FuseArgs fa;
-        memset(&fa, 0, sizeof(fa));
-#if MPQE_HAS_EXPERIMENTS
-        if (use_chain && fuse_tail && first == 0 && count == hp.wblocks_total) {
-            // [tiles / vector ops / zero fill as before][table rows][loss][reduction groups]: the groups wait for the tiles
-            // and vector ops, which come before them in the launch
-            fa.first = (nblocks + 7) / 8 * 8;
-            fa.gx = (int)r_gx;
-            fa.trows = (int)r_trows;
-            fa.tx = 8;
-            fa.tspan = (fa.trows * fa.gx + fa.tx - 1) / fa.tx * 8;
-            fa.arrive = epoch_f + 41;
-            ReduceArgs rf = ra;
-            rf.arrive = fa.arrive;
-            rf.phase1 = (unsigned)(tl.ublocks + count);
-            UArgs uf = ub;
-            uf.vt_through = 2;      // (only the outputs the reduction reads: UOp.through)
-            dim3 fgrid((unsigned)(fa.first + fa.tspan + 1 + (int)(hp.groups.size() * r_gx)));
-            hipLaunchKernelGGL((step_tail_kernel<LD_T, true>), fgrid, dim3(256), 0, on, sd, tl, (const float *)H,
-                               (const float *)GH, hp.level_stride, gp, zeroed, lp, uf, fa, rf);
-            reduced = true;
-        } else
-#endif
         if (use_chain)
             // (ONE tile workgroup per CU -- the launch's LDS padded beyond half a CU's -- was measured on the 988-tile step of
             // the MLP readout: 71 - 75 us against 64; two per CU stay)
             hipLaunchKernelGGL(step_tail_kernel<LD_T>, tgrid, dim3(256), 0, on, sd, tl, (const float *)H,
-                               (const float *)GH, hp.level_stride, gp, zeroed, lp, ub, fa, ra);
+                               (const float *)GH, hp.level_stride, gp, zeroed, lp, ub, ra);
         else if (fast && hp.whole_ksteps)
             hipLaunchKernelGGL(step_tail_kernel<LD_FAST>, tgrid, dim3(256), 0, on, sd, tl, (const float *)H,
-                               (const float *)GH, hp.level_stride, gp, zeroed, lp, ub, fa, ra);
+                               (const float *)GH, hp.level_stride, gp, zeroed, lp, ub, ra);
         else if (vec)
             hipLaunchKernelGGL(step_tail_kernel<LD_PRED>, tgrid, dim3(256), 0, on, sd, tl, (const float *)H,
-                               (const float *)GH, hp.level_stride, gp, zeroed, lp, ub, fa, ra);
+                               (const float *)GH, hp.level_stride, gp, zeroed, lp, ub, ra);
         else
             hipLaunchKernelGGL(step_tail_kernel<LD_SCALAR>, tgrid, dim3(256), 0, on, sd, tl, (const float *)H,
-                               (const float *)GH, hp.level_stride, gp, zeroed, lp, ub, fa, ra);
+                               (const float *)GH, hp.level_stride, gp, zeroed, lp, ub, ra);
     };
     // the readout's regulariser (model.py:486-490), after the launch that writes loss[0]
     auto ro_regulariser = [&](bool with_grads) {
@@ -2051,7 +1968,7 @@ static int step_ex(const mpqe_step_params_t *P, const mpqe_step_batch_t *B, int 
             ca.wt_count = pa.tblocks > 0 ? pa.wt_count : nullptr;
             ca.wt_blocks = wt_all;
             // (counters and their epoch advance on merged steps only: targets are epoch x count)
-            ca.done = pic ? reinterpret_cast<unsigned *>(db + hp.o_done) : nullptr;
+            ca.done = merged ? reinterpret_cast<unsigned *>(db + hp.o_done) : nullptr;
             ca.arrive = ca.done ? ca.done + hp.done_inc.size() : nullptr;
             ca.done_inc = reinterpret_cast<const int *>(db + hp.o_done_inc);
             ca.ro = hp.ro_chain ? 1 : 0;
@@ -2063,7 +1980,7 @@ static int step_ex(const mpqe_step_params_t *P, const mpqe_step_batch_t *B, int 
             long long grid_blocks = pa.lead + pa.nchain + zblocks;
             // (split tail: the untouched relation matrices' zero fill rides behind the chain workgroups; mpqe_debug_option
             // ZMATS_IN_TAIL = 1: by workgroups of the weight-gradient launch, as before)
-            const bool zm_here = !pic && backward && (P->flags & MPQE_STEP_ZERO_GRADS) && !hp.zmats.empty() && !dbg_on("ZMATS_IN_TAIL") &&
+            const bool zm_here = !merged && backward && (P->flags & MPQE_STEP_ZERO_GRADS) && !hp.zmats.empty() && !dbg_on("ZMATS_IN_TAIL") &&
                                  !phase_bwd && !phase_score;
             if (zm_here) {
                 po.zmblocks = (int)hp.zmats.size() * ta.zper;
@@ -2074,17 +1991,17 @@ static int step_ex(const mpqe_step_params_t *P, const mpqe_step_batch_t *B, int 
                 grid_blocks += po.zmblocks;
                 zmats_done_in_chain = true;
             }
-            if (pic) {
+            if (merged) {
                 unsigned *done = reinterpret_cast<unsigned *>(db + hp.o_done);
                 po.zpad = (int)((zblocks + 7) / 8 * 8);
                 if (po.zpad == 0) po.zpad = 8;              // (> 0 marks the merged launch)
-                po.zmblocks = (merged && (P->flags & MPQE_STEP_ZERO_GRADS)) ? (int)hp.zmats.size() * ta.zper : 0;
+                po.zmblocks = (P->flags & MPQE_STEP_ZERO_GRADS) ? (int)hp.zmats.size() * ta.zper : 0;
                 po.ublocks = ub.nops * ub.chunks;
                 po.na = hp.post_na;
                 po.xrank = 0;
                 for (int x = 0; x < STEP_XCDS; ++x) po.xrank |= (unsigned)(hp.post_rank[x] + 1) << (4 * x);
                 po.ppad = (po.zmblocks + po.ublocks + po.na - 1) / po.na * po.na;
-                po.wblocks = merged ? hp.wblocks_total : 0;      // (post-pass only: the tiles stay a launch of their own)
+                po.wblocks = hp.wblocks_total;
                 po.zper = ta.zper;
                 po.D = D;
                 po.tile_n = hp.tile_n;
@@ -2321,7 +2238,7 @@ static int step_ex(const mpqe_step_params_t *P, const mpqe_step_batch_t *B, int 
             hipLaunchKernelGGL(step_tail_small_kernel, dim3(small_blocks), dim3(256), 0, s, sd, ta, tabs,
                                (const float *)H, (const float *)GH, hp.level_stride);
     }
-    if (!reduced) {
+    {
         // (matrix groups first in the table, vector groups behind them: then the vector groups share ONE row of the launch)
         int nmat = 0;
         const int ng = (int)hp.groups.size();

@@ -7,7 +7,6 @@
 // role of this workgroup (uniform): chain workgroup, prologue work in front of / behind them, zero fill, then the
 // post roles: a producer is never queued behind a consumer that waits for it
     int bid = (int)blockIdx.x, role;
-    if (bid == 0 && threadIdx.x == 0 && pa.tail_arrive) *pa.tail_arrive = 0u;       // (read by the NEXT launch)
     if (bid == 0 && threadIdx.x == 0 && pa.runs_count) *pa.runs_count = 0;
     if (pa.strail && bid >= (int)gridDim.x - pa.strail) {
         if (NW == 4 || threadIdx.x < TSORT_THREADS) tsort_block(pa.ts, bid - ((int)gridDim.x - pa.strail), reinterpret_cast<unsigned *>(S.xs));

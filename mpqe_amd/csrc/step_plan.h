@@ -37,9 +37,6 @@ struct HostPlan {
     // batch-uniform node states: vector ops of the forward pre-pass / backward post-pass, rank-1 weight-gradient terms
     bool chain, uniform;
     std::vector<UOp> uops_f, uops_b;
-    // split tail launch: the backward post-pass as one closure workgroup per batch (step_closure.h); empty: the vector-op form
-    std::vector<ClBlock> closures;
-    size_t o_closures;
     std::vector<Rank1> rank1;
     int nvec, ngran;
     size_t o_uopf, o_uopb, o_rank1, o_epoch, o_gran, o_VT, o_DG, o_runs;
@@ -859,194 +856,6 @@ int make_plan(const mpqe_step_params_t *P, const mpqe_step_batch_t *B, int nb, c
                 if (hp->uops_f[k].out_vec >= 0) hp->uops_f[k].out_gran = gran_of[hp->uops_f[k].out_vec];
             for (size_t k = 0; k < hp->uops_b.size(); ++k)          // (a rank-1 op writes a matrix, not a vector: out_vec = -1)
                 if (hp->uops_b[k].out_vec >= 0) hp->uops_b[k].out_gran = gran_of[hp->uops_b[k].out_vec];
-            // ---- the same post-pass as CLOSURES (step_closure.h): per batch ONE workgroup runs its ops in dependence order,
-            // vectors handed on through LDS slots. Only where the post-pass is a launch's own role -- the split tail launch
-            // (the merged launch and the fused tail keep the vector-op form: their ops wait for other workgroups anyway).
-            hp->closures.clear();
-            long long blk_total = 0;
-            for (int i = 0; i < nb; ++i) blk_total += (sd.b[i].B + CH_GB - 1) / CH_GB;
-            const bool will_merge = hp->nlanes == 1 && !(P->flags & MPQE_STEP_SPLIT_TAIL) &&
-                                    ((P->flags & MPQE_STEP_MERGE_TAIL) || blk_total <= STEP_CUS + STEP_CUS / 8);
-            // Measured on the AIFB step (profiles/r04_*): NOT faster yet -- a closure is one wave per SIMD working through
-            // dependent LDS / scalar reads: ~1 us per item, the 3-chain batch's closure 21 - 30 us against 15.4 for the
-            // vector-op form's last op -- so it is built only on request (mpqe_debug_option CLOSURE = 1).
-#if MPQE_HAS_EXPERIMENTS
-            if (!will_merge && hp->nlanes == 1 && exp_on("CLOSURE") && !exp_on("FUSE_TAIL")) {
-                bool ok = true;
-                std::vector<ClBlock> cls;
-                std::vector<RGroup> moved;               // rank-1-only matrices whose terms span batches: reduction groups
-                // the R1 ops of uops_b are its last r1_only.size() entries, in r1_only's order
-                const size_t r1_first = hp->uops_b.size() - r1_only.size();
-                std::vector<char> r1_taken(r1_only.size(), 0);
-                for (int i = 0; i < nb && ok; ++i) {
-                    ClBlock cb;
-                    memset(&cb, 0, sizeof(cb));
-                    cb.batch = i;
-                    std::unordered_map<int, int> slot_of_vec, slot_of_part;
-                    int nslots = 0;
-                    auto add_pre = [&](int kind, int row, int nrows) -> int {
-                        if (cb.npre >= CL_MAX_PRE) { ok = false; return 0; }
-                        ClPreRec &r = cb.pre[cb.npre++];
-                        r.kind = kind;
-                        r.row = row;
-                        r.nrows = nrows;
-                        r.slot = nslots++;
-                        r.out_vec = -1;
-                        return r.slot;
-                    };
-                    auto part_slot = [&](int row0, int nrows) -> int {      // the column sum of rows [row0, row0 + nrows) of `parts`
-                        auto it = slot_of_part.find(row0);
-                        if (it != slot_of_part.end()) return it->second;
-                        const int sl = add_pre(3, row0, nrows);
-                        slot_of_part[row0] = sl;
-                        return sl;
-                    };
-                    auto vt_slot = [&](int v) -> int {                      // a copy of VT row v (a pre-pass vector)
-                        auto it = slot_of_vec.find(v);
-                        if (it != slot_of_vec.end()) return it->second;
-                        const int sl = add_pre(2, v, 1);
-                        slot_of_vec[v] = sl;
-                        return sl;
-                    };
-                    // the batch's column-sum vectors somebody reads (UOP_RED of the vector-op form): slot + VT row
-                    for (size_t k = 0; k < r1_first && ok; ++k) {
-                        const UOp &o = hp->uops_b[k];
-                        if (o.kind != UOP_RED || vinfo[o.out_vec].batch != i) continue;
-                        const int sl = part_slot(o.row0, o.nrows);
-                        for (int q = 0; q < cb.npre; ++q)
-                            if (cb.pre[q].slot == sl) cb.pre[q].out_vec = o.out_vec;
-                        slot_of_vec[o.out_vec] = sl;
-                    }
-                    auto in_slot = [&](const UOp &op, int t) -> int {
-                        if (op.in_kind[t] == 3) return part_slot(op.in_vec[t], op.in_gran[t]);
-                        if (op.in_kind[t] == 0) {
-                            auto it = slot_of_vec.find(op.in_vec[t]);
-                            if (it != slot_of_vec.end()) return it->second;
-                        }
-                        ok = false;                                         // (its producer is not of this batch: cannot be)
-                        return 0;
-                    };
-                    // BWD ops, level L-1 down to 0 (uops_b's order: the ops of one level are adjacent and independent of each
-                    // other). Per level and 64-row chunk ONE item per distinct matrix, with every (op, term) that multiplies by it.
-                    struct LevOp { int k, acc, out_slot, mask_slot, terms_left[4]; int ins[UOP_MAX_TERMS]; };
-                    {
-                        std::vector<size_t> mine;
-                        for (size_t k = 0; k < r1_first; ++k)
-                            if (hp->uops_b[k].kind == UOP_BWD && vinfo[hp->uops_b[k].out_vec].batch == i) mine.push_back(k);
-                        size_t q0 = 0;
-                        while (q0 < mine.size() && ok) {
-                            const int lev = vinfo[hp->uops_b[mine[q0]].out_vec].level;
-                            size_t q1 = q0;
-                            while (q1 < mine.size() && vinfo[hp->uops_b[mine[q1]].out_vec].level == lev) ++q1;
-                            if (q1 - q0 > CL_ACCS) { ok = false; break; }
-                            std::vector<LevOp> lops;
-                            for (size_t q = q0; q < q1 && ok; ++q) {
-                                const UOp &op = hp->uops_b[mine[q]];
-                                LevOp lo;
-                                memset(&lo, 0, sizeof(lo));
-                                lo.k = (int)mine[q];
-                                lo.acc = (int)(q - q0);
-                                for (int t = 0; t < op.nterms; ++t) lo.ins[t] = in_slot(op, t);
-                                lo.mask_slot = op.mask_vec >= 0 ? vt_slot(op.mask_vec) : -1;
-                                lops.push_back(lo);
-                            }
-                            // (outputs get their slots after every input of the level is resolved: a level never reads its own)
-                            for (size_t q = 0; q < lops.size(); ++q) {
-                                lops[q].out_slot = nslots++;
-                                const UOp &op = hp->uops_b[lops[q].k];
-                                if (op.out_vec >= 0 || op.out_part >= 0) {
-                                    if (cb.nout >= CL_MAX_OUT) { ok = false; break; }
-                                    ClOutRec &o = cb.out[cb.nout++];
-                                    o.slot = lops[q].out_slot;
-                                    o.out_vec = op.out_vec;
-                                    o.out_part = op.out_part;
-                                }
-                            }
-                            // distinct matrices of the level in first-use order, each with its (op, term) uses
-                            struct MatUse { int layer, mat; std::vector<std::pair<int, int>> uses; };
-                            std::vector<MatUse> mats;
-                            for (size_t q = 0; q < lops.size(); ++q) {
-                                const UOp &op = hp->uops_b[lops[q].k];
-                                for (int t = 0; t < op.nterms; ++t) {
-                                    size_t m = 0;
-                                    for (; m < mats.size(); ++m)
-                                        if (mats[m].layer == uid[op.layer[t]] && mats[m].mat == op.mat[t] && mats[m].uses.size() < CL_USES) break;
-                                    if (m == mats.size()) mats.push_back(MatUse{uid[op.layer[t]], op.mat[t], {}});
-                                    mats[m].uses.push_back(std::make_pair((int)q, t));
-                                }
-                            }
-                            for (int ch = 0; ch < D / 64 && ok; ++ch) {
-                                int seen[CL_ACCS] = {0, 0, 0};             // terms of each op already emitted in this chunk
-                                for (size_t m = 0; m < mats.size(); ++m) {
-                                    if (cb.nitems >= CL_MAX_ITEMS) { ok = false; break; }
-                                    ClItemRec &r = cb.item[cb.nitems++];
-                                    memset(&r, 0, sizeof(r));
-                                    r.layer = mats[m].layer;
-                                    r.mat = mats[m].mat;
-                                    const bool level_end = ch == D / 64 - 1 && m + 1 == mats.size();
-                                    r.meta = ch | ((int)mats[m].uses.size() << 8) | (level_end ? 1 << 16 : 0);
-                                    for (size_t u = 0; u < mats[m].uses.size(); ++u) {
-                                        const int q = mats[m].uses[u].first, t = mats[m].uses[u].second;
-                                        const UOp &op = hp->uops_b[lops[q].k];
-                                        const int fl = (seen[q] == 0 ? CLI_FIRST : 0) | (seen[q] == op.nterms - 1 ? CLI_LAST : 0);
-                                        ++seen[q];
-                                        if (lops[q].ins[t] > 31 || lops[q].out_slot > 31 || lops[q].mask_slot > 31) ok = false;
-                                        r.use[u] = lops[q].ins[t] | (lops[q].acc << 5) | (fl << 7) | (lops[q].out_slot << 9) |
-                                                   ((lops[q].mask_slot + 1) << 14);
-                                    }
-                                }
-                            }
-                            for (size_t q = 0; q < lops.size(); ++q) slot_of_vec[hp->uops_b[lops[q].k].out_vec] = lops[q].out_slot;
-                            q0 = q1;
-                        }
-                    }
-                    for (size_t k = 0; k < r1_only.size() && ok; ++k) {   // rank-1-only matrices all of whose terms are this batch's
-                        const UOp &op = hp->uops_b[r1_first + k];
-                        bool mine = true, any = false;
-                        for (int t = 0; t < op.nterms; ++t) {
-                            const int bt = vinfo[hp->rank1[r1_only[k].r1_start + t].v].batch;
-                            mine = mine && bt == i;
-                            any = any || bt == i;
-                        }
-                        if (!mine) {
-                            if (any && !r1_taken[k]) {
-                                r1_taken[k] = 2;
-                                moved.push_back(r1_only[k]);
-                            }
-                            continue;
-                        }
-                        r1_taken[k] = 1;
-                        if (cb.nr1 >= CL_MAX_R1) { ok = false; break; }
-                        ClR1Rec &r = cb.r1[cb.nr1++];
-                        r.layer = op.r1_layer;
-                        r.rel = op.r1_rel;
-                        r.nterms = op.nterms;
-                        for (int t = 0; t < op.nterms && ok; ++t) {
-                            r.v[t] = in_slot(op, t);
-                            r.u[t] = vt_slot(op.u_vec[t]);
-                        }
-                    }
-                    if (nslots > CL_MAX_SLOTS) ok = false;
-                    while (ok && cb.nitems % 4 != 0) {                     // whole trips of the item loop: items that do nothing
-                        if (cb.nitems >= CL_MAX_ITEMS) { ok = false; break; }
-                        ClItemRec &r = cb.item[cb.nitems++];
-                        memset(&r, 0, sizeof(r));
-                        r.mat = -1;                 // (no uses, no barrier: the root matrix of layer 0 is read and dropped)
-                    }
-                    if (!ok || (cb.npre == 0 && cb.nitems == 0 && cb.nr1 == 0)) continue;
-                    cls.push_back(cb);
-                }
-                for (size_t k = 0; k < r1_only.size(); ++k) ok = ok && r1_taken[k] != 0;
-                if (ok && !cls.empty()) {
-                    // heaviest closures first: they start first
-                    std::stable_sort(cls.begin(), cls.end(), [](const ClBlock &a, const ClBlock &b) { return a.nitems > b.nitems; });
-                    hp->closures.swap(cls);
-                    hp->groups.insert(hp->groups.end(), moved.begin(), moved.end());
-                }
-            }
-#else
-            (void)will_merge;
-#endif
         }
     }
     hp->nvec = (int)vinfo.size();
@@ -1417,23 +1226,8 @@ int make_plan(const mpqe_step_params_t *P, const mpqe_step_batch_t *B, int nb, c
     hp->o_cops = take(hp->cops.size() * sizeof(ChainOp));
     hp->o_wtslots = take(hp->wt_slots.size() * sizeof(WtSlot));
     hp->o_zmats = take(hp->zmats.size() * sizeof(ZMat));
-    {   // post-pass outputs the step's reduction reads (fused tail: they travel inside one launch)
-        std::vector<char> isv((size_t)std::max(hp->nvec, 1), 0);
-        for (size_t k = 0; k < hp->rank1.size(); ++k)
-            if (hp->rank1[k].v >= 0 && hp->rank1[k].v < hp->nvec) isv[hp->rank1[k].v] = 1;
-        for (size_t k = 0; k < hp->uops_b.size(); ++k) {
-            UOp &op = hp->uops_b[k];
-            op.through = (op.out_part >= 0 || (op.out_vec >= 0 && op.out_vec < hp->nvec && isv[op.out_vec])) ? 1 : 0;
-        }
-        for (size_t k = 0; k < hp->uops_f.size(); ++k) hp->uops_f[k].through = 1;
-    }
     hp->o_uopf = take(hp->uops_f.size() * sizeof(UOp));
     hp->o_uopb = take(hp->uops_b.size() * sizeof(UOp));
-#if MPQE_HAS_EXPERIMENTS
-    hp->o_closures = take(hp->closures.size() * (size_t)CL_BLOCK_WORDS * 4);
-#else
-    hp->o_closures = take(0);
-#endif
     hp->o_rank1 = take(hp->rank1.size() * sizeof(Rank1));
     hp->o_done_inc = take(hp->done_inc.size() * sizeof(int));
     TouchMeta tmeta;
@@ -1537,10 +1331,6 @@ int make_plan(const mpqe_step_params_t *P, const mpqe_step_batch_t *B, int nb, c
         put(hp->o_zmats, hp->zmats.data(), hp->zmats.size() * sizeof(ZMat));
         put(hp->o_uopf, hp->uops_f.data(), hp->uops_f.size() * sizeof(UOp));
         put(hp->o_uopb, hp->uops_b.data(), hp->uops_b.size() * sizeof(UOp));
-#if MPQE_HAS_EXPERIMENTS
-        for (size_t k = 0; k < hp->closures.size(); ++k)
-            put(hp->o_closures + k * (size_t)CL_BLOCK_WORDS * 4, &hp->closures[k], sizeof(ClBlock));
-#endif
         put(hp->o_rank1, hp->rank1.data(), hp->rank1.size() * sizeof(Rank1));
         put(hp->o_done_inc, hp->done_inc.data(), hp->done_inc.size() * sizeof(int));
         if (hp->ts_blocks) put(hp->o_tmeta, &tmeta, sizeof(tmeta));
@@ -1553,17 +1343,12 @@ int make_plan(const mpqe_step_params_t *P, const mpqe_step_batch_t *B, int nb, c
     hp->o_tsort = take(hp->ts_blocks ? (size_t)hp->ts_blocks * (4 * (size_t)TSORT_THREADS * tsort_rounds(hp->touch_M) + 4 * 256) * sizeof(unsigned) : 0);
     hp->total = off;
     if (dbg_on("DUMP_PLAN")) {        // diagnostics: what the step's launches consist of
-        fprintf(stderr, "plan: chain %d uniform %d blocks %d | tile sources %zu tiles %d slabs %d | groups %zu | uops f %zu b %zu | closures %zu | rank1 %zu | zmats %zu | touch M %lld\n",
+        fprintf(stderr, "plan: chain %d uniform %d blocks %d | tile sources %zu tiles %d slabs %d | groups %zu | uops f %zu b %zu | rank1 %zu | zmats %zu | touch M %lld\n",
                 (int)chain, (int)hp->uniform, hp->blk_off[nb], hp->wsrc.size(), hp->wblocks_total, hp->total_slabs, hp->groups.size(),
-                hp->uops_f.size(), hp->uops_b.size(), hp->closures.size(), hp->rank1.size(), hp->zmats.size(), hp->touch_M);
+                hp->uops_f.size(), hp->uops_b.size(), hp->rank1.size(), hp->zmats.size(), hp->touch_M);
         for (size_t k = 0; k < hp->groups.size(); ++k)
             fprintf(stderr, "  group %zu kind %d layer %d row %lld slabs/rows %d rank1 %d\n", k, hp->groups[k].kind, hp->groups[k].layer,
                     hp->groups[k].row, hp->groups[k].count, hp->groups[k].r1_count);
-#if MPQE_HAS_EXPERIMENTS
-        for (size_t k = 0; k < hp->closures.size(); ++k)
-            fprintf(stderr, "  closure %zu batch %d pre %d items %d r1 %d\n", k, hp->closures[k].batch, hp->closures[k].npre,
-                    hp->closures[k].nitems, hp->closures[k].nr1);
-#endif
     }
     return MPQE_OK;
 }
@@ -1592,7 +1377,7 @@ int plan_auto(const mpqe_step_params_t *P, const mpqe_step_batch_t *B, int nb, c
 // Everything make_plan() reads, field by field (struct padding never takes part in the comparison).
 struct PlanKey {
     int dim, num_layers, num_relations, num_modes, readout, flags, nb, nlanes, chain;
-    int dbg_gen;                              // diagnostics switches may shape a plan (TILE_N, NO_CLOSURE, ...): their generation
+    int dbg_gen;                              // diagnostics switches may shape a plan (TILE_N, NO_RUNS, ...): their generation
     int lane_begin[MPQE_STEP_MAX_LANES + 1];
     int alias[MPQE_STEP_MAX_LAYERS];          // first layer with the same parameter buffers
     long long table_rows[MPQE_STEP_MAX_MODES];      // (the in-step touch plan's key widths and batch table)

@@ -13,7 +13,7 @@ __device__ __forceinline__ void grad_w_block(const StepDev *__restrict__ sd, con
                                              long long level_stride, float *__restrict__ slabs, int bid,
                                              int wblocks_total, float *smem, const GradPtrs &gp, bool zeroed,
                                              long long *dbg, int D, const PostArgs *po = nullptr, int tile_n = GT_BN,
-                                             int nxcd = 8, bool through = false) {
+                                             int nxcd = 8) {
     const int tiles_j = (D + tile_n - 1) / tile_n, tiles = tiles_j * ((D + GT_BM - 1) / GT_BM);
     // Workgroups are dealt round-robin over the 8 XCDs, each with its own L2: blocks b and b+8 share
     // one. The `tiles` output tiles of a K-chunk read the SAME rows of H and gH (different column
@@ -54,9 +54,8 @@ __device__ __forceinline__ void grad_w_block(const StepDev *__restrict__ sd, con
         }
     }
     if constexpr (MODE == LD_T) {      // chain form (D % 64 == 0, 16-byte aligned rows): register-only K loop
-        // (through: a slab of the fused tail is read by the reduction workgroups of the same launch)
-        if (tile_n == 32) grad_w_tile_rows<LDS_TILES, 2>(x, g, D, xs, xo, go, q0, q1, wk.i0, wk.j0, dst, smem, direct && !zeroed, dbg, through && !direct);
-        else grad_w_tile_rows<LDS_TILES, 4>(x, g, D, xs, xo, go, q0, q1, wk.i0, wk.j0, dst, smem, direct && !zeroed, dbg, through && !direct);
+        if (tile_n == 32) grad_w_tile_rows<LDS_TILES, 2>(x, g, D, xs, xo, go, q0, q1, wk.i0, wk.j0, dst, smem, direct && !zeroed, dbg);
+        else grad_w_tile_rows<LDS_TILES, 4>(x, g, D, xs, xo, go, q0, q1, wk.i0, wk.j0, dst, smem, direct && !zeroed, dbg);
         (void)gs; (void)out;
     } else if constexpr (MODE == LD_FAST)      // whole K-steps, D % 64 == 0: deep LDS-DMA pipeline
         // (a form with NO LDS -- every MFMA operand one coalesced global_load_dword into its register, four
@@ -182,16 +181,9 @@ struct ReduceArgs {
     long long touch_M;
     int touch_row_bits;
     int32_t *err;
-    // fused tail (the reduction as trailing workgroups of the weight-gradient launch): the groups and the loss workgroup
-    // wait until `arrive` has counted the launch's `phase1` tile and vector-op workgroups; NULL: a launch of its own
-    const unsigned *arrive;
-    unsigned phase1;
-    int rows_multi;          // 1: the entity-table workgroups take a range of sorted positions each (table_sum_multi)
     int nmat;                // >= 0: the launch's rows are packed (step_reduce_kernel): the first nmat groups are the matrix groups
     const int *runs;         // != NULL: the plan's run starts, compacted by a role of the weight-gradient launch
                              // (touch_runs_block): runs[0 .. runs[touch_M]) -- the table workgroups take those, not every position
-    int early;               // 1: the loss and the entity-table rows were roles of the weight-gradient launch (TailArgs.extra0):
-                             // the loss workgroup here only closes the step (epochs, the sort's barrier word, the plan's failure flag)
     unsigned *notify;        // mpqe_step_extra_t.notify (pinned host words) or NULL; written by the loss workgroup
     unsigned notify_value;
 };
@@ -210,54 +202,14 @@ __device__ __forceinline__ void reduce_block(const ReduceArgs &ra, int bx, int b
     if (by > ngroups) {        // further rows: entity-table gradients, per destination row (step_touch.h).
         // (As workgroups of the weight-gradient launch they are throttled to two per CU by its 64 KB of LDS: 23.6 us
         // for that launch instead of 16.6; here they cost 2.6 us.)
-#if MPQE_HAS_EXPERIMENTS
-        if (ra.rows_multi) {
-            // a RANGE of sorted positions per workgroup (step_touch.h: table_sum_multi): 344 workgroups for the AIFB step's
-            // 22 016 ids, all resident at once, instead of 2 752 one-run workgroups in two and a half rounds of the chip
-            static_assert(sizeof(f32x4) * 4 * 64 >= TSM_LDS_WORDS(64) * 4, "table_sum_multi's window lives in the reduction's LDS");
-            table_sum_multi(ra.touch_M, ra.touch_row_bits, reinterpret_cast<const tkey_t *>(touch + ra.touch_keys),
-                            reinterpret_cast<const int *>(touch + ra.touch_perm), ra.DG, D, ra.tabs, table_store & 1,
-                            (long long)(by - ngroups - 1) * gx + bx, &reinterpret_cast<const TouchHeader *>(touch)->pad[0],
-                            reinterpret_cast<unsigned *>(part));
-            return;
-        }
-#endif
         table_sum_block(ra.touch_M, ra.touch_row_bits, reinterpret_cast<const tkey_t *>(touch + ra.touch_keys),
                         reinterpret_cast<const int *>(touch + ra.touch_perm), ra.DG, D, ra.tabs, table_store & 1,
                         (long long)(by - ngroups - 1) * gx + bx, &reinterpret_cast<const TouchHeader *>(touch)->pad[0],
                         ra.runs, ra.runs ? ra.runs + ra.touch_M : nullptr);
         return;
     }
-    // fused tail: what follows reads what tiles / vector ops of THIS launch wrote (slabs and the post-pass' last vectors and
-    // rows of `parts`, all written through) or must come after their last read of the epochs. One lane polls the arrival
-    // counter (agent scope, bounded), then the workgroup's barrier. No acquire fence: nothing on this XCD has read those
-    // lines before in this launch. Everything that does NOT depend on them -- the group's record, its rank-1 records, the u
-    // vectors (pre-pass), the old value -- is requested before the wait.
-    auto wait_phase1 = [&]() {
-        if (ra.arrive) {
-            if (threadIdx.x == 0) {
-                // (hundreds of workgroups wait on ONE word: polled every ~1.5 us while more than a few arrivals are missing --
-                // at one poll per 0.25 us each they saturated the word's L2 channel and the post-pass next to them took
-                // 31 us instead of 15 -- and quickly only for the last few)
-                for (int spins = 0;; ++spins) {
-                    const unsigned have = uop_poll(ra.arrive);
-                    if ((int)(have - ra.phase1) >= 0) break;
-                    if (spins >= UOP_SPIN_LIMIT) {
-                        flag_error(ra.err, MPQE_FLAG_INTERNAL | 0x1000);
-                        break;
-                    }
-#ifndef MPQE_EMU
-                    if (ra.phase1 - have > 3u) __builtin_amdgcn_s_sleep(48);
-                    else __builtin_amdgcn_s_sleep(2);
-#endif
-                }
-            }
-            __syncthreads();
-        }
-    };
     if (by == ngroups) {       // one extra workgroup row: the loss reduction rides along
         if (bx == 0) {
-            wait_phase1();
             // the step is over: the next step's granules (forward pre-pass, backward post-pass) get new tags, and the
             // count of finished transpose workgroups a new target (step_uniform.h, step_chain.h)
             if (epoch_b && threadIdx.x == 0) {
@@ -277,7 +229,6 @@ __device__ __forceinline__ void reduce_block(const ReduceArgs &ra, int bx, int b
 #endif
                 ra.notify[0] = ra.notify_value;
             }
-            if (ra.early) return;
             if (ra.lm.chain) loss_block_chain(ra.lm, ra.bterms, ra.loss, reinterpret_cast<float *>(part), 4);
             else loss_block(ra.sd, ra.terms, ra.loss, reinterpret_cast<float *>(part), 4);
         }
@@ -296,7 +247,6 @@ __device__ __forceinline__ void reduce_block(const ReduceArgs &ra, int bx, int b
         // beyond the first slice were never summed)
         const int NS = (D % (4 * VEC_SLICES) == 0 && 256 % (D / 4 / VEC_SLICES) == 0 && (ra.nmat >= 0 || gx >= VEC_SLICES)) ? VEC_SLICES : 1;
         if (bx >= NS) return;
-        wait_phase1();
         const int LQ = D / 4 / NS, RG = 256 / LQ;
         const int c4 = bx * LQ + threadIdx.x % LQ, rg = threadIdx.x / LQ;
         const float *pv = partial + (long long)g.start * D + 4 * c4;
@@ -363,7 +313,6 @@ __device__ __forceinline__ void reduce_block(const ReduceArgs &ra, int bx, int b
     }
     f32x4 old4 = {0.f, 0.f, 0.f, 0.f};       // accumulate mode: the old value travels with the other loads, not after them
     if (vec && dst && !zeroed && sg == 0 && idx + 3 < elems) old4 = gload4(dst + idx);
-    wait_phase1();
     if (r1) {
         for (int t0 = sg; t0 < g.r1_count; t0 += 4 * R1_CHUNK) {
             Rank1 rk[R1_CHUNK];
@@ -469,11 +418,6 @@ struct TailArgs {
     int runs_front, runs_n;  // > 0: the launch's first runs_front workgroups (runs_n of them at work) compact the touch plan's run
     int *runs_out;           // starts (touch_runs_block) for the reduction launch's table workgroups: runs_out[0 .. M) the
                              // positions, runs_out[M] their number
-    int extra0;              // >= 0: workgroups [extra0, ...) of the launch are roles that read only what the CHAIN launch wrote --
-    int tm_blocks;           // [extra0] the loss (loss_block_chain), then tm_blocks entity-table workgroups (table_sum_multi):
-                             // they were 2 800 + 1 workgroups of the reduction launch; here they run beside the tiles
-    ClosureArgs ca;          // ca.ncl > 0: the post-pass as closures (step_closure.h) -- the launch's FIRST ncl workgroups, padded
-    int clpad;               // to clpad (a multiple of 8: tile b keeps XCD b % 8); ublocks is 0 then
 
     const long long *node_map;
     long long map_len;
@@ -527,31 +471,15 @@ __device__ __forceinline__ void post_block(const StepDev *__restrict__ sd, const
     }       // (else: padding)
 }
 
-// FUSED (chain form, LD_T; diagnostics switch FUSE_TAIL, off by default): the step's reduction rides in this launch --
-// `fa.first` workgroups of tiles / vector ops / zero fill as before, then the reduction's workgroups: entity-table rows and
-// the loss (they read what the chain launch wrote) and, waiting for the arrival counter of the tiles and vector ops, the
-// reduction groups: two launches per step instead of three. Built, parity-tested (tests/test_step.py), and SLOWER on the
-// AIFB step -- 32.3 us against 19.8 + 10.2 -- for two measured reasons: (1) every workgroup of a launch has the launch's
-// register footprint, the tile's 228 VGPRs = two workgroups per CU whatever their LDS, so ~2 800 table-row and ~400
-// group workgroups queue for the ~270 slots the tiles and vector ops leave (and the waiting groups hold some); (2) the
-// post-pass outputs the reduction reads must be written through to reach another XCD inside a launch, and those
-// agent-scope stores stretch the post-pass' dependence chain from 15.7 to 20.6 us. DESIGN.md 4.2 (round 3).
-struct FuseArgs {
-    int first;              // workgroups in front of the reduction's (the un-fused launch's grid); 0: not fused
-    int gx, trows;          // the reduction's grid: gx workgroups per group, trows rows of gx table-row workgroups
-    int tx;                 // the table-row workgroups are dealt to the first tx XCDs only (8: all): not where the post-pass runs
-    int tspan;              // workgroups of the launch the table rows take (holes included)
-    unsigned *arrive;       // arrival counter (zeroed by the chain launch)
-};
-template <int MODE, bool FUSED = false>
+template <int MODE>
 __global__ __launch_bounds__(256) void step_tail_kernel(const StepDev *__restrict__ sd, TailArgs ta,
                                                         const float *__restrict__ H, const float *__restrict__ GH,
                                                         long long level_stride, GradPtrs gp, int zeroed, LayerPtrs lp,
-                                                        UArgs ua, FuseArgs fa, ReduceArgs ra) {
+                                                        UArgs ua, ReduceArgs ra) {
     // weight-gradient tiles only: the DMA ring takes 64 KB of LDS per workgroup, which would throttle the
     // thousands of light partial-sum / anchor workgroups to 2 per CU if they shared this kernel
     // (LD_T, the chain form: the tiles meet in a 17 KB LDS tile at their end; the post-pass' vector ops use 8 KB)
-    __shared__ __attribute__((aligned(16))) float smem[MODE == LD_T ? (FUSED ? GWR_SMEM_FLOATS2 : GWR_SMEM_FLOATS) : (MODE == LD_FAST ? GWD_SMEM_FLOATS : GT_SMEM_FLOATS)];
+    __shared__ __attribute__((aligned(16))) float smem[MODE == LD_T ? GWR_SMEM_FLOATS : (MODE == LD_FAST ? GWD_SMEM_FLOATS : GT_SMEM_FLOATS)];
     // The launch's FIRST ta.runs_front workgroups (a multiple of 8: workgroup b of the rest keeps XCD b % 8) compact the run
     // starts of the step's touch plan for the reduction launch's table workgroups (touch_runs_block): they depend on the chain
     // launch alone and are through before the first tile has its rows
@@ -566,58 +494,6 @@ __global__ __launch_bounds__(256) void step_tail_kernel(const StepDev *__restric
         }
         bid -= ta.runs_front;
     }
-    if constexpr (FUSED) {
-        if (bid >= fa.first) {
-            int p = bid - fa.first;
-            const int T = fa.tspan;
-            int bx, by;
-            if (p < T) {
-                if ((p & 7) >= fa.tx) return;            // (a hole: this XCD is the post-pass')
-                p = (p >> 3) * fa.tx + (p & 7);
-                if (p >= fa.trows * fa.gx) return;
-                bx = p % fa.gx, by = ra.ngroups + 1 + p / fa.gx;
-            } else if (p == T) bx = 0, by = ra.ngroups;
-            else bx = (p - T - 1) % fa.gx, by = (p - T - 1) / fa.gx;
-            reduce_block(ra, bx, by, fa.gx, reinterpret_cast<f32x4(*)[64]>(smem));
-            return;
-        }
-    }
-#if MPQE_HAS_EXPERIMENTS
-    if (ta.extra0 >= 0 && bid >= ta.extra0) {
-        // roles that depend on the chain launch alone: the loss of the step, the entity-table rows (step_touch.h)
-        const int e = bid - ta.extra0;
-#ifndef MPQE_EMU
-        if (ta.stamps && threadIdx.x == 0) ta.stamps[(long long)bid * 8 + 0] = (long long)wall_clock64();
-#endif
-        if (e == 0) {
-            loss_block_chain(ra.lm, ra.bterms, ra.loss, smem, 4);
-        } else if (e - 1 < ta.tm_blocks) {
-            static_assert(sizeof(smem) >= TSM_LDS_WORDS(64) * 4, "table_sum_multi's window lives in the launch's LDS");
-            table_sum_multi(ra.touch_M, ra.touch_row_bits, reinterpret_cast<const tkey_t *>(ra.touch + ra.touch_keys),
-                            reinterpret_cast<const int *>(ra.touch + ra.touch_perm), ra.DG, ta.D, ra.tabs, ra.table_store & 1,
-                            (long long)(e - 1), &reinterpret_cast<const TouchHeader *>(ra.touch)->pad[0],
-                            reinterpret_cast<unsigned *>(smem));
-        }
-#ifndef MPQE_EMU
-        if (ta.stamps && threadIdx.x == 0) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            ta.stamps[(long long)bid * 8 + 5] = (long long)wall_clock64();
-            ta.stamps[(long long)bid * 8 + 6] = 1 + 6;            // kind 6: loss / entity-table rows
-        }
-#endif
-        return;
-    }
-#endif
-    // (fused: a tile / vector-op workgroup counts itself in once its stores -- written through -- are acknowledged)
-    auto arrived = [&]() {
-        if constexpr (FUSED) {
-#ifndef MPQE_EMU
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-            __syncthreads();
-            if (threadIdx.x == 0) atomicAdd(fa.arrive, 1u);
-        }
-    };
 #ifndef MPQE_EMU
     long long tick0 = 0;
     if (ta.stamps && threadIdx.x == 0) {
@@ -631,26 +507,6 @@ __global__ __launch_bounds__(256) void step_tail_kernel(const StepDev *__restric
     // tiles the others (workgroup b runs on XCD b % 8) -- the vector ops are a latency chain of small loads and polls, the
     // tiles stream ~40 MB through their XCDs' L2s and fabric ports
     int ub = -1, tb;
-#if MPQE_HAS_EXPERIMENTS
-    if (ta.ca.ncl > 0) {       // the post-pass as closures: the launch's first workgroups, one per batch (step_closure.h)
-        if (bid < ta.clpad) {
-            if (bid < ta.ca.ncl) {
-#ifndef MPQE_EMU
-                __builtin_amdgcn_s_setprio(3);      // a latency chain next to throughput work
-#endif
-                closure_block(bid, ta.D, ta.ca, lp, ua, smem, gp, zeroed, ta.stamps ? ta.stamps + (long long)bid * 8 : nullptr);
-#ifndef MPQE_EMU
-                if (ta.stamps && threadIdx.x == 0) {
-                    ta.stamps[(long long)bid * 8 + 5] = (long long)wall_clock64();       // (word 1 stays 0: not a tile)
-                    ta.stamps[(long long)bid * 8 + 6] = 1 + 5;                           // kind 5: a closure
-                }
-#endif
-            }
-            return;
-        }
-        tb = bid - ta.clpad;
-    } else
-#endif
     if (ta.ux > 0) {
         const int x = bid & 7, r = bid >> 3, tx = 8 - ta.ux;
         if (x >= tx) {
@@ -670,17 +526,15 @@ __global__ __launch_bounds__(256) void step_tail_kernel(const StepDev *__restric
             ta.stamps[(long long)bid * 8 + 6] = 1 + (long long)ua.ops[ub / ua.chunks].kind;
         }
 #endif
-        arrived();
         return;
     }
     if (tb >= ta.wblocks) {        // zero fill of a gradient matrix nobody writes (uniform branch)
         if (tb - ta.wblocks < ta.zblocks) zmat_block(ta.zmats, ta.zper, tb - ta.wblocks, sd->D, gp);
         return;
     }
-    grad_w_block<MODE, (FUSED ? 2 : 4)>(sd, ta.wsrc, ta.nwsrc, ta.wblock, H, GH, level_stride, ta.slabs, tb, ta.wblocks,
+    grad_w_block<MODE>(sd, ta.wsrc, ta.nwsrc, ta.wblock, H, GH, level_stride, ta.slabs, tb, ta.wblocks,
                        smem, gp, zeroed != 0, ta.stamps ? ta.stamps + (long long)bid * 8 : nullptr, ta.D, nullptr, ta.tile_n,
-                       ta.ux > 0 ? 8 - ta.ux : 8, FUSED);      // zeroed: this call zero-filled the gradients, a store suffices
-    arrived();
+                       ta.ux > 0 ? 8 - ta.ux : 8);      // zeroed: this call zero-filled the gradients, a store suffices
 #ifndef MPQE_EMU
     if (ta.stamps && threadIdx.x == 0) {
         ta.stamps[(long long)bid * 8 + 1] = (long long)wall_clock64();

@@ -454,35 +454,6 @@ def test_fused_step_small_dimensions(be, D, readout, adaptive):
         np.testing.assert_allclose(grads[k], ref, rtol=1e-4, atol=2e-6, err_msg=k)
 
 
-@pytest.mark.parametrize('D,readout,adaptive', [(128, 'mp', True), (64, 'mp', True), (128, 'sum', False)])
-def test_post_pass_closures_match_oracle(be, request, D, readout, adaptive):
-    """The backward post-pass of the batch-uniform node states as one closure workgroup per batch (split tail launch,
-    csrc/step_closure.h; mpqe_debug_option CLOSURE) against the oracle and against the vector-op form:
-    batches of more than 8 x 16 graphs, so that a column sum has more rows than the closure has row groups (its order
-    of additions then differs from the vector ops': same values within rounding), every chain depth, ragged sizes."""
-    if not be.lib.mpqe_debug_has_experiments():
-        pytest.skip('measured slower and taken out of the shipped library: builds with -DMPQE_EXPERIMENTS only '
-                    '(MPQE_EMU_EXPERIMENTS=1 / tools/build_variant.sh)')
-    mix = [('3-chain', 200, 1.0), ('2-chain', 150, 0.5), ('3-inter_chain', 40, 0.25), ('3-chain_inter', 33, 2.0),
-           ('3-chain', 17, 0.3)]
-    schema, mode_ids, rel_ids, params, node_map, cfg, batches = make_problem(29, D, 3, False, mix, readout, adaptive)
-    ref_loss, ref_per, ref_sp, ref_sn = oracle_step(params, cfg, node_map, batches, 1.0)
-    be.lib.mpqe_debug_option(b'CLOSURE', 1, 1)               # (built on request: not the default form)
-    request.addfinalizer(lambda: be.lib.mpqe_debug_option(b'CLOSURE', 0, 0))
-    for zero in (True, False):
-        flags = _capi.STEP_SPLIT_TAIL | (_capi.STEP_ZERO_GRADS if zero else 0)
-        got = run_step(be, schema, mode_ids, params, node_map, cfg, batches, 1.0, flags=flags, repeat=2 if zero else 1)
-        assert got[4] == 0
-        np.testing.assert_allclose(got[0][0], ref_loss, rtol=1e-5, atol=1e-6)
-        for k, p in params.items():
-            ref = np.zeros(tuple(p.shape), np.float32) if p.grad is None else p.grad.numpy()
-            np.testing.assert_allclose(got[3][k], ref, rtol=1e-4, atol=2e-6, err_msg=k)
-    be.lib.mpqe_debug_option(b'CLOSURE', 0, 0)
-    old = run_step(be, schema, mode_ids, params, node_map, cfg, batches, 1.0, flags=_capi.STEP_SPLIT_TAIL)
-    for k in got[3]:
-        np.testing.assert_allclose(got[3][k], old[3][k], rtol=1e-5, atol=1e-7, err_msg=k)
-
-
 @pytest.mark.parametrize('zero', [True, False])
 def test_failed_in_step_touch_plan_is_recovered(be, request, zero):
     """The step builds the touch plan of its ids by workgroups that must all be resident at once (step_touch.h); on a GPU
@@ -841,7 +812,7 @@ def test_fused_step_chain_kernels(be, D, readout, adaptive, shared, L):
     if every or readout == 'mp':
         # Where the weight-gradient tiles + post-pass run. A step this small takes the MERGED launch by default (workgroups
         # of the chain launch: include/mpqe_amd.h MPQE_STEP_MERGE_TAIL); the benchmarked step is larger and takes the
-        # SPLIT form (a launch of their own, the post-pass as closures: step_closure.h) -- forced here: the same gradients
+        # SPLIT form (a launch of their own: the tiles beside the post-pass' vector ops) -- forced here: the same gradients
         # (other kernels for the batch-uniform part: equal within rounding, not bit for bit). Then the merged form forced, three
         # runs on one descriptor buffer -- the later runs' counters start from the earlier ones' (targets are epoch x
         # count) -- with the call's own zero fill (the whole-root rule).
@@ -849,46 +820,20 @@ def test_fused_step_chain_kernels(be, D, readout, adaptive, shared, L):
         runs.append(split)
         for k in got[3]:
             np.testing.assert_allclose(split[3][k], got[3][k], rtol=1e-5, atol=1e-7, err_msg=k)
-        # where the loss and the entity-table rows of the split form run: in the reduction launch (default), or as trailing
-        # workgroups of the weight-gradient launch (EARLY_ROWS: table_sum_multi, a range of sorted positions per workgroup;
-        # measured slower, kept as a switch) -- the same additions in the same order, bit for bit
-        # ... and the reduction's table workgroups taking a range of positions each (ROWS_MULTI; default: one run each)
-        # ... and the post-pass alone riding in the chain launch (POST_IN_CHAIN: the tiles stay a launch of their own)
-        # ... and the table workgroups taking every sorted position (NO_RUNS) instead of the compacted run starts (default)
-        exps = bool(be.lib.mpqe_debug_has_experiments())      # (the forms taken out of the shipped library: -DMPQE_EXPERIMENTS)
-        for opt in ((b'EARLY_ROWS', b'ROWS_MULTI', b'POST_IN_CHAIN', b'NO_RUNS') if exps else (b'NO_RUNS',)):
-            be.lib.mpqe_debug_option(opt, 1, 1)
-            try:
-                other = run_step(be, schema, mode_ids, params, node_map, cfg, batches, 1.0, flags=_capi.STEP_SPLIT_TAIL)
-            finally:
-                be.lib.mpqe_debug_option(opt, 0, 0)
-            np.testing.assert_array_equal(split[0], other[0])
-            for k in got[3]:
-                np.testing.assert_array_equal(split[3][k], other[3][k], err_msg='%s %s' % (opt, k))
+        # the split form's table workgroups taking every sorted position (NO_RUNS) instead of the compacted run starts
+        # (default) -- the same additions in the same order, bit for bit
+        be.lib.mpqe_debug_option(b'NO_RUNS', 1, 1)
+        try:
+            other = run_step(be, schema, mode_ids, params, node_map, cfg, batches, 1.0, flags=_capi.STEP_SPLIT_TAIL)
+        finally:
+            be.lib.mpqe_debug_option(b'NO_RUNS', 0, 0)
+        np.testing.assert_array_equal(split[0], other[0])
+        for k in got[3]:
+            np.testing.assert_array_equal(split[3][k], other[3][k], err_msg='NO_RUNS %s' % k)
         runs.append(run_step(be, schema, mode_ids, params, node_map, cfg, batches, 1.0,
                              flags=_capi.STEP_SPLIT_TAIL | _capi.STEP_ZERO_GRADS, repeat=2))
-        if exps:
-            be.lib.mpqe_debug_option(b'POST_IN_CHAIN', 1, 1)
-            try:        # (three runs on one descriptor buffer: the counters' targets are epoch x count; the whole-root rule)
-                runs.append(run_step(be, schema, mode_ids, params, node_map, cfg, batches, 1.0,
-                                     flags=_capi.STEP_SPLIT_TAIL | _capi.STEP_ZERO_GRADS, repeat=3))
-            finally:
-                be.lib.mpqe_debug_option(b'POST_IN_CHAIN', 0, 0)
         runs.append(run_step(be, schema, mode_ids, params, node_map, cfg, batches, 1.0,
                              flags=_capi.STEP_MERGE_TAIL | _capi.STEP_ZERO_GRADS, repeat=3))
-        # the reduction as trailing workgroups of the weight-gradient launch (two launches per step in the split form):
-        # accumulate and zero-fill modes, three runs on one descriptor buffer (the arrival counter is re-armed per step)
-        if exps:
-            be.lib.mpqe_debug_option(b'FUSE_TAIL', 1, 1)
-            try:
-                fz = run_step(be, schema, mode_ids, params, node_map, cfg, batches, 1.0,
-                              flags=_capi.STEP_SPLIT_TAIL | _capi.STEP_ZERO_GRADS, repeat=3)
-                fa = run_step(be, schema, mode_ids, params, node_map, cfg, batches, 1.0, flags=_capi.STEP_SPLIT_TAIL)
-            finally:
-                be.lib.mpqe_debug_option(b'FUSE_TAIL', 0, 0)
-            runs += [fz, fa]
-            for k in fz[3]:          # (same tiles, same order of additions: zero fill + store == accumulate into zeros)
-                np.testing.assert_array_equal(fz[3][k], fa[3][k], err_msg=k)
     if every:
         # entity-table gradients by fp32 atomics instead of the per-row sums of the touch plan
         runs.append(run_step(be, schema, mode_ids, params, node_map, cfg, batches, 1.0, touch=False))
