@@ -909,6 +909,45 @@ static std::shared_ptr<CachedPlan> plan_for(const mpqe_step_params_t *P, const m
     return fresh;
 }
 
+// The launch plan is a pure function of the descriptors; it is kept on the host next to the device
+// table it describes (same key: the caller's desc buffer), so a steady-state call costs one lookup.
+// upload_desc NULL: look up only (the plan of a step that has run from `desc` with these descriptors, or none). Otherwise a
+// plan that is not there is made, and *upload_desc is raised where this call has to write the table again.
+static int plan_lookup(const mpqe_step_params_t *P, const mpqe_step_batch_t *B, int nb, const mpqe_step_lanes_t *lanes,
+                       void *desc, int *upload_desc, std::shared_ptr<const CachedPlan> *out) {
+    const bool ask_chain = want_chain(P, B, nb);
+    PlanKey key;
+    make_key(P, B, nb, lanes, &key);
+    key.chain = ask_chain ? 1 : 0;
+    std::lock_guard<std::mutex> lock(g_plan_mu);
+    auto it = g_plans.find(desc);
+    if (it != g_plans.end() && memcmp(&it->second->key, &key, sizeof(key)) == 0) {
+        *out = it->second;
+        return MPQE_OK;
+    }
+    if (!upload_desc) return MPQE_ERR_INVALID_ARG;
+    if (it != g_plans.end() && !*upload_desc) {
+        // desc holds another step's table -- unless only the diagnostics switches changed since it was planned: then the
+        // same step is planned again and its table uploaded again by this call
+        PlanKey old = it->second->key;
+        old.dbg_gen = key.dbg_gen;
+        if (memcmp(&old, &key, sizeof(key)) != 0) return MPQE_ERR_INVALID_ARG;
+        *upload_desc = 1;
+    }
+    // (the size queries of this packed step have just built it)
+    std::shared_ptr<CachedPlan> plan = g_recent && memcmp(&g_recent->key, &key, sizeof(key)) == 0 ? g_recent : nullptr;
+    if (!plan) {
+        plan = std::make_shared<CachedPlan>();
+        plan->key = key;
+        const int st = plan_auto(P, B, nb, lanes, ask_chain, &plan->hp);
+        if (st) return st;
+    }
+    if (g_plans.size() >= 1024) g_plans.clear();      // plans in use stay alive through their shared_ptr
+    g_plans[desc] = plan;
+    *out = plan;
+    return MPQE_OK;
+}
+
 static bool want_chain(const mpqe_step_params_t *P, const mpqe_step_batch_t *B, int nb) {
     if (!P || !B || nb < 1 || nb > MPQE_STEP_MAX_BATCHES) return false;
     bool use_chain = !(P->flags & MPQE_STEP_NO_CHAIN) && (P->dim == 64 || P->dim == 128 || P->dim == 256) &&
@@ -1214,15 +1253,8 @@ extern "C" int mpqe_step_table_rows(const mpqe_step_params_t *P, const mpqe_step
     if (!P || !B || !G || !desc || !workspace || !touch || nb < 1 || nb > MPQE_STEP_MAX_BATCHES) return MPQE_ERR_INVALID_ARG;
     if ((uintptr_t)touch % 256 != 0 || (uintptr_t)workspace % 256 != 0) return MPQE_ERR_INVALID_ARG;
     std::shared_ptr<const CachedPlan> cached;
-    {
-        PlanKey key;
-        make_key(P, B, nb, nullptr, &key);
-        key.chain = want_chain(P, B, nb) ? 1 : 0;
-        std::lock_guard<std::mutex> lock(g_plan_mu);
-        auto it = g_plans.find(const_cast<void *>(desc));
-        if (it != g_plans.end() && memcmp(&it->second->key, &key, sizeof(key)) == 0) cached = it->second;
-    }
-    if (!cached) return MPQE_ERR_INVALID_ARG;           // (not the descriptor buffer of a step that has run with these descriptors)
+    // (refused: not the descriptor buffer of a step that has run with these descriptors)
+    if (plan_lookup(P, B, nb, nullptr, const_cast<void *>(desc), nullptr, &cached)) return MPQE_ERR_INVALID_ARG;
     const HostPlan &hp = cached->hp;
     if (!hp.chain || hp.touch_M <= 0) return MPQE_ERR_UNSUPPORTED;
     if (workspace_bytes < hp.total) return MPQE_ERR_WORKSPACE;
@@ -1345,912 +1377,5 @@ extern "C" int mpqe_step_forward_backward(const mpqe_step_params_t *P, const mpq
                                          touch, stream, nullptr);
 }
 
-static int step_ex(const mpqe_step_params_t *P, const mpqe_step_batch_t *B, int nb, const int64_t *anchor_ids,
-                   const int64_t *targets, const int64_t *negs, float margin, const mpqe_step_grads_t *G, int backward,
-                   float *loss, float *scores_pos, float *scores_neg, void *desc, size_t desc_bytes, int upload_desc,
-                   void *workspace, size_t workspace_bytes, int32_t *err, const mpqe_step_lanes_t *lanes, void *const *events,
-                   int num_events, void *touch, void *stream, const mpqe_step_extra_t *extra);
-
-extern "C" int mpqe_step_forward_backward_ex(const mpqe_step_params_t *P, const mpqe_step_batch_t *B, int nb,
-                                             const int64_t *anchor_ids, const int64_t *targets, const int64_t *negs,
-                                             float margin, const mpqe_step_grads_t *G, int backward,
-                                             float *loss, float *scores_pos, float *scores_neg, void *desc,
-                                             size_t desc_bytes, int upload_desc, void *workspace,
-                                             size_t workspace_bytes, int32_t *err, const mpqe_step_lanes_t *lanes,
-                                             void *const *events, int num_events, void *touch, void *stream,
-                                             const mpqe_step_extra_t *extra) {
-    const int st = step_ex(P, B, nb, anchor_ids, targets, negs, margin, G, backward, loss, scores_pos, scores_neg, desc, desc_bytes,
-                           upload_desc, workspace, workspace_bytes, err, lanes, events, num_events, touch, stream, extra);
-    // (mpqe_step_extra_t.join_event / join_stream: the consumer's stream waits for this call's launches)
-    if (st == MPQE_OK && extra && extra->join_event && extra->join_stream != stream) {
-        if (hipEventRecord(reinterpret_cast<hipEvent_t>(extra->join_event), as_stream(stream)) != hipSuccess ||
-            hipStreamWaitEvent(as_stream(extra->join_stream), reinterpret_cast<hipEvent_t>(extra->join_event), 0) != hipSuccess)
-            return MPQE_ERR_LAUNCH;
-    }
-    return st;
-}
-
-static int step_ex(const mpqe_step_params_t *P, const mpqe_step_batch_t *B, int nb, const int64_t *anchor_ids,
-                   const int64_t *targets, const int64_t *negs, float margin, const mpqe_step_grads_t *G, int backward,
-                   float *loss, float *scores_pos, float *scores_neg, void *desc, size_t desc_bytes, int upload_desc,
-                   void *workspace, size_t workspace_bytes, int32_t *err, const mpqe_step_lanes_t *lanes, void *const *events,
-                   int num_events, void *touch, void *stream, const mpqe_step_extra_t *extra) {
-    if (!P || !B || nb < 1 || nb > MPQE_STEP_MAX_BATCHES || !desc) return MPQE_ERR_INVALID_ARG;
-    const bool ask_chain = want_chain(P, B, nb);
-    // The launch plan is a pure function of the descriptors; it is kept on the host next to the device
-    // table it describes (same key: the caller's desc buffer), so a steady-state call costs one lookup.
-    std::shared_ptr<const CachedPlan> cached;
-    {
-        PlanKey key;
-        make_key(P, B, nb, lanes, &key);
-        key.chain = ask_chain ? 1 : 0;
-        std::lock_guard<std::mutex> lock(g_plan_mu);
-        auto it = g_plans.find(desc);
-        if (it != g_plans.end() && memcmp(&it->second->key, &key, sizeof(key)) == 0) cached = it->second;
-        else if (it != g_plans.end() && !upload_desc) {
-            // desc holds another step's table -- unless only the diagnostics switches changed since it was planned: then the
-            // same step is planned again and its table uploaded again by this call
-            PlanKey old = it->second->key;
-            old.dbg_gen = key.dbg_gen;
-            if (memcmp(&old, &key, sizeof(key)) != 0) return MPQE_ERR_INVALID_ARG;
-            upload_desc = 1;
-        }
-        if (!cached && g_recent && memcmp(&g_recent->key, &key, sizeof(key)) == 0) {
-            // (the size queries of this packed step have just built it)
-            if (g_plans.size() >= 1024) g_plans.clear();      // plans in use stay alive through their shared_ptr
-            g_plans[desc] = g_recent;
-            cached = g_recent;
-        }
-        if (!cached) {
-            std::shared_ptr<CachedPlan> fresh = std::make_shared<CachedPlan>();
-            fresh->key = key;
-            int st = plan_auto(P, B, nb, lanes, ask_chain, &fresh->hp);
-            if (st) return st;
-            if (g_plans.size() >= 1024) g_plans.clear();
-            g_plans[desc] = fresh;
-            cached = fresh;
-        }
-    }
-    const HostPlan &hp = cached->hp;
-    const bool use_chain = hp.chain;
-    // backward = 2 .. 5: the step in three calls around a readout the CALLER computes (include/mpqe_amd.h: MPQE_STEP_PHASE_*,
-    // MPQE_READOUT_CALLER; level form, every node state live)
-    const int phase = backward;
-    if (phase < 0 || phase > MPQE_STEP_PHASE_SCORES_ONLY) return MPQE_ERR_INVALID_ARG;
-    const bool phase_fwd = phase == MPQE_STEP_PHASE_STATES, phase_bwd = phase == MPQE_STEP_PHASE_FROM_STATES;
-    const bool phase_score = phase == MPQE_STEP_PHASE_SCORES || phase == MPQE_STEP_PHASE_SCORES_ONLY;
-    if ((phase >= 2) != (P->readout == MPQE_READOUT_CALLER)) return MPQE_ERR_INVALID_ARG;
-    const bool learned = P->readout >= MPQE_READOUT_MLP;       // (step_readout.h: the readout's two Linear layers are the library's too)
-    if ((phase >= 2 || learned) && ((use_chain && !hp.ro_chain) || hp.nlanes > 1)) return MPQE_ERR_UNSUPPORTED;
-    if (learned) {
-        if (!P->readout_w0 || !P->readout_b0 || !P->readout_w2 || !P->readout_b2) return MPQE_ERR_INVALID_ARG;
-        if (P->readout_scatter < MPQE_SCATTER_ADD || P->readout_scatter > MPQE_SCATTER_MEAN) return MPQE_ERR_INVALID_ARG;
-        if (D_ok_for_readout(P->dim) == 0) return MPQE_ERR_UNSUPPORTED;
-        if (backward && G && (!G->readout_w0 || !G->readout_b0 || !G->readout_w2 || !G->readout_b2)) return MPQE_ERR_INVALID_ARG;
-        if (P->readout == MPQE_READOUT_CONCAT)
-            for (int i = 0; i < nb; ++i)
-                if (hp.sd.b[i].L != P->num_layers) return MPQE_ERR_INVALID_ARG;     // (model.py:441-446: one input block per layer)
-    }
-    // (the caller's readout read every level: its gradients of the intermediate levels are in the workspace already)
-    const int add_states = ((phase_bwd && (P->flags & MPQE_STEP_ADD_STATE_GRADS)) || P->readout == MPQE_READOUT_CONCAT) ? 1 : 0;
-    if (phase == MPQE_STEP_PHASE_SCORES_ONLY) backward = 0;        // (scores and loss from the caller's embeddings, no gradients)
-    // touch plan given: the chain form stores per-entry table-gradient rows and sums them per destination (no atomics)
-    bool use_touch = touch != nullptr && use_chain && backward;
-    // ... BUILD_TOUCH: `touch` is an OUTPUT -- the step builds the plan of the ids it is called with inside its chain launch
-    // (the level form has no use for a plan and leaves the buffer alone, as it ignores a plan built at pack time)
-    const bool build_touch = use_touch && (P->flags & MPQE_STEP_BUILD_TOUCH) != 0;
-    if (build_touch && (hp.ts_blocks <= 0 || (P->flags & MPQE_STEP_EIGHT_WAVES) || hp.nlanes > 1))
-        return MPQE_ERR_UNSUPPORTED;        // (a step beyond TSORT_MAX_ENTRIES ids: build the plan at pack time)
-    const bool sparse_tables = (P->flags & MPQE_STEP_SPARSE_TABLES) != 0;
-    if (sparse_tables && backward && !use_touch) return MPQE_ERR_INVALID_ARG;      // (needs the touch plan and the chain form)
-    int touch_row_bits = 1;         // (= the header of the caller's plan: mpqe_step_touch_build derives it the same way)
-    if (use_touch) {
-        long long trows = 1;
-        for (int m = 0; m < P->num_modes; ++m) trows = std::max(trows, (long long)P->table_rows[m]);
-        touch_row_bits = touch_bits(trows);
-        if ((uintptr_t)touch % 256 != 0) return MPQE_ERR_INVALID_ARG;
-        for (int m = 0; m < P->num_modes; ++m)
-            if (G->tables[m] && (uintptr_t)G->tables[m] % 16 != 0) return MPQE_ERR_INVALID_ARG;
-    }
-    for (int l = 1; l < hp.nlanes; ++l)           // handles are per call, not part of the cached plan
-        if (!lanes->fork_event || !lanes->aux_stream[l] || !lanes->join_event[l]) return MPQE_ERR_INVALID_ARG;
-    if (!anchor_ids || !targets || !negs || !loss || !workspace) return MPQE_ERR_INVALID_ARG;
-    if (desc_bytes < hp.desc_total) return MPQE_ERR_WORKSPACE;
-    if ((uintptr_t)desc % 256 != 0) return MPQE_ERR_INVALID_ARG;
-    if (backward && !G) return MPQE_ERR_INVALID_ARG;
-    if (workspace_bytes < hp.total) return MPQE_ERR_WORKSPACE;
-    if ((uintptr_t)workspace % 256 != 0) return MPQE_ERR_INVALID_ARG;
-    if (!P->node_map || !P->mode_emb) return MPQE_ERR_INVALID_ARG;
-    hipStream_t s = as_stream(stream);
-    char *wb = reinterpret_cast<char *>(workspace);
-    char *db = reinterpret_cast<char *>(desc);
-    const int D = P->dim;
-    const int NL = hp.nlanes;
-    hipStream_t ls[MPQE_STEP_MAX_LANES];
-    ls[0] = s;
-    for (int l = 1; l < NL; ++l) ls[l] = as_stream(lanes->aux_stream[l]);
-    // optional timing: event pair k brackets one launch, recorded on the stream of that launch
-    // (see mpqe_amd.h for the order)
-    int ev = 0;
-    auto mark = [&](hipStream_t on) {
-        if (events && ev < num_events) (void)hipEventRecord(reinterpret_cast<hipEvent_t>(events[ev]), on);
-        ++ev;
-    };
-
-    LayerPtrs lp;
-    GradPtrs gp;
-    TablePtrs tabs;
-    memset(&lp, 0, sizeof(lp));
-    memset(&gp, 0, sizeof(gp));
-    memset(&tabs, 0, sizeof(tabs));
-    int vec = D % 4 == 0;
-    const bool fast_dims = D % GT_BN == 0;     // D is both K (multiple of 32) and the tile width (64)
-    for (int l = 0; l < P->num_layers; ++l) {
-        if (!P->basis[l] || !P->root[l]) return MPQE_ERR_INVALID_ARG;
-        lp.basis[l] = P->basis[l];
-        lp.root[l] = P->root[l];
-        lp.bias[l] = P->bias[l];
-        vec = vec && ptr_vec_ok(P->basis[l], D) && ptr_vec_ok(P->root[l], D);
-        if (backward) {
-            gp.basis[l] = G->basis[l];
-            gp.root[l] = G->root[l];
-            gp.bias[l] = G->bias[l];
-        }
-    }
-    if (hp.ro_chain) {       // the readout's Linear layers: virtual layers of the chain form (HostPlan.ro_chain)
-        lp.root[hp.ro_layer] = P->readout_w0;
-        lp.bias[hp.ro_layer] = P->readout_b0;
-        lp.root[hp.ro_layer + 1] = P->readout_w2;
-        lp.bias[hp.ro_layer + 1] = P->readout_b2;
-        if (backward) {
-            gp.root[hp.ro_layer] = G->readout_w0;
-            gp.bias[hp.ro_layer] = G->readout_b0;
-            gp.root[hp.ro_layer + 1] = G->readout_w2;
-            gp.bias[hp.ro_layer + 1] = G->readout_b2;
-        }
-    }
-    int vec_tab = D % 4 == 0;
-    for (int m = 0; m < P->num_modes; ++m) {
-        if (!P->tables[m]) return MPQE_ERR_INVALID_ARG;
-        vec_tab = vec_tab && (uintptr_t)P->tables[m] % 16 == 0;
-        tabs.table[m] = P->tables[m];
-        tabs.rows[m] = P->table_rows[m];
-        tabs.grad[m] = backward ? G->tables[m] : nullptr;
-    }
-    if (backward) gp.mode_emb = G->mode_emb;
-
-    const bool fast = vec && fast_dims;
-    const StepDev *sd = reinterpret_cast<const StepDev *>(db + hp.o_sd);
-    if (upload_desc) {
-        // the descriptor table: ONE copy of the host image the plan keeps (the plan outlives the call: the cache holds
-        // it); then the hand-off state of this packed step: epochs 0, every granule tagged 0 (a live tag is >= 1)
-        (void)hipMemcpyAsync(db, hp.image.data(), hp.image.size(), hipMemcpyHostToDevice, s);
-        (void)hipMemsetAsync(db + hp.o_epoch, 0, hp.desc_total - hp.o_epoch, s);
-    }
-    bool dev_weights = false;
-    for (int i = 0; extra && i < nb; ++i) dev_weights = dev_weights || extra->batch_weight[i] != nullptr;
-    unsigned *notify = extra ? reinterpret_cast<unsigned *>(extra->notify) : nullptr;
-    const unsigned notify_value = extra ? extra->notify_value : 0u;
-    if (extra && extra->query_out && !use_chain) return MPQE_ERR_UNSUPPORTED;       // (the chain workgroups' score phase writes it)
-    if (dev_weights || (cached->weights_patched && !upload_desc)) {
-        WeightPatch wp;
-        memset(&wp, 0, sizeof(wp));
-        wp.nb = nb;
-        for (int i = 0; i < nb; ++i) {
-            wp.whost[i] = hp.sd.b[i].weight;
-            wp.wdev[i] = dev_weights ? extra->batch_weight[i] : nullptr;
-        }
-        hipLaunchKernelGGL(step_weights_kernel, dim3(1), dim3(64), 0, s, const_cast<StepDev *>(sd), wp);
-    }
-    cached->weights_patched = dev_weights;
-    unsigned *epoch_f = reinterpret_cast<unsigned *>(db + hp.o_epoch), *epoch_b = epoch_f + 16;
-    float *VT = reinterpret_cast<float *>(wb + hp.o_VT);
-    UArgs ua;
-    memset(&ua, 0, sizeof(ua));
-    ua.chunks = D / 64;
-    ua.VT = VT;
-    ua.gran = reinterpret_cast<u64 *>(db + hp.o_gran);
-    ua.mode_emb = P->mode_emb;
-    ua.num_modes = (long long)P->num_modes;
-    ua.parts = reinterpret_cast<float *>(wb + hp.o_parts);
-    ua.err = err;
-    float *H = reinterpret_cast<float *>(wb + hp.o_H), *GH = reinterpret_cast<float *>(wb + hp.o_GH);
-    float *tpos = reinterpret_cast<float *>(wb + hp.o_tpos), *tneg = reinterpret_cast<float *>(wb + hp.o_tneg);
-    float *spos = scores_pos ? scores_pos : reinterpret_cast<float *>(wb + hp.o_spos);
-    float *sneg = scores_neg ? scores_neg : reinterpret_cast<float *>(wb + hp.o_sneg);
-    float *terms = reinterpret_cast<float *>(wb + hp.o_terms);
-    const long long *ids = reinterpret_cast<const long long *>(anchor_ids);
-    const long long *tg = reinterpret_cast<const long long *>(targets), *ng = reinterpret_cast<const long long *>(negs);
-    const long long *nm = reinterpret_cast<const long long *>(P->node_map);
-
-    // Stream lanes: lane l runs the whole dependent chain (assemble -> levels -> score -> levels back)
-    // of ITS batches on its own stream, so the ~8 us a short launch costs regardless of its size
-    // overlaps with the other lanes' work; the lanes meet again before the weight gradients.
-    long long row0[MPQE_STEP_MAX_LANES + 1], gr0[MPQE_STEP_MAX_LANES + 1];
-    for (int l = 0; l <= NL; ++l) {
-        const int b = hp.lane_begin[l];
-        row0[l] = b < nb ? hp.sd.b[b].row_off : hp.sd.rows_total;
-        gr0[l] = b < nb ? hp.sd.b[b].g_off : hp.sd.graphs_total;
-    }
-    float *WT = reinterpret_cast<float *>(wb + hp.o_WT);
-    // prologue work: the forward pre-pass of the batch-uniform node states; backward: transposed weight copies for the
-    // backward chains, zero fill of the gradients. Chain form: roles of the chain launch itself (PrepArgs); level form:
-    // a zero-fill launch.
-    PrepArgs pa;
-    memset(&pa, 0, sizeof(pa));
-    long long zblocks = 0;
-    int wt_all = 0;            // transposed-copy workgroups of a full launch of this packed step
-    // merged launch: tiles + post-pass ride in the chain launch (include/mpqe_amd.h: MPQE_STEP_MERGE_TAIL)
-    // Measured (AIFB mix, D = 128, B per batch 32 / 64 / 128 / 256 / 384 / 512 / 8192): merged 48.9 / 50.3 / 52.6 / 56.8 /
-    // 61.3 / 68.4 / 569 us per step against 59.8 / 59.4 / 62.0 / 62.9 / 64.8 / 65.2 / 550 -- it wins while the chain
-    // workgroups leave a free slot on (almost) every CU, and loses once the tiles have to share CUs with running chain
-    // workgroups and queue behind them. Hence: merged up to 9/8 x CUs chain workgroups unless a flag says otherwise.
-    const bool merged = use_chain && backward && NL == 1 && !(P->flags & MPQE_STEP_SPLIT_TAIL) &&
-                        ((P->flags & MPQE_STEP_MERGE_TAIL) || hp.blk_off[nb] <= STEP_CUS + STEP_CUS / 8);
-    {
-        ZeroSegs &zs = pa.zs;
-        if (backward && !phase_bwd && !phase_score && (P->flags & MPQE_STEP_ZERO_GRADS)) {     // (step in several calls: the first one fills)
-            auto seg = [&](float *ptr, long long n) {
-                if (!ptr || n <= 0) return;
-                // (merged launch: a root matrix that tiles / a rank-1 op of the SAME launch write whole is not zero-filled
-                // -- the fill would race with its writers, who store instead of adding)
-                for (size_t k = 0; merged && k < hp.whole_roots.size(); ++k)
-                    if (gp.root[hp.whole_roots[k]] == ptr) return;
-                for (int k = 0; k < zs.count; ++k)
-                    if (zs.p[k] == ptr) return;                  // shared layers repeat their buffers
-                if (zs.count >= PREP_MAX_SEGS) return;
-                zs.p[zs.count] = ptr;
-                zs.n[zs.count] = n;
-                zs.block0[zs.count] = zblocks;
-                zblocks += (n + PREP_ZERO_FLOATS_PER_BLOCK - 1) / PREP_ZERO_FLOATS_PER_BLOCK;
-                zs.count++;
-            };
-            for (int l = 0; l < P->num_layers; ++l) {
-                // (relation matrices: the written ones are stored by their writers, the untouched ones are zero-filled
-                // by spare workgroups of the weight-gradient launch, off the critical path: ZMat)
-                seg(G->root[l], (long long)D * D);
-                seg(G->bias[l], D);
-            }
-            seg(G->mode_emb, (long long)P->num_modes * D);
-            if (learned) {
-                seg(G->readout_w0, (long long)D * hp.ro_kin);
-                seg(G->readout_b0, D);
-                seg(G->readout_w2, (long long)D * D);
-                seg(G->readout_b2, D);
-            }
-            // (SPARSE_TABLES: only the touched rows of the table gradients are ever read; they are written, not accumulated)
-            if (use_chain && !use_touch && !sparse_tables) {
-                // chain form WITHOUT a touch plan: the chain workgroups add into the tables with atomics -- a zero fill inside
-                // their own launch would race with them: a launch of its own in front
-                ZeroSegs zt;
-                memset(&zt, 0, sizeof(zt));
-                long long ztb = 0;
-                for (int m = 0; m < P->num_modes && zt.count < PREP_MAX_SEGS; ++m) {
-                    if (!G->tables[m] || P->table_rows[m] <= 0) continue;
-                    bool dup = false;
-                    for (int k = 0; k < zt.count; ++k) dup = dup || zt.p[k] == G->tables[m];
-                    if (dup) continue;
-                    zt.p[zt.count] = G->tables[m];
-                    zt.n[zt.count] = (long long)P->table_rows[m] * D;
-                    zt.block0[zt.count] = ztb;
-                    ztb += (zt.n[zt.count] + PREP_ZERO_FLOATS_PER_BLOCK - 1) / PREP_ZERO_FLOATS_PER_BLOCK;
-                    zt.count++;
-                }
-                zt.block0[zt.count] = ztb;
-                if (ztb > 0) hipLaunchKernelGGL(step_zero_kernel, dim3((unsigned)ztb), dim3(256), 0, s, zt);
-            } else
-                for (int m = 0; m < P->num_modes && !sparse_tables; ++m) seg(G->tables[m], (long long)P->table_rows[m] * D);
-            zs.block0[zs.count] = zblocks;
-        }
-        if (use_chain) {
-            const int tpd = D / 64;
-            pa.ua = ua;
-            pa.ua.ops = reinterpret_cast<const UOp *>(db + hp.o_uopf);
-            pa.ua.nops = (int)hp.uops_f.size();
-            pa.ua.epoch = epoch_f;
-            pa.ublocks = pa.ua.nops * pa.ua.chunks;
-            // (forward only: just the copies a learned readout's forward multiplies by -- the plan lists them last... not
-            // sorted: all of them are made, the backward levels' are then unused)
-            pa.tblocks = (backward || hp.ro_chain) ? (int)hp.wt_slots.size() * tpd * tpd : 0;
-            wt_all = pa.tblocks;
-            if (!backward && hp.ro_chain && !dbg_on("FWD_ALL_COPIES")) {
-                // (the readout's forward multiplies by the TRANSPOSED blocks of its own two layers; the relation matrices'
-                // copies and the plain column blocks belong to the backward programmes)
-                int n = 0;
-                bool fits = true;
-                for (size_t k = 0; k < hp.wt_slots.size(); ++k)
-                    if (hp.wt_slots[k].mat < 0 && !hp.wt_slots[k].plain && hp.wt_slots[k].layer >= hp.ro_layer) {
-                        if (n < 8) pa.tsel[n] = (int)k;
-                        else fits = false;
-                        ++n;
-                    }
-                if (fits && n > 0 && n < (int)hp.wt_slots.size()) {
-                    pa.tsel_n = n;
-                    pa.tblocks = n * tpd * tpd;
-                    pa.tskip = (unsigned)(wt_all - pa.tblocks);
-                }
-            }
-            pa.sblocks = 0;
-            if (build_touch) {
-                const TouchLayout TL = touch_layout(hp.touch_M, 0);
-                char *tb = reinterpret_cast<char *>(touch);
-                const size_t Mp = (size_t)hp.ts_blocks * TSORT_THREADS * tsort_rounds(hp.touch_M);
-                TSortArgs &ts = pa.ts;
-                ts.tm = reinterpret_cast<const TouchMeta *>(db + hp.o_tmeta);
-                ts.anchor_ids = ids;
-                ts.targets = tg;
-                ts.negs = ng;
-                ts.node_map = nm;
-                ts.map_len = (long long)P->node_map_len;
-                ts.ka = reinterpret_cast<unsigned *>(wb + hp.o_tsort);
-                ts.kb = ts.ka + Mp;
-                ts.va = ts.kb + Mp;
-                ts.vb = ts.va + Mp;
-                ts.hist = ts.vb + Mp;
-                ts.counter = epoch_f + 40;
-                ts.keys_out = reinterpret_cast<tkey_t *>(tb + TL.keys);
-                ts.perm = reinterpret_cast<int *>(tb + TL.perm);
-                ts.erow = nullptr;
-                ts.th_out = reinterpret_cast<TouchHeader *>(tb);
-                ts.M = (int)hp.touch_M;
-                ts.key_bits = hp.ts_key_bits;
-                ts.row_bits = hp.ts_row_bits;
-                ts.nblk = hp.ts_blocks;
-                ts.rounds = tsort_rounds(hp.touch_M);
-                ts.fail = dbg_on("TSORT_FAIL") ? 1 : 0;
-                ts.stamps = nullptr;
-                if (dbg_on("TSORT_TRAIL")) pa.strail = hp.ts_blocks;
-                else {
-                    pa.sna = hp.sort_na;
-                    pa.sxrank = 0;
-                    for (int x = 0; x < STEP_XCDS; ++x) pa.sxrank |= (unsigned)(hp.sort_rank[x] + 1) << (4 * x);
-                    pa.sblocks = (hp.ts_blocks + pa.sna - 1) / pa.sna * 8;
-                }
-            }
-            // The chain workgroups wait for vectors / matrices that the prologue workgroups produce, so the prologue
-            // workgroups come first in the launch: a producer is never queued behind a consumer. (Every wait is bounded
-            // all the same: a launch that could not make progress reports MPQE_FLAG_INTERNAL instead of hanging.)
-            // (Dealing the prologue workgroups only to the XCDs the chain workgroups leave room on was measured and is
-            // worse: those are the XCDs of the heaviest batches, whose workgroups then lose their CU to themselves --
-            // chain kernel 53.5 us against 41.4 with the prologue spread over all eight.)
-            // (sblocks = 8 x rows; a row holds sna sort workgroups and 8 - sna prologue items)
-            pa.lead = (pa.sblocks / 8 * pa.sna + pa.ublocks + pa.tblocks + 7) / 8 * 8;
-            if (pa.lead < pa.sblocks) pa.lead = pa.sblocks;
-            pa.nchain = (int)hp.crefs.size();
-            if (NL == 1) {
-                // (two workgroups per CU by registers and LDS; D = 256: one)
-                const int slots = (D == 256 || (P->flags & MPQE_STEP_EIGHT_WAVES)) ? STEP_CUS : 2 * STEP_CUS;
-#ifdef MPQE_EMU
-                const bool fits = false && slots;       // (the host emulator runs a launch's workgroups one after the other, in order)
-#else
-                // (the placement grid's holes leave at once: only the real chain workgroups hold slots)
-                const bool fits = pa.sblocks + hp.blk_off[nb] + 32 <= slots;
-#endif
-                const int force = mpqe_dbg_value("PROLOGUE_LAST", -1);       // (timing experiments)
-                pa.plast = fits && hp.pl_na > 0 && (force >= 0 ? force != 0 : pa.lead > slots / 2) ? 1 : 0;
-                if (pa.plast) {
-                    pa.plna = hp.pl_na;
-                    pa.plxrank = 0;
-                    for (int x = 0; x < STEP_XCDS; ++x) pa.plxrank |= (unsigned)(hp.pl_rank[x] + 1) << (4 * x);
-                    const int held = pa.sblocks / 8 * (8 - pa.sna);          // items the sort rows hold
-                    const int rest = pa.ublocks + pa.tblocks > held ? pa.ublocks + pa.tblocks - held : 0;
-                    pa.lead = pa.sblocks + (rest + pa.plna - 1) / pa.plna * 8;
-                }
-            }
-            // (mpqe_step_extra_t.xcd_shift: idle workgroups in front of the chain workgroups move every one of them that many
-            // XCDs on -- forward-only steps on several streams at once)
-            if (!backward && extra && extra->xcd_shift > 0 && extra->xcd_shift < STEP_XCDS && !pa.plast && pa.sblocks == 0)
-                pa.lead += extra->xcd_shift;
-            if (dbg_on("DUMP_PLAN"))
-                fprintf(stderr, "launch: sort rows %d (x8) | pre-pass %d transposes %d | lead %d | chain %d of %d | prologue behind the chain %d (XCDs %d)\n",
-                        pa.sblocks / 8, pa.ublocks, pa.tblocks, pa.lead, hp.blk_off[nb], pa.nchain, pa.plast, pa.plna);
-            pa.slots = reinterpret_cast<const WtSlot *>(db + hp.o_wtslots);
-            pa.WT = WT;
-            pa.wt_count = epoch_f + 32;
-            pa.late = dbg_on("HANDOFF_LATE") ? 1 : 0;
-            pa.fwd_done = merged && pa.ublocks > 0 ? epoch_f + 33 : nullptr;
-            pa.ua.vt_through = merged ? 1 : 0;
-        } else if (zblocks > 0) {
-            hipLaunchKernelGGL(step_zero_kernel, dim3((unsigned)zblocks), dim3(256), 0, s, zs);
-        }
-    }
-    LossMeta lm;
-    memset(&lm, 0, sizeof(lm));
-    lm.nb = nb;
-    lm.chain = use_chain ? 1 : 0;
-    for (int i = 0; i < nb; ++i) {
-        lm.B[i] = hp.sd.b[i].B;
-        lm.weight[i] = hp.sd.b[i].weight;
-        lm.blk_off[i] = hp.blk_off[i];
-    }
-    lm.blk_off[nb] = hp.blk_off[nb];
-    const float *bterms = reinterpret_cast<const float *>(wb + hp.o_bterms);
-    if (NL > 1) {       // fork: the lanes start after the descriptor uploads and the prologue
-        (void)hipEventRecord(reinterpret_cast<hipEvent_t>(lanes->fork_event), s);
-        for (int l = 1; l < NL; ++l) (void)hipStreamWaitEvent(ls[l], reinterpret_cast<hipEvent_t>(lanes->fork_event), 0);
-    }
-    float *slabs = reinterpret_cast<float *>(wb + hp.o_slabs), *parts = reinterpret_cast<float *>(wb + hp.o_parts);
-    TailArgs ta;
-    ta.wsrc = reinterpret_cast<const WSource *>(db + hp.o_wsrc);
-    ta.wblock = reinterpret_cast<const WBlock *>(db + hp.o_wblock);
-    ta.nwsrc = (int)hp.wsrc.size();
-    ta.wblocks = hp.wblocks_total;
-    ta.vsrc = reinterpret_cast<const VSource *>(db + hp.o_vsrc);
-    ta.vblock = reinterpret_cast<const int *>(db + hp.o_vblock);
-    ta.nvsrc = (int)hp.vsrc.size();
-    ta.vblocks = hp.vblocks_total;
-    ta.anchor_off = reinterpret_cast<const int *>(db + hp.o_anchor);
-    ta.nb = nb;
-    ta.D = D;
-    ta.tile_n = hp.tile_n;
-    ta.ux = 0;
-    ta.runs_front = ta.runs_n = 0;
-    ta.runs_out = nullptr;
-    ta.node_map = nm;
-    ta.map_len = (long long)P->node_map_len;
-    ta.anchor_ids = ids;
-    ta.slabs = slabs;
-    ta.parts = parts;
-    // weight-gradient launch over the block table entries [first, first + count) on stream `on`
-    ta.zmats = reinterpret_cast<const ZMat *>(db + hp.o_zmats);
-    ta.zper = (int)(((long long)D * D + ZMAT_FLOATS_PER_BLOCK - 1) / ZMAT_FLOATS_PER_BLOCK);
-    ta.zblocks = 0;
-    ta.ublocks = 0;
-    ta.stamps = nullptr;
-    UArgs ub = ua;
-    ub.ops = reinterpret_cast<const UOp *>(db + hp.o_uopb);
-    ub.nops = (int)hp.uops_b.size();
-    ub.epoch = epoch_b;
-    // the step's reduction: a launch of its own
-    ReduceArgs ra;
-    memset(&ra, 0, sizeof(ra));
-    ra.nmat = -1;
-    const long long r_elems = (long long)D * D;
-    const unsigned r_gx = (unsigned)((r_elems + 255) / 256);
-    unsigned r_trows = 0;         // entity-table gradient rows: 256 / (D / 4) sorted positions per workgroup
-    if (use_touch && !(STEP_DBG & 1)) {
-        const long long per = 256 / (D / 4), tblk = (hp.touch_M + per - 1) / per;
-        r_trows = (unsigned)((tblk + r_gx - 1) / r_gx);
-    }
-    ra.groups = reinterpret_cast<const RGroup *>(db + hp.o_groups);
-    ra.ngroups = (int)hp.groups.size();
-    ra.D = D;
-    ra.gp = gp;
-    ra.slabs = slabs;
-    ra.partial = parts;
-    ra.vec = (int)(D % 4 == 0);
-    ra.zeroed = (P->flags & MPQE_STEP_ZERO_GRADS) ? 1 : 0;
-    ra.sd = sd;
-    ra.terms = terms;
-    ra.loss = loss;
-    ra.lm = lm;
-    ra.bterms = bterms;
-    ra.rank1 = reinterpret_cast<const Rank1 *>(db + hp.o_rank1);
-    ra.VT = VT;
-    ra.epoch_b = use_chain ? epoch_b : nullptr;
-    ra.touch = use_touch ? reinterpret_cast<const char *>(touch) : nullptr;
-    ra.touch_keys = touch_layout(hp.touch_M, 0).keys;
-    ra.touch_perm = touch_layout(hp.touch_M, 0).perm;
-    ra.DG = reinterpret_cast<const float *>(wb + hp.o_DG);
-    ra.tabs = tabs;
-    ra.table_store = ((sparse_tables || (P->flags & MPQE_STEP_ZERO_GRADS)) ? 1 : 0) | (merged ? 2 : 0);
-    ra.touch_M = (long long)hp.touch_M;
-    ra.touch_row_bits = touch_row_bits;
-    ra.err = err;
-    ra.notify = notify;
-    ra.notify_value = notify_value;
-    // (the loss and the entity-table rows of the split tail as a light launch of their own beside the weight-gradient launch
-    // -- enqueued behind it with hipExtAnyOrderLaunch, i.e. without the queue's barrier bit -- was tried: the flag is not
-    // honoured on gfx9 boards (hip_ext.h says so): the launch ran in order and the step took 4.4 us longer)
-    // The table workgroups of the reduction launch take the plan's RUN STARTS, compacted by one workgroup of the weight-gradient
-    // launch (touch_runs_block), instead of every sorted position: a step's distinct rows are at most the tables' rows -- the
-    // launch is sized for that bound (AIFB step: 326 workgroups instead of 2 752). mpqe_debug_option NO_RUNS = 1: as before.
-    const bool use_runs = use_touch && !merged && NL == 1 && D % 4 == 0 && 256 % (D / 4) == 0 && !(STEP_DBG & 1) &&
-                          !dbg_on("NO_RUNS");
-    if (use_runs) {
-        long long total_rows = 0;
-        for (int m = 0; m < P->num_modes; ++m) total_rows += P->table_rows[m];
-        const long long rmax = std::min<long long>(hp.touch_M, total_rows), per = 256 / (D / 4);
-        r_trows = (unsigned)(((rmax + per - 1) / per + r_gx - 1) / r_gx);
-        ra.runs = reinterpret_cast<const int *>(wb + hp.o_runs);
-        pa.runs_count = reinterpret_cast<int *>(wb + hp.o_runs) + hp.touch_M;
-    }
-    bool zmats_done_in_chain = false;
-    auto launch_grad_w = [&](hipStream_t on, int first, int count) {
-        TailArgs tl = ta;
-        tl.wblock = ta.wblock + first;
-        tl.wblocks = count;
-        if (first == 0 && (P->flags & MPQE_STEP_ZERO_GRADS) && !zmats_done_in_chain) tl.zblocks = (int)hp.zmats.size() * ta.zper;
-        if (first == 0) tl.ublocks = ub.nops * ub.chunks;
-        int nblocks = tl.ublocks + count + tl.zblocks;
-        // chain form: two of the eight XCDs for the post-pass' vector ops, six for the tiles (AIFB step, same box,
-        // three runs each: 64.95 / 65.15 / 65.04 us against 65.70 / 65.60 / 65.47 with both kinds everywhere; one
-        // or three XCDs: 65.8 / 66.0). mpqe_debug_option TAIL_UX overrides (0 = everywhere).
-        const int uxv = mpqe_dbg_value("TAIL_UX", 2);
-        // (only while the tiles are all resident at once on the other XCDs -- two per CU: with more of them the vector
-        // ops' XCDs would stand idle for most of the launch. AIFB step with the MLP readout, 988 tiles: 64.3 -> 52.9 us)
-        if (use_chain && first == 0 && tl.ublocks >= 4 && uxv > 0 && uxv < 8 &&
-            (count <= (8 - uxv) * 2 * (STEP_CUS / STEP_XCDS) || mpqe_dbg_value("TAIL_UX", -1) > 0)) {
-            tl.ux = uxv;
-            const int ra = (tl.ublocks + tl.ux - 1) / tl.ux, rb = (count + tl.zblocks + (8 - tl.ux) - 1) / (8 - tl.ux);
-            nblocks = 8 * (ra > rb ? ra : rb);
-        }
-        if (use_runs && first == 0 && count == hp.wblocks_total) {       // a few workgroups in front: the touch plan's run starts
-            tl.runs_n = (int)((hp.touch_M + TRUNS_PER - 1) / TRUNS_PER);
-            tl.runs_front = (tl.runs_n + 7) / 8 * 8;
-            tl.runs_out = reinterpret_cast<int *>(wb + hp.o_runs);
-            nblocks += tl.runs_front;
-        }
-        tl.stamps = g_tail_stamps && (size_t)nblocks <= g_tail_stamp_blocks ? g_tail_stamps : nullptr;
-        if (nblocks <= 0) return;
-        dim3 tgrid((unsigned)nblocks);
-        const int zeroed = (P->flags & MPQE_STEP_ZERO_GRADS) ? 1 : 0;
-        if (use_chain)
-            // (ONE tile workgroup per CU -- the launch's LDS padded beyond half a CU's -- was measured on the 988-tile step of
-            // the MLP readout: 71 - 75 us against 64; two per CU stay)
-            hipLaunchKernelGGL(step_tail_kernel<LD_T>, tgrid, dim3(256), 0, on, sd, tl, (const float *)H,
-                               (const float *)GH, hp.level_stride, gp, zeroed, lp, ub, ra);
-        else if (fast && hp.whole_ksteps)
-            hipLaunchKernelGGL(step_tail_kernel<LD_FAST>, tgrid, dim3(256), 0, on, sd, tl, (const float *)H,
-                               (const float *)GH, hp.level_stride, gp, zeroed, lp, ub, ra);
-        else if (vec)
-            hipLaunchKernelGGL(step_tail_kernel<LD_PRED>, tgrid, dim3(256), 0, on, sd, tl, (const float *)H,
-                               (const float *)GH, hp.level_stride, gp, zeroed, lp, ub, ra);
-        else
-            hipLaunchKernelGGL(step_tail_kernel<LD_SCALAR>, tgrid, dim3(256), 0, on, sd, tl, (const float *)H,
-                               (const float *)GH, hp.level_stride, gp, zeroed, lp, ub, ra);
-    };
-    // the readout's regulariser (model.py:486-490), after the launch that writes loss[0]
-    auto ro_regulariser = [&](bool with_grads) {
-        float wsum = 0.f;
-        for (int i = 0; i < nb; ++i) wsum += hp.sd.b[i].weight;
-        if (!(P->readout_weight_decay > 0.f)) return;
-        RoRegArgs rr;
-        memset(&rr, 0, sizeof(rr));
-        rr.p[0] = P->readout_w0; rr.p[1] = P->readout_b0; rr.p[2] = P->readout_w2; rr.p[3] = P->readout_b2;
-        rr.n[0] = (long long)D * hp.ro_kin; rr.n[1] = D; rr.n[2] = (long long)D * D; rr.n[3] = D;
-        if (with_grads) { rr.g[0] = G->readout_w0; rr.g[1] = G->readout_b0; rr.g[2] = G->readout_w2; rr.g[3] = G->readout_b2; }
-        rr.coef = P->readout_weight_decay * wsum;
-        rr.loss = loss;
-        if (dev_weights && with_grads) {        // (the gradients' coefficient: weight_decay x sum_i host_i x *device_i, formed on the device)
-            rr.nw = nb;
-            rr.wd = P->readout_weight_decay;
-            for (int i = 0; i < nb; ++i) {
-                rr.whost[i] = hp.sd.b[i].weight;
-                rr.wdev[i] = extra->batch_weight[i];
-            }
-        }
-        hipLaunchKernelGGL(step_ro_reg_kernel, dim3(1), dim3(1024), 0, s, rr);
-    };
-    bool loss_in_chain = false, reg_in_chain = false;
-    if (use_chain) {
-        // assemble -> levels -> scores (-> levels back -> anchor-table gradients): one launch per lane
-        ChainArgs ca;
-        ca.refs = reinterpret_cast<const ChainRef *>(db + hp.o_cref);
-        ca.ops = reinterpret_cast<const ChainOp *>(db + hp.o_cops);
-        ca.node_map = nm;
-        ca.map_len = (long long)P->node_map_len;
-        ca.mode_emb = P->mode_emb;
-        ca.num_modes = (long long)P->num_modes;
-        ca.anchor_ids = ids;
-        ca.targets = tg;
-        ca.negs = ng;
-        ca.H = H;
-        ca.GH = GH;
-        ca.WT = WT;
-        ca.VT = VT;
-        ca.epoch_f = epoch_f;
-        ca.DG = use_touch ? reinterpret_cast<float *>(wb + hp.o_DG) : nullptr;
-        // (a plan built at pack time also holds the id -> table row hop of every entry; a step that builds its own plan
-        // resolves the ids itself)
-        ca.erow = use_touch && !build_touch ? reinterpret_cast<const int *>(reinterpret_cast<const char *>(touch) +
-                                                                            touch_layout(hp.touch_M, 0).erow) : nullptr;
-        ca.Manchor = (long long)hp.anchor_off[nb];
-        ca.Gtot = hp.sd.graphs_total;
-        ca.parts = reinterpret_cast<float *>(wb + hp.o_parts);
-        ca.block_terms = reinterpret_cast<float *>(wb + hp.o_bterms);
-        ca.level_stride = hp.level_stride;
-        ca.margin = margin;
-        ca.eps = 1e-8f;
-        ca.s_pos = spos;
-        ca.s_neg = sneg;
-        ca.terms = terms;
-        ca.q_out = extra ? extra->query_out : nullptr;
-        ca.err = err;
-        ca.backward = backward ? 1 : 0;
-        ca.stamps = g_chain_stamps && 2 * hp.crefs.size() + (size_t)hp.ts_blocks <= g_chain_stamp_blocks ? g_chain_stamps : nullptr;
-        if (ca.stamps && build_touch) pa.ts.stamps = g_chain_stamps + 16 * (long long)hp.crefs.size();     // (behind the chain entries)
-        {
-            ca.cb = 0;
-            ca.nchain = pa.nchain;
-            ca.cv_gran = pa.ublocks > 0 ? reinterpret_cast<const unsigned long long *>(db + hp.o_gran) : nullptr;
-            ca.epoch_b = epoch_b;
-            ca.wt_count = pa.tblocks > 0 ? pa.wt_count : nullptr;
-            ca.wt_blocks = wt_all;
-            // (counters and their epoch advance on merged steps only: targets are epoch x count)
-            ca.done = merged ? reinterpret_cast<unsigned *>(db + hp.o_done) : nullptr;
-            ca.arrive = ca.done ? ca.done + hp.done_inc.size() : nullptr;
-            ca.done_inc = reinterpret_cast<const int *>(db + hp.o_done_inc);
-            ca.ro = hp.ro_chain ? 1 : 0;
-            ca.wt_early = hp.ro_chain && P->readout == MPQE_READOUT_CONCAT ? 1 : 0;
-            ca.ro_layer = hp.ro_layer;
-            ca.ro_scatter = P->readout_scatter;
-            PostArgs po;
-            memset(&po, 0, sizeof(po));
-            long long grid_blocks = pa.lead + pa.nchain + zblocks;
-            // (split tail: the untouched relation matrices' zero fill rides behind the chain workgroups; mpqe_debug_option
-            // ZMATS_IN_TAIL = 1: by workgroups of the weight-gradient launch, as before)
-            const bool zm_here = !merged && backward && (P->flags & MPQE_STEP_ZERO_GRADS) && !hp.zmats.empty() && !dbg_on("ZMATS_IN_TAIL") &&
-                                 !phase_bwd && !phase_score;
-            if (zm_here) {
-                po.zmblocks = (int)hp.zmats.size() * ta.zper;
-                po.zmats = ta.zmats;
-                po.zper = ta.zper;
-                po.D = D;
-                po.gp = gp;
-                grid_blocks += po.zmblocks;
-                zmats_done_in_chain = true;
-            }
-            if (merged) {
-                unsigned *done = reinterpret_cast<unsigned *>(db + hp.o_done);
-                po.zpad = (int)((zblocks + 7) / 8 * 8);
-                if (po.zpad == 0) po.zpad = 8;              // (> 0 marks the merged launch)
-                po.zmblocks = (P->flags & MPQE_STEP_ZERO_GRADS) ? (int)hp.zmats.size() * ta.zper : 0;
-                po.ublocks = ub.nops * ub.chunks;
-                po.na = hp.post_na;
-                po.xrank = 0;
-                for (int x = 0; x < STEP_XCDS; ++x) po.xrank |= (unsigned)(hp.post_rank[x] + 1) << (4 * x);
-                po.ppad = (po.zmblocks + po.ublocks + po.na - 1) / po.na * po.na;
-                po.wblocks = hp.wblocks_total;
-                po.zper = ta.zper;
-                po.D = D;
-                po.tile_n = hp.tile_n;
-                po.zeroed = (P->flags & MPQE_STEP_ZERO_GRADS) ? 1 : 0;
-                po.ub = ub;
-                po.ub.done = done;
-                po.ub.done_inc = reinterpret_cast<const int *>(db + hp.o_done_inc);
-                po.ub.dm = hp.dm;
-                po.ub.fwd_done = pa.fwd_done;
-                po.ub.epoch_m = epoch_f + 48;
-                po.ub.fwd_blocks = pa.ublocks;
-                po.wblock = ta.wblock;
-                po.zmats = ta.zmats;
-                po.slabs = slabs;
-                po.H = H;
-                po.GH = GH;
-                po.level_stride = hp.level_stride;
-                po.gp = gp;
-                po.done = done;
-                po.done_inc = po.ub.done_inc;
-                po.epoch_m = epoch_f + 48;
-                po.err = err;
-                po.stamps = g_tail_stamps && (size_t)po.wblocks <= g_tail_stamp_blocks ? g_tail_stamps : nullptr;
-                grid_blocks = pa.lead + pa.nchain + po.zpad +
-                              (long long)(po.ppad + po.wblocks + po.na - 1) / po.na * 8;       // (8 workgroups per `na` items)
-            }
-            grid_blocks += pa.strail;
-            dim3 cgrid((unsigned)grid_blocks);
-            // forward-only: loss, epoch advance and notification by the launch's last workgroup (chain_finish) instead of a
-            // launch behind it. mpqe_debug_option LOSS_LAUNCH = 1: step_loss_kernel as before
-            FinArgs fin;
-            memset(&fin, 0, sizeof(fin));
-            if (!backward && NL == 1 && !dbg_on("LOSS_LAUNCH")) {
-                fin.count = epoch_f + 42;
-                fin.loss = loss;
-                fin.bterms = bterms;
-                fin.epoch_f = epoch_f;
-                fin.bump_b = pa.tblocks > 0 ? 1 : 0;
-                fin.notify = notify;
-                fin.notify_value = notify_value;
-                fin.err = err;
-                fin.lm = lm;
-                loss_in_chain = true;
-                if (learned && extra && extra->readout_norms && P->readout_weight_decay > 0.f) {
-                    float wsum = 0.f;
-                    for (int i = 0; i < nb; ++i) wsum += hp.sd.b[i].weight;
-                    fin.reg_norms = extra->readout_norms;
-                    fin.reg_coef = P->readout_weight_decay * wsum;
-                    reg_in_chain = true;
-                }
-            }
-            mark(s);
-#define LAUNCH_CHAIN(THREADS, ...)                                                                                       \
-    do {                                                                                                                 \
-        if (fin.count)                                                                                                   \
-            hipLaunchKernelGGL((step_chain_fwd_kernel<__VA_ARGS__>), cgrid, dim3(THREADS), 0, s, sd, lp, tabs, ca, pa, po, fin); \
-        else                                                                                                             \
-            hipLaunchKernelGGL((step_chain_kernel<__VA_ARGS__>), cgrid, dim3(THREADS), 0, s, sd, lp, tabs, ca, pa, po);  \
-    } while (0)
-            if (hp.ro_chain) {
-                // (a learned readout on the chain: its own instances -- the others' code stays as it was)
-                if (D == 64) LAUNCH_CHAIN(256, 1, 1, 4, true);
-                else if (D == 128 && (P->flags & MPQE_STEP_NO_KSPLIT)) LAUNCH_CHAIN(256, 2, 1, 4, true);
-                else if (D == 128) LAUNCH_CHAIN(256, 4, 2, 4, true);
-                else LAUNCH_CHAIN(256, 4, 1, 4, true);
-            } else if (D == 64) LAUNCH_CHAIN(256, 1, 1);
-            else if (D == 128 && (P->flags & MPQE_STEP_NO_KSPLIT)) LAUNCH_CHAIN(256, 2, 1);
-            else if (D == 128 && (P->flags & MPQE_STEP_EIGHT_WAVES)) LAUNCH_CHAIN(512, 2, 2, 8);
-            else if (D == 128) LAUNCH_CHAIN(256, 4, 2);
-            else LAUNCH_CHAIN(256, 4, 1);
-#undef LAUNCH_CHAIN
-            mark(s);
-        }
-        if (!backward) {
-            for (int l = 1; l < NL; ++l) {
-                (void)hipEventRecord(reinterpret_cast<hipEvent_t>(lanes->join_event[l]), ls[l]);
-                (void)hipStreamWaitEvent(s, reinterpret_cast<hipEvent_t>(lanes->join_event[l]), 0);
-            }
-            if (!loss_in_chain)
-                hipLaunchKernelGGL(step_loss_kernel, dim3(1), dim3(1024), 0, s, sd, (const float *)terms, loss, lm, bterms,
-                                   use_chain ? epoch_f : (unsigned *)nullptr, pa.tblocks > 0 ? 1 : 0, notify, notify_value,
-                                   (const int32_t *)err);
-            if (learned && !reg_in_chain) ro_regulariser(false);
-            return mpqe_launch_status();
-        }
-        // (a side stream for the post-pass / table rows beside the tiles was measured: the cross-stream fork and join
-        // cost more than the overlap gains -- 93.8 us per step against 81.8 with everything on one stream)
-        mark(s);
-        if (!merged) launch_grad_w(s, 0, hp.wblocks_total);
-        mark(s);
-    }
-    // ---- forward
-    const float *Qc = P->readout == MPQE_READOUT_CALLER ? reinterpret_cast<const float *>(wb + hp.o_Q) : nullptr;
-    float *GQc = P->readout == MPQE_READOUT_CALLER ? reinterpret_cast<float *>(wb + hp.o_GQ) : nullptr;
-    // learned readouts: gather -> Linear - ReLU - Linear -> reduction over each graph's rows, and the way back
-    RoArgs roa;
-    memset(&roa, 0, sizeof(roa));
-    roa.kind = P->readout;
-    roa.op = P->readout_scatter;
-    roa.mrows = hp.ro_rows;
-    roa.kin = hp.ro_kin;
-    roa.level_stride = hp.level_stride;
-    float *ro_x = nullptr, *ro_gx = nullptr, *ro_h = nullptr, *ro_y = nullptr, *ro_gy = nullptr, *ro_gh = nullptr;
-    if (learned) {
-        const long long lv = (long long)hp.sd.b[0].L * hp.level_stride;
-        ro_x = hp.ro_direct ? H + lv : reinterpret_cast<float *>(wb + hp.o_rx);
-        ro_gx = hp.ro_direct ? GH + lv : reinterpret_cast<float *>(wb + hp.o_rgx);
-        ro_h = reinterpret_cast<float *>(wb + hp.o_rh);
-        ro_y = reinterpret_cast<float *>(wb + hp.o_ry);
-        ro_gy = reinterpret_cast<float *>(wb + hp.o_rgy);
-        ro_gh = reinterpret_cast<float *>(wb + hp.o_rgh);
-    }
-    auto ro_blocks = [](long long threads) { return dim3((unsigned)((threads + 255) / 256)); };
-    auto ro_forward = [&]() -> int {
-        if (!hp.ro_direct)
-            hipLaunchKernelGGL(step_ro_gather_kernel, ro_blocks(roa.mrows * (roa.kin / 4)), dim3(256), 0, s, sd, roa,
-                               (const float *)H, ro_x);
-        int st = mpqe_linear_fwd(ro_x, roa.mrows, P->readout_w0, roa.kin, P->readout_b0, roa.kin, D, 1, 0, ro_h, s);
-        if (st) return st;
-        st = mpqe_linear_fwd(ro_h, roa.mrows, P->readout_w2, D, P->readout_b2, D, D, 0, 0, ro_y, s);
-        if (st) return st;
-        return MPQE_OK;         // (the reduction over each graph's rows: inside the score kernel)
-    };
-    auto ro_backward = [&]() -> int {
-        void *lw = wb + hp.o_rlin;         // (the score kernel has written the rows' gradients)
-        int st = mpqe_linear_bwd(ro_h, roa.mrows, P->readout_w2, D, ro_y, ro_gy, D, D, 0, 0, ro_gh, G->readout_w2, D,
-                                 G->readout_b2, lw, hp.rlin_bytes, s);
-        if (st) return st;
-        st = mpqe_linear_bwd(ro_x, roa.mrows, P->readout_w0, roa.kin, ro_h, ro_gh, roa.kin, D, 1, 0, ro_gx,
-                             G->readout_w0, roa.kin, G->readout_b0, lw, hp.rlin_bytes, s);
-        if (st) return st;
-        if (!hp.ro_direct)
-            hipLaunchKernelGGL(step_ro_spread_kernel, ro_blocks(hp.sd.rows_total * (D / 4)), dim3(256), 0, s, sd, roa,
-                               (const float *)ro_gx, GH);
-        return MPQE_OK;
-    };
-    for (int l = 0; !use_chain && !phase_bwd && !phase_score && l < NL; ++l) {
-        const long long nr = row0[l + 1] - row0[l], ngr = gr0[l + 1] - gr0[l];
-        const long long waves = nr + 2 * ngr;
-        const int lpr_h = [&] { if (!vec_tab) return 64; int q = 1; while (q < 64 && q * 4 < D) q <<= 1; return q; }();
-        const long long per_block = 4 * (64 / lpr_h);
-        hipLaunchKernelGGL(step_assemble_kernel, dim3((unsigned)((waves + per_block - 1) / per_block)), dim3(256), 0,
-                           ls[l], sd, tabs, nm, (long long)P->node_map_len, P->mode_emb, (long long)P->num_modes, ids,
-                           tg, ng, H, tpos, tneg, err, vec_tab, row0[l], nr, gr0[l], ngr);
-    }
-    for (int p = 0; !use_chain && !phase_bwd && !phase_score && p < hp.Lmax; ++p)
-        for (int l = 0; l < NL; ++l) {
-            if (p >= hp.lane_Lmax[l]) continue;
-            const float *hin = H + (long long)p * hp.level_stride;
-            float *hout = H + (long long)(p + 1) * hp.level_stride;
-            const TileRef *gf = reinterpret_cast<const TileRef *>(db + hp.o_tf[l][p]);
-            dim3 grid((unsigned)hp.tfwd[l][p].size());
-            mark(ls[l]);
-            if (fast)
-                hipLaunchKernelGGL(step_layer_fwd_kernel<LD_FAST>, grid, dim3(256), 0, ls[l], sd, lp, p, gf, hin, hout);
-            else if (vec)
-                hipLaunchKernelGGL(step_layer_fwd_kernel<LD_PRED>, grid, dim3(256), 0, ls[l], sd, lp, p, gf, hin, hout);
-            else
-                hipLaunchKernelGGL(step_layer_fwd_kernel<LD_SCALAR>, grid, dim3(256), 0, ls[l], sd, lp, p, gf, hin,
-                                   hout);
-            mark(ls[l]);
-        }
-#define LAUNCH_SCORE(BWD, NJ, GHP, L)                                                                               \
-    hipLaunchKernelGGL((step_score_kernel<BWD, NJ>), dim3((unsigned)((gr0[L + 1] - gr0[L] + 3) / 4)), dim3(256), 0, \
-                       ls[L], sd, (const float *)H, hp.level_stride, (const float *)tpos, (const float *)tneg,     \
-                       margin, 1e-8f, spos, sneg, terms, GHP, tabs, nm, (long long)P->node_map_len, tg, ng, gr0[L], \
-                       gr0[L + 1] - gr0[L], (const float *)Qc, GQc, \
-                       (const float *)(learned ? ro_y : nullptr), learned ? ro_gy : (float *)nullptr, roa.op)
-#define LAUNCH_SCORE_D(BWD, GHP, L)                  \
-    if (D <= 64) LAUNCH_SCORE(BWD, 1, GHP, L);       \
-    else if (D <= 128) LAUNCH_SCORE(BWD, 2, GHP, L); \
-    else if (D <= 256) LAUNCH_SCORE(BWD, 4, GHP, L); \
-    else LAUNCH_SCORE(BWD, 8, GHP, L)
-    auto join = [&]() {
-        for (int l = 1; l < NL; ++l) {
-            (void)hipEventRecord(reinterpret_cast<hipEvent_t>(lanes->join_event[l]), ls[l]);
-            (void)hipStreamWaitEvent(s, reinterpret_cast<hipEvent_t>(lanes->join_event[l]), 0);
-        }
-    };
-    if (phase_fwd) return mpqe_launch_status();     // the node states of every level are in the workspace (mpqe_step_states_layout)
-    if (learned && !use_chain) {
-        const int st = ro_forward();
-        if (st) return st;
-    }
-    if (!backward) {      // (not reached with the chain kernel)
-        for (int l = 0; l < NL; ++l) { LAUNCH_SCORE_D(false, (float *)nullptr, l); }
-        join();
-        hipLaunchKernelGGL(step_loss_kernel, dim3(1), dim3(1024), 0, s, sd, (const float *)terms, loss, lm, bterms,
-                           use_chain ? epoch_f : (unsigned *)nullptr, 0, notify, notify_value, (const int32_t *)err);
-        if (learned) ro_regulariser(false);
-        return mpqe_launch_status();
-    }
-
-    // ---- backward (the score kernel's backward instance writes scores and hinge terms too; the loss
-    // itself is reduced by the last launch of the step)
-    // (the caller's readout: its own call for the scores -- embeddings in, their gradients out --, then the caller writes the
-    // rows of gH[L_b] and the last call takes it from there)
-    for (int l = 0; !use_chain && !phase_bwd && l < NL; ++l) { LAUNCH_SCORE_D(true, GH, l); }
-    if (phase_score) return mpqe_launch_status();
-    if (learned && !use_chain) {
-        const int st = ro_backward();
-        if (st) return st;
-    }
-#undef LAUNCH_SCORE_D
-#undef LAUNCH_SCORE
-    for (int p = hp.Lmax - 1; !use_chain && p >= 0; --p)
-        for (int l = 0; l < NL; ++l) {
-            if (p >= hp.lane_Lmax[l]) continue;
-            const float *gout = GH + (long long)(p + 1) * hp.level_stride;
-            const float *hin = H + (long long)p * hp.level_stride;
-            float *gin = GH + (long long)p * hp.level_stride;
-            const TileRef *gb = reinterpret_cast<const TileRef *>(db + hp.o_tb[l][p]);
-            dim3 grid((unsigned)hp.tbwd[l][p].size());
-            mark(ls[l]);
-            if (fast)
-                hipLaunchKernelGGL(step_layer_bwd_x_kernel<LD_FAST>, grid, dim3(256), 0, ls[l], sd, lp, p, gb, gout,
-                                   hin, gin, add_states);
-            else if (vec)
-                hipLaunchKernelGGL(step_layer_bwd_x_kernel<LD_PRED>, grid, dim3(256), 0, ls[l], sd, lp, p, gb, gout,
-                                   hin, gin, add_states);
-            else
-                hipLaunchKernelGGL(step_layer_bwd_x_kernel<LD_SCALAR>, grid, dim3(256), 0, ls[l], sd, lp, p, gb,
-                                   gout, hin, gin, add_states);
-            mark(ls[l]);
-        }
-    join();
-    if (!use_chain) {
-        mark(s);
-        launch_grad_w(s, 0, hp.wblocks_total);
-        mark(s);
-        // bias / variable-row partials and anchor-table gradients (the chain kernel does them itself)
-        const unsigned small_blocks = (unsigned)(ta.vblocks + (hp.anchor_off[nb] + 3) / 4);
-        if (small_blocks)
-            hipLaunchKernelGGL(step_tail_small_kernel, dim3(small_blocks), dim3(256), 0, s, sd, ta, tabs,
-                               (const float *)H, (const float *)GH, hp.level_stride);
-    }
-    {
-        // (matrix groups first in the table, vector groups behind them: then the vector groups share ONE row of the launch)
-        int nmat = 0;
-        const int ng = (int)hp.groups.size();
-        while (nmat < ng && (hp.groups[nmat].kind <= 1 || hp.groups[nmat].kind >= 4)) ++nmat;
-        bool packed = ra.vec && D % 4 == 0 && 256 % (D / 4) == 0 && !dbg_on("REDUCE_ROWS") && (ng - nmat) * VEC_SLICES + 1 <= (int)r_gx;
-        for (int k = nmat; k < ng; ++k) packed = packed && (hp.groups[k].kind == 2 || hp.groups[k].kind == 3);
-        ra.nmat = packed ? nmat : -1;
-        dim3 grid(r_gx, (unsigned)(packed ? nmat + 1 : ng + 1) + r_trows);
-        mark(s);
-        hipLaunchKernelGGL(step_reduce_kernel, grid, dim3(256), 0, s, ra);
-        mark(s);
-    }
-    if (learned) ro_regulariser(true);
-    return mpqe_launch_status();
-}
+// the step's host driver: plan lookup, argument checks, the two launch forms, mpqe_step_forward_backward_ex
+#include "step_drive.h"
