@@ -271,6 +271,32 @@ int mpqe_hinge_fwd(const float *pos, const float *neg, int64_t n, float margin, 
 int mpqe_hinge_bwd(const float *pos, const float *neg, int64_t n, float margin, const float *grad_loss /*[1]*/,
                    float *grad_pos, float *grad_neg, void *stream);
 
+/* ---- answering a query: all rows of one mode's table ranked against Q query embeddings ----------------------
+ * (the reference has no such call; the score is the one its model gives a candidate, model.py:452:)
+ *   score(i, r) = cosine_similarity(q[i], table[r] / ||table[r]||, eps)
+ * with the row normalisation of mpqe_embed_l2norm_fwd and the norm clamp of mpqe_cosine_fwd, formed as
+ * ((q[i] . table[r]) * 1/||table[r]||) * 1/max(||q[i]||, eps) on the fp32 MFMA tile -- a function of q[i] and table[r] alone,
+ * so rank, top-k and exclusions agree exactly. A zero table row scores 0; a NaN score ranks last (-inf). The [Q, N] score
+ * matrix is never written to memory. Everything is in TABLE ROWS; the caller translates entity ids.
+ * Total order: higher fp32 score first, the smaller row on equal scores.
+ *   excl_offsets [Q+1], excl_rows [num_excluded]: CSR of the rows NOT eligible for query i, each list sorted ascending
+ *             (repeats allowed; a descent ORs MPQE_FLAG_BAD_INDEX). Both NULL / num_excluded 0: every row is eligible.
+ *   topk_rows, topk_scores [Q, k] (k > 0): the first min(k, eligible_i) eligible rows of query i in the total order,
+ *             then -1 / -inf. k <= 128 (the per-query candidate lists live in LDS), MPQE_ERR_UNSUPPORTED above.
+ *   rank [Q] (needs target_rows): 1 + the number of eligible rows other than the target that precede the target. The
+ *             target itself is never excluded, listed or not (filtered evaluation lists every known answer).
+ *   target_scores [Q] (needs target_rows; may be NULL): score(i, target_rows[i]).
+ * A target or excluded row outside [0, table_rows) ORs MPQE_FLAG_BAD_INDEX into err and is not dereferenced: such a
+ * target gives rank -1 / score NaN, such an excluded row excludes nothing; the other queries are unaffected.
+ * Integer counters only (integer atomics), fixed-order merge: bit-identical run to run, and for any split of the
+ * queries over calls. table_rows, num_queries <= 2^30, dim <= 2^20. num_queries == 0 is a no-op.             */
+size_t mpqe_rank_workspace_bytes(int64_t num_queries, int64_t table_rows, int64_t dim, int k);
+int mpqe_rank_entities(const float *q /*[Q, dim]*/, int64_t num_queries, const float *table /*[table_rows, dim], raw rows*/,
+                       int64_t table_rows, int64_t dim, float eps, const int64_t *target_rows /*[Q] or NULL*/,
+                       const int64_t *excl_offsets, const int64_t *excl_rows, int64_t num_excluded, int k /*0: no top-k*/,
+                       int64_t *topk_rows, float *topk_scores, int64_t *rank, float *target_scores, void *workspace,
+                       size_t workspace_bytes, int32_t *err, void *stream);
+
 /* ---- fused training step -------------------------------------------------------------------
  * Forward + backward of RGCNEncoderDecoder.margin_loss (reference model.py:464-494) for ALL the
  * formula batches of one training step (reference train_helpers.py:76-120 draws 11 after

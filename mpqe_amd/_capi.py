@@ -104,6 +104,8 @@ PROTOTYPES = {
     'mpqe_cosine_bwd': (I, [P, P, P, P, L, L, F, P, P, P]),
     'mpqe_hinge_fwd': (I, [P, P, L, F, P, P]),
     'mpqe_hinge_bwd': (I, [P, P, L, F, P, P, P, P]),
+    'mpqe_rank_workspace_bytes': (Z, [L, L, L, I]),
+    'mpqe_rank_entities': (I, [P, L, P, L, L, F, P, P, P, L, I, P, P, P, P, P, Z, P, P]),
     'mpqe_debug_chain_stamps': (None, [P, Z]),
     'mpqe_debug_tail_stamps': (None, [P, Z]),
     'mpqe_debug_option': (None, [c_char_p, I, I]),

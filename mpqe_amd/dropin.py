@@ -705,8 +705,9 @@ class DropIn(object):
 
     # ------------------------------------------------------------------------------------------- forward (evaluation)
     def forward(self, formula, queries, target_nodes, anchor_ids=None, var_ids=None, q_graphs=None, neg_nodes=None,
-                neg_lengths=None):
-        """reference model.py:400-462 without autograd: scores [B] or [B + sum(neg_lengths)]."""
+                neg_lengths=None, query_out=None):
+        """reference model.py:400-462 without autograd: scores [B] or [B + sum(neg_lengths)]. `query_out` ([B, D] fp32 on the
+        device; chain form only): the call also leaves the query embeddings there."""
         m = self.model
         B = len(queries)
         r = self._one.get((0, formula, B)) or self._one_rec(formula, B)
@@ -739,10 +740,10 @@ class DropIn(object):
         scores = torch.empty(2 * B, dtype=torch.float32, device=self.device)
         loss = torch.empty(2, dtype=torch.float32, device=self.device)
         extra = q = None
-        if ragged:
+        if ragged or query_out is not None:
             if not self.step.uses_chain(r.ps):
                 raise NotImplementedError('ragged negatives on the fused forward need the chain form')
-            q = torch.empty(B, m.emb_dim, dtype=torch.float32, device=self.device)
+            q = query_out if query_out is not None else torch.empty(B, m.emb_dim, dtype=torch.float32, device=self.device)
             extra = _capi.StepExtra()
             extra.query_out = q.data_ptr()
         self.step.margin = 1.0
@@ -770,3 +771,18 @@ class DropIn(object):
         if m.validate:
             ops.raise_on_flags(self.step.err)
         return out
+
+    def query_embeddings(self, formula, queries, anchor_ids=None, var_ids=None, q_graphs=None):
+        """Query embeddings [B, D] of the fused forward (mpqe_step_extra_t.query_out), or None where the step would not run
+        its chain form (the caller encodes on the module path then). The step scores a target as it goes: any entity of the
+        target mode serves. Cost beside model.encode: ONE library call (the chain launch; B target-row gathers and B cosines
+        of surplus work, a few KB) instead of encode's assemble + one launch per layer + readout, which is why the fused
+        forward is preferred; the host side is forward()'s own (the ids of B queries written into the arena)."""
+        B = len(queries)
+        r = self._one.get((0, formula, B)) or self._one_rec(formula, B)
+        if not self.step.uses_chain(r.ps):
+            return None
+        q = torch.empty(B, self.model.emb_dim, dtype=torch.float32, device=self.device)
+        some = self.model.graph.full_lists[formula.target_mode][0]
+        self.forward(formula, queries, [some] * B, anchor_ids, var_ids, q_graphs, query_out=q)
+        return q

@@ -94,3 +94,34 @@ def eval_perc_queries(test_queries, enc_dec, batch_size=128, hard_negatives=Fals
             scores = enc_dec.forward(formula, batch_queries, targets, neg_nodes=negatives, neg_lengths=lengths)
             perc_scores.extend(_get_perc_scores(scores.detach().cpu().tolist(), lengths))
     return np.mean(perc_scores)
+
+
+def eval_rank_queries(test_queries, enc_dec, batch_size=128, ks=(1, 3, 10), known_answers=None):
+    """Link-prediction metrics over ALL entities of each query's target mode (no counterpart in the reference, whose
+    evaluation ranks the target among the negatives stored with the query): the rank of query.target_node from
+    `enc_dec.rank_targets`, filtered by `known_answers[query]` (every entity known to answer the query; the target is
+    never filtered out) when given -- the standard filtered setting -- raw otherwise.
+    -> {'mrr', 'hits@k' for k in ks, 'num_queries', 'per_formula': {formula: {'mrr', 'hits@k', 'num_queries'}}}."""
+    def summary(ranks):
+        r = np.asarray(ranks, dtype=np.float64)
+        out = {'mrr': float(np.mean(1.0 / r)) if r.size else float('nan')}
+        for k in ks:
+            out['hits@%d' % k] = float(np.mean(r <= k)) if r.size else float('nan')
+        out['num_queries'] = int(r.size)
+        return out
+
+    all_ranks, per_formula = [], {}
+    for formula in test_queries:
+        formula_queries = test_queries[formula]
+        formula_ranks = []
+        for lo, hi in _batches(formula_queries, batch_size):
+            batch_queries = formula_queries[lo:hi]
+            exclude = None if known_answers is None else [list(known_answers[q]) for q in batch_queries]
+            targets = [q.target_node for q in batch_queries]
+            ranks = enc_dec.rank_targets(formula, batch_queries, targets, exclude=exclude)
+            formula_ranks.extend(int(r) for r in ranks.detach().cpu().tolist())
+        per_formula[formula] = summary(formula_ranks)
+        all_ranks.extend(formula_ranks)
+    out = summary(all_ranks)
+    out['per_formula'] = per_formula
+    return out

@@ -5,6 +5,7 @@ and state_dict keys -- every float computed by the gfx950 kernels behind include
 import math
 import random
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -251,6 +252,8 @@ class RGCNEncoderDecoder(nn.Module):
         state['_dropin_state'] = None
         state['_dropin_checked'] = False
         state['_err'] = None
+        state['_row_ids'] = None        # (the row -> id maps answer() caches on the device)
+        state['_maps_np'] = None
         return state
 
     def __setstate__(self, state):
@@ -262,6 +265,8 @@ class RGCNEncoderDecoder(nn.Module):
         # (.to() / .cuda() / .float(): the parameters move -- the fused step's addresses are taken again at the next call)
         out = super(RGCNEncoderDecoder, self)._apply(fn, *args, **kwargs)
         self.__dict__['_dropin_checked'] = False
+        self.__dict__['_row_ids'] = None
+        self.__dict__['_maps_np'] = None
         return out
 
     def dropin(self):
@@ -311,6 +316,127 @@ class RGCNEncoderDecoder(nn.Module):
         scores = self.score(formula, out, target_nodes, neg_nodes, neg_lengths)
         self._check()
         return scores
+
+    # ------------------------------------------------------------------ answering a query (no counterpart in the reference)
+    def _mode_rows(self, mode, device):
+        """(row -> global id [n] int64 on the device, rows below n that are no entity, the map on the host) of one mode, from
+        graph.full_lists[mode] through enc.node_maps; built once per mode. n = 1 + the last row that is an entity: the
+        tables carry a spare row at the end (data_utils.make_feature_modules), which is never ranked."""
+        cache = self.__dict__.get('_row_ids')
+        if cache is None:
+            cache = self.__dict__['_row_ids'] = {}
+        hit = cache.get(mode)
+        if hit is not None and hit[0].device == device:
+            return hit
+        ids = np.asarray(list(self.graph.full_lists[mode]), dtype=np.int64)
+        maps = self._maps_host()
+        if ids.size == 0 or ids.min() < 0 or ids.max() >= maps.shape[0]:
+            raise IndexError('mpqe_amd: full_lists[%r] is empty or holds ids outside node_maps' % (mode,))
+        rows = maps[ids]
+        if rows.min() < 0 or rows.max() >= self.enc.table(mode).shape[0]:
+            raise IndexError('mpqe_amd: full_lists[%r] holds ids that are not of this mode' % (mode,))
+        row_ids = np.full(int(rows.max()) + 1, -1, dtype=np.int64)
+        row_ids[rows] = ids
+        hit = (torch.from_numpy(row_ids).to(device), np.nonzero(row_ids < 0)[0].astype(np.int64), row_ids)
+        cache[mode] = hit
+        return hit
+
+    def _maps_host(self):
+        # (ONE host copy of node_maps, shared by the row maps of every mode and by the id translation of every call)
+        m = self.__dict__.get('_maps_np')
+        if m is None:
+            m = self.__dict__['_maps_np'] = self.enc.node_maps.detach().cpu().numpy()
+        return m
+
+    def _query_embeddings(self, formula, queries, anchor_ids, var_ids, q_graphs):
+        d = self.dropin()
+        if d is not None and self._fused_covers(d, formula, len(queries)):
+            q = d.query_embeddings(formula, queries, anchor_ids, var_ids, q_graphs)
+            if q is not None:
+                return q
+        return self.encode(formula, queries, anchor_ids, var_ids, q_graphs)
+
+    def _rank_all(self, formula, queries, target_nodes, exclude, k, anchor_ids, var_ids, q_graphs):
+        enc = self.enc
+        if not (hasattr(enc, 'table') and getattr(enc, 'node_maps', None) is not None):
+            raise NotImplementedError('answering a query needs the entity tables (DirectEncoder with node_maps)')
+        device = self._device()
+        B = len(queries)
+        mode = formula.target_mode
+        row_ids, holes, row_ids_host = self._mode_rows(mode, device)
+        n = row_ids.shape[0]
+        err = self._error_word(device)
+        maps_host = self._maps_host()
+
+        def rows_of(ids):
+            # an id of another mode (node_maps gives it a row of ITS table), of no mode or outside node_maps becomes row n:
+            # outside the ranked rows, so the kernel flags it and _check raises
+            ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+            inside = (ids >= 0) & (ids < maps_host.shape[0])
+            cand = np.where(inside, maps_host[np.where(inside, ids, 0)], -1)
+            ok = (cand >= 0) & (cand < n)
+            ok &= row_ids_host[np.where(ok, cand, 0)] == ids
+            return np.where(ok, cand, n)
+
+        target_rows = None
+        if target_nodes is not None:
+            t = target_nodes.detach().cpu().numpy() if torch.is_tensor(target_nodes) else target_nodes
+            target_rows = torch.from_numpy(rows_of(t)).to(device)
+            if target_rows.shape[0] != B:
+                raise ValueError('one target per query')
+        csr = None
+        if exclude is not None:
+            if len(exclude) != B:
+                raise ValueError('exclude must hold one id list per query')
+            # one translation and one sort for the whole batch: keys (query, row), unique, then the segment bounds
+            lens = np.fromiter((len(e) for e in exclude), dtype=np.int64, count=B)
+            flat = np.fromiter((x for e in exclude for x in e), dtype=np.int64, count=int(lens.sum()))
+            rows = np.concatenate([rows_of(flat), np.tile(holes, B)])
+            owner = np.concatenate([np.repeat(np.arange(B, dtype=np.int64), lens),
+                                    np.repeat(np.arange(B, dtype=np.int64), holes.size)])
+            keys = np.unique(owner * (n + 1) + rows)
+            off = np.searchsorted(keys, np.arange(B + 1, dtype=np.int64) * (n + 1)).astype(np.int64)
+            csr = (torch.from_numpy(off), torch.from_numpy(keys % (n + 1)))
+        elif holes.size:
+            # rows of the table that are no entity: the same list for every query, kept on the device for the LAST batch size
+            # seen per mode (one entry per mode: an evaluation loop's ragged last batch rebuilds it once, nothing accumulates)
+            cache = self.__dict__['_row_ids']
+            hit = cache.get(('holes', mode))
+            if hit is None or hit[0] != B or hit[1][0].device != device:
+                off = torch.arange(B + 1, dtype=torch.int64) * holes.size
+                hit = cache[('holes', mode)] = (B, (off.to(device), torch.from_numpy(np.tile(holes, B)).to(device)))
+            csr = hit[1]
+        q = self._query_embeddings(formula, queries, anchor_ids, var_ids, q_graphs)
+        table = enc.table(mode).detach()[:n]
+        topr, tops, rank, _ = ops.rank_entities(q, table, target_rows, csr, k, err=err)
+        self._check()
+        ids = None
+        if topr is not None:
+            ids = torch.where(topr >= 0, row_ids[topr.clamp(min=0)], topr)
+        return ids, tops, rank
+
+    def answer(self, formula, queries, k=10, exclude=None, anchor_ids=None, var_ids=None, q_graphs=None):
+        """The k entities of formula.target_mode the model proposes for each query, best first:
+        (ids [B, k] int64 global entity ids, scores [B, k] float32), -1 / -inf past the last eligible entity. The score is
+        the one forward() gives a candidate. `exclude`: one list of entity ids per query that must not be returned.
+        Every entity of the mode is scored (mpqe_rank_entities); k <= ops.RANK_MAX_K."""
+        if k < 1:
+            raise ValueError('answer: k must be at least 1')
+        with torch.no_grad():
+            ids, scores, _ = self._rank_all(formula, queries, None, exclude, k, anchor_ids, var_ids, q_graphs)
+        return ids, scores
+
+    def rank_targets(self, formula, queries, target_nodes=None, exclude=None, anchor_ids=None, var_ids=None,
+                     q_graphs=None):
+        """ranks [B] int64: 1 + the number of entities of formula.target_mode, other than the target and those in
+        `exclude`, that the model places before each query's target (default: query.target_node); ties go to the entity
+        with the smaller table row. The target is never excluded, listed or not (the filtered setting passes every known
+        answer)."""
+        if target_nodes is None:
+            target_nodes = [query.target_node for query in queries]
+        with torch.no_grad():
+            _, _, rank = self._rank_all(formula, queries, target_nodes, exclude, 0, anchor_ids, var_ids, q_graphs)
+        return rank
 
     def sample_negatives(self, formula, queries, hard_negatives=False):
         """reference: model.py:466-476 (same python `random` stream, so the same draws)."""

@@ -553,6 +553,77 @@ def cosine(q, t, q_row=None, eps=1e-8):
     return _Cosine.apply(q, t, q_row, float(eps))
 
 
+RANK_MAX_K = 128          # csrc/rank.hip: the per-query candidate lists live in LDS
+
+
+def exclusion_csr(exclude, n_queries):
+    """One list of table rows per query -> (offsets [Q+1], rows) int64 numpy, each list sorted and without repeats."""
+    if len(exclude) != n_queries:
+        raise ValueError('rank_entities: exclude must hold one list per query (%d for %d)' % (len(exclude), n_queries))
+    lists = [np.unique(np.asarray(e, dtype=np.int64).reshape(-1)) for e in exclude]
+    off = np.zeros(n_queries + 1, dtype=np.int64)
+    if lists:
+        off[1:] = np.cumsum([l.shape[0] for l in lists])
+    rows = np.concatenate(lists) if lists else np.zeros(0, dtype=np.int64)
+    return off, rows.astype(np.int64, copy=False)
+
+
+def rank_entities(q, table, target_rows=None, exclude=None, k=0, eps=1e-8, err=None):
+    """Every row of `table` ([N, D], raw rows) ranked against the query embeddings q [Q, D] by the model's score
+    cos(q[i], table[r] / |table[r]|): mpqe_rank_entities (include/mpqe_amd.h). Inference only: nothing here is
+    differentiated. Everything is in table rows.
+      target_rows  [Q] int64 or None
+      exclude      None, one list of rows per query, or (offsets [Q+1], rows) int64 tensors (lists sorted ascending)
+    -> (topk_rows [Q, k] int64, topk_scores [Q, k], rank [Q] int64 or None, target_scores [Q] or None); the first two
+    are None for k = 0. Rows outside the table OR MPQE_FLAG_BAD_INDEX into `err` (ops.raise_on_flags)."""
+    k = int(k)
+    if k < 0 or k > RANK_MAX_K:
+        raise ValueError('rank_entities: k must be in [0, %d], got %d' % (RANK_MAX_K, k))
+    if not torch.is_tensor(q) or not torch.is_tensor(table) or q.dim() != 2 or table.dim() != 2:
+        raise ValueError('rank_entities: q and table must be 2-d tensors')
+    if q.shape[1] != table.shape[1] or table.shape[0] < 1:
+        raise ValueError('rank_entities: shapes %s vs %s' % (tuple(q.shape), tuple(table.shape)))
+    Q, D = q.shape
+    N = table.shape[0]
+    if target_rows is not None and (not torch.is_tensor(target_rows) or tuple(target_rows.shape) != (Q,)):
+        raise ValueError('rank_entities: target_rows must be a tensor of one row per query')
+    if k == 0 and target_rows is None:
+        raise ValueError('rank_entities: nothing to compute (k = 0 and no target_rows)')
+    off = rows = None
+    if exclude is not None:
+        if isinstance(exclude, tuple) and len(exclude) == 2 and torch.is_tensor(exclude[0]):
+            off, rows = exclude
+            if tuple(off.shape) != (Q + 1,) or rows.dim() != 1:
+                raise ValueError('rank_entities: exclude offsets must be [Q + 1], rows 1-d')
+        else:
+            off, rows = (torch.from_numpy(a) for a in exclusion_csr(exclude, Q))
+    q, table = _f(q.detach(), 'query embeddings'), _f(table.detach(), 'embedding table')
+    dev = q.device
+    if target_rows is not None:
+        target_rows = _i(target_rows, 'target_rows')
+    E = 0
+    if off is not None:
+        E = int(rows.shape[0])
+        off, rows = _i(off.to(dev), 'exclude offsets'), _i(rows.to(dev), 'exclude rows')
+        if E == 0:
+            off = rows = None
+    topr = torch.empty((Q, k), dtype=torch.int64, device=dev) if k else None
+    tops = torch.empty((Q, k), dtype=torch.float32, device=dev) if k else None
+    rank = torch.empty((Q,), dtype=torch.int64, device=dev) if target_rows is not None else None
+    tsc = torch.empty((Q,), dtype=torch.float32, device=dev) if target_rows is not None else None
+    if Q == 0:
+        return topr, tops, rank, tsc
+    with torch.cuda.device(dev):
+        need = lib().mpqe_rank_workspace_bytes(Q, N, D, k)
+        if need == 0:
+            raise ValueError('rank_entities: shape outside what the kernel covers')
+        ws = _ws(need, dev)
+        _ck(lib().mpqe_rank_entities(_p(q), Q, _p(table), N, D, float(eps), _p(target_rows), _p(off), _p(rows), E, k,
+                                     _p(topr), _p(tops), _p(rank), _p(tsc), _p(ws), need, _p(err), _stream()),
+            'mpqe_rank_entities')
+    return topr, tops, rank, tsc
+
+
 class _Hinge(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pos, neg, margin):
