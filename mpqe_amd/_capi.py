@@ -182,6 +182,12 @@ class MpqeError(RuntimeError):
     pass
 
 
+def _align256(ptr):
+    """The first 256-byte boundary at or after an address: the library wants its workspaces, descriptor tables and plans
+    aligned so, and the buffers behind them are allocated 256 bytes larger."""
+    return (ptr + 255) // 256 * 256
+
+
 def check(cdll, status, what):
     if status != 0:
         msg = cdll.mpqe_status_string(status)

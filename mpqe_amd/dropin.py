@@ -38,7 +38,8 @@ import torch
 
 from . import _capi, _lib, ops
 from .data_utils import RGCNQueryDataset
-from .fused import FusedTrainStep, _TEMPLATES
+from ._capi import _align256
+from .fused import FusedTrainStep
 
 MAX_CALLS = _capi.STEP_MAX_BATCHES
 MAX_LANES = 7                              # side streams of the forward-only calls (channel 0 is the caller's stream)
@@ -280,7 +281,7 @@ class DropIn(object):
             if lane.ws is not None:
                 lane.stream.synchronize()          # (nothing in flight in the buffer that goes)
             lane.ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
-        return (lane.ws.data_ptr() + 255) // 256 * 256
+        return _align256(lane.ws.data_ptr())
 
     def _fork(self, lane, cur):
         """The lane's next kernel runs behind everything the caller's stream holds now."""
@@ -322,7 +323,7 @@ class DropIn(object):
     def _one_rec(self, formula, B, ch=0):
         r = self._one.get((ch, formula, B))
         if r is None:
-            A = _TEMPLATES[formula.query_type][0]
+            A = ops.template_info(formula.query_type).num_anchors
             if A != len(formula.anchor_modes):
                 raise ValueError('formula %s has %d anchor modes, template expects %d'
                                  % (formula, len(formula.anchor_modes), A))
@@ -335,7 +336,7 @@ class DropIn(object):
         """One library call on the current stream (lane: on the lane's, the current stream waiting for it): the argument
         block's changing fields, then csrc/host/pyhost.c: step_call."""
         step, ps, c = self.step, r.ps, r.call
-        step.P.flags = step.flags | ps.step_flags | (_capi.STEP_ZERO_GRADS if (backward and zero_grad) else 0)
+        step._call_flags(ps, backward and zero_grad)
         c.params, c.grads = ctypes.addressof(step.P), ctypes.addressof(step.G)      # (refresh() makes new structs)
         c.anchor_ids, c.targets, c.negs = a_ptr, t_ptr, n_ptr
         c.margin = step.margin
@@ -568,7 +569,7 @@ class DropIn(object):
             csr = None
         oa, og = ar.na, ar.ng
         if csr is not None:
-            step.P.flags = step.flags | r.ps.step_flags
+            step._call_flags(r.ps)
             self._calls = seq = (self._calls + 1) & 0xffffffff
             if len(csr) == 7:          # (one list for every query)
                 lens_p, len_all, base_p = 0, csr[6], 0

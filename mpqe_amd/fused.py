@@ -1,7 +1,7 @@
 """Whole-step execution of the encoder: every formula batch of one training step (the
 reference's run_train inner loop, train_helpers.py:76-120: `loss = margin_loss(1-chain) +
 path_weight * ... + inter_weight * ...; loss.backward()`) goes through ONE C-ABI call,
-mpqe_step_forward_backward (~15 kernel launches), instead of one launch per op per batch.
+mpqe_step_forward_backward (two or three kernel launches in the chain form), instead of one launch per op per batch.
 
     step = FusedTrainStep(model)                 # model: mpqe_amd.model.RGCNEncoderDecoder
     packed = step.pack(batches)                  # ids -> HBM, descriptors -> host structs
@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _capi, ops
+from ._capi import _align256
 from .data_utils import RGCNQueryDataset
 
 
@@ -65,16 +66,68 @@ def _template_info(query_type):
 
 def _batch_work(query_type, passes):
     """Relative MFMA work of one batch per graph: passes * (edges + nodes) K-blocks."""
-    e_n = {'1-chain': 3, '2-chain': 5, '3-chain': 7, '2-inter': 5, '3-inter': 7, '3-inter_chain': 7,
-           '3-chain_inter': 7}[query_type]
-    return passes * e_n
+    info = _template_info(query_type)
+    return passes * (info.num_edges + info.num_nodes)
 
 
-_TEMPLATES = {   # query type -> (num anchors, num nodes, [(src, dst)]) : reference data_utils.py:325-362
-    '1-chain': (1, 2, [(0, 1)]), '2-chain': (1, 3, [(0, 2), (2, 1)]), '3-chain': (1, 4, [(0, 3), (3, 2), (2, 1)]),
-    '2-inter': (2, 3, [(0, 2), (1, 2)]), '3-inter': (3, 4, [(0, 3), (1, 3), (2, 3)]),
-    '3-inter_chain': (2, 4, [(0, 2), (1, 3), (3, 2)]), '3-chain_inter': (2, 4, [(0, 3), (1, 3), (3, 2)])}
-CHAIN_MAX_GRAPHS = 1 << 20          # csrc/step.hip
+def _as_numpy(x):
+    return x if isinstance(x, np.ndarray) else x.cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+
+
+# The library's rule for the launch form of a step (csrc/step.hip: want_chain) and for the merged tail, mirrored
+CHAIN_DIMS = (64, 128, 256)             # want_chain: P->dim == 64 || 128 || 256 (the chain kernel's instantiations)
+CHAIN_MAX_GRAPHS = 1 << 20              # csrc/step.hip: CHAIN_MAX_GRAPHS
+CHAIN_MAX_PASSES = 5                    # csrc/step_chain.h: num_passes <= CH_MASK_LEVELS + 1
+CHAIN_MAX_PASSES_LEARNED = 3            # csrc/step_chain.h: num_passes + 1 <= CH_MASK_LEVELS (the readout's two levels)
+MERGE_MAX_BLOCKS = 256 + 256 // 8       # csrc/step_drive.h: STEP_CUS + STEP_CUS / 8 chain workgroups
+
+
+def chain_form(flags, dim, learned, graphs, max_passes):
+    """True when the library runs a step in the chain form (csrc/step.hip: want_chain) -- the ONE statement of that rule
+    in Python. flags: the step's MPQE_STEP_* switches; learned: a learned readout that rides the chain (the constructor
+    sends the others to the level form through MPQE_STEP_NO_CHAIN); graphs: query graphs of the step; max_passes: of
+    its deepest batch. want_chain's checks of pointers and alignment are not mirrored (torch's allocations pass them),
+    nor is the planner's own refusal of a batch with more than CH_MAX_CV forward node updates (csrc/step_plan.h)."""
+    return (not (flags & _capi.STEP_NO_CHAIN) and dim in CHAIN_DIMS and graphs <= CHAIN_MAX_GRAPHS and
+            max_passes <= (CHAIN_MAX_PASSES_LEARNED if learned else CHAIN_MAX_PASSES))
+
+
+def split_lanes(work, passes, sizes, num_lanes, chain):
+    """Lane assignment of a step's batches: (order, lane_begin) -- order[i] = caller's index of library batch i, lane l owns
+    library batches lane_begin[l] .. lane_begin[l + 1]. work / passes / sizes: per batch, MFMA work per graph
+    (_batch_work), message-passing passes, query graphs. The chain form is one launch sequence on the caller's stream
+    whatever the split (the library ignores it): one lane, batch order kept, `work` not read. Otherwise: deepest chains
+    first, each batch to the lane with the least work so far; the library wants every lane to own a contiguous range
+    of batches, so the batches are re-ordered."""
+    nb = len(passes)
+    if chain:
+        return list(range(nb)), [0, nb]
+    nl = min(num_lanes, nb)
+    load = [0.0] * nl
+    members = [[] for _ in range(nl)]
+    for i in sorted(range(nb), key=lambda i: (-passes[i], -work[i])):
+        l = min(range(nl), key=lambda l: load[l])
+        members[l].append(i)
+        load[l] += work[i] * sizes[i]
+    members = [sorted(mm) for mm in members if mm]
+    order = [i for mm in members for i in mm]
+    lane_begin = [0]
+    for mm in members:
+        lane_begin.append(lane_begin[-1] + len(mm))
+    return order, lane_begin
+
+
+def touch_mode_for(configured_mode, chain, n_ids, external, in_retry_set):
+    """Where the touch plan of one step is built: 'step' (inside the step: nothing id-dependent left for pack), 'pack', or
+    None (no plan). configured_mode: the step object's touch_mode; n_ids: looked-up ids of the step; external: the ids
+    are named per run (ids='external'); in_retry_set: the in-step plan of this descriptor set failed once."""
+    mode = configured_mode
+    if mode == 'step' and (not chain or n_ids > _capi.TSORT_MAX_ENTRIES):
+        # (the level form has no use for a plan: a step whose ids are named per run carries none)
+        mode = None if (external and not chain) else 'pack'
+    if mode == 'step' and in_retry_set:
+        mode = 'pack'
+    return mode
 
 
 def live_units(query_type, passes, readout, prune=True, uniform=False):
@@ -85,7 +138,9 @@ def live_units(query_type, passes, readout, prune=True, uniform=False):
     (SURVEY.md 8d). uniform: states no anchor has reached yet are one vector per batch (csrc/step.hip: UOp) and
     their products are matrix-vector work done once per batch, not counted here. Forward, backward-x and the
     weight gradient each execute exactly these units."""
-    A, N, edges = _TEMPLATES[query_type]
+    info = _template_info(query_type)
+    A, N = info.num_anchors, info.num_nodes
+    edges = [(info.src[e], info.dst[e]) for e in range(info.num_edges)]
     full = (1 << N) - 1
     live = [0] * (passes + 1)
     live[passes] = (1 << A) if (prune and readout == 'mp') else full
@@ -124,7 +179,8 @@ class CapturedStep(object):
 
 class FusedTrainStep(object):
     """lanes: number of HIP streams a step is spread over (1 = everything on the current stream).
-    A step is a chain of ~13 dependent, very short launches; with lanes > 1 the batches are split
+    A chain-form step is two or three launches on the caller's stream whatever the split. A level-form step is a
+    chain of ~13 dependent, very short launches; with lanes > 1 the batches are split
     into groups whose chains run concurrently on their own streams and meet before the weight
     gradients (include/mpqe_amd.h, mpqe_step_lanes_t). The split balances MFMA work and keeps
     batches of equal depth together (longest chains first)."""
@@ -154,7 +210,7 @@ class FusedTrainStep(object):
         if self.learned:
             if model.emb_dim % 4:
                 raise NotImplementedError('fused step with a learned readout: embedding dimension must be a multiple of 4')
-            on_chain = (chain and model.emb_dim in (64, 128, 256) and model.num_layers <= 3 and not eight_waves and
+            on_chain = (chain and model.emb_dim in CHAIN_DIMS and model.num_layers <= 3 and not eight_waves and
                         (model.readout_str != 'concat' or not model.adaptive))
             if on_chain:
                 lanes = 1
@@ -207,6 +263,11 @@ class FusedTrainStep(object):
         self.err = ops.new_error_word(self.device)
         self._ws = None
         self._desc_cache, self._size_cache, self._pool = {}, {}, {}
+        self._prof, self._prof_t0 = None, 0.0          # (tools/pack_profile.py: seconds per section of pack(), or None)
+        # build workspace of the touch plan with the stream that used it last (build_touch); pinned staging ring of
+        # host_ids='copy' with the event of each buffer's last copy (_staging)
+        self._touch_ws = self._touch_ws_stream = self._touch_ws_stream_obj = None
+        self._stage_ring, self._stage_events, self._stage_next = [None] * 4, [None] * 4, -1
         # descriptor sets whose in-step touch plan failed once (run(checked=True)): their plans are built by pack() from then on
         self._pack_touch_sets = set()
         self.param_epoch = 0               # bumped by writers of the parameters that bypass autograd's version counters (FlatOptimizer.step)
@@ -278,7 +339,7 @@ class FusedTrainStep(object):
         """The ids of a step in the layout the library reads: [anchors of batch 0 (slot-major: [A, B]) | ... | targets of
         all batches | negatives of all batches], as one int64 numpy array (`out`: write there). batches: dicts with
         formula, anchor_ids [B, A], targets [B], negs [B]."""
-        acols = [_TEMPLATES[b['formula'].query_type][0] for b in batches]
+        acols = [_template_info(b['formula'].query_type).num_anchors for b in batches]
         sizes = [len(b['targets']) for b in batches]
         na, ngr = sum(B * A for B, A in zip(sizes, acols)), sum(sizes)
         snp = np.empty(na + 2 * ngr, dtype=np.int64) if out is None else out
@@ -287,13 +348,7 @@ class FusedTrainStep(object):
         oa = 0
         tl, nl_ = [], []
         for b, B, A in zip(batches, sizes, acols):
-            a, t, n = b['anchor_ids'], b['targets'], b['negs']
-            if not isinstance(a, np.ndarray):
-                a = a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
-            if not isinstance(t, np.ndarray):
-                t = t.cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
-            if not isinstance(n, np.ndarray):
-                n = n.cpu().numpy() if torch.is_tensor(n) else np.asarray(n)
+            a, t, n = _as_numpy(b['anchor_ids']), _as_numpy(b['targets']), _as_numpy(b['negs'])
             if a.shape != (B, A):
                 raise ValueError('anchor_ids must be [B, %d] for %s' % (A, b['formula'].query_type))
             if t.shape != (B,) or n.shape != (B,):
@@ -317,123 +372,133 @@ class FusedTrainStep(object):
         their size (`batch_size`, or `targets` for its length). A CUDA tensor (a loader that stages ids itself, ids drawn
         on the device): pack() does no device work at all; the step reads the tensor when it runs, keep its contents
         until then. A numpy array / CPU tensor (a collate function that writes this layout directly): one copy into
-        pinned staging + one host-to-device copy, in stream order."""
-        m = self.model
+        pinned staging + one host-to-device copy, in stream order. 'external': descriptors and buffers only, every
+        run names the three id arrays itself (run(id_ptrs=...))."""
         nb = len(batches)
         if nb == 0 or nb > _capi.STEP_MAX_BATCHES:
             raise ValueError('a step holds 1..%d batches' % _capi.STEP_MAX_BATCHES)
-        # lane assignment: deepest chains first, each batch to the lane with the least work so far;
-        # the library wants every lane to own a contiguous range of batches, so the batches are
-        # re-ordered (packed.order[i] = caller's index of library batch i)
-        passes_of = []
-        for b in batches:
-            qt = b['formula'].query_type
-            passes_of.append(RGCNQueryDataset.query_diameters[qt] if m.adaptive else m.num_layers)
-        if self.learned and m.readout_str == 'concat' and any(p != m.num_layers for p in passes_of):
+        passes = self._passes_of(batches)
+        sizes = [_bsize(b) for b in batches]
+        chain = chain_form(self.flags, self.model.emb_dim, self.learned, sum(sizes), max(passes))
+        work = None if chain else [_batch_work(b['formula'].query_type, p) for b, p in zip(batches, passes)]
+        ps = PackedStep()
+        ps.nb, ps.captured = nb, False
+        ps.order, ps.lane_begin = split_lanes(work, passes, sizes, self.num_lanes, chain)
+        batches = [batches[i] for i in ps.order]
+        prof = self._prof
+        if prof is not None:
+            self._tick()
+        na = self._descriptors(ps, batches, passes)
+        if prof is not None:
+            self._tick('descriptors')
+        ps.lanes = self._lanes_struct(ps.lane_begin)
+        # where the touch plan is built; then everything that is a function of the descriptors alone -- the sizes, the
+        # buffer set -- under one key
+        dkey = (bytes(ps.batches), tuple(ps.lane_begin))
+        ps.touch_mode = touch_mode_for(self.touch_mode, chain, na + 2 * ps.num_graphs, isinstance(ids, str),
+                                       bool(self._pack_touch_sets) and dkey in self._pack_touch_sets)
+        ps.step_flags = _capi.STEP_BUILD_TOUCH if ps.touch_mode == 'step' else 0
+        skey = dkey + (ps.touch_mode,)
+        self._sizes(ps, skey)
+        self._take_buffers(ps, skey)
+        self._place_ids(ps, batches, ids, na)
+        self._touch_plan(ps)
+        return ps
+
+    def _tick(self, section=None):
+        """(tools/pack_profile.py) The time since the last tick goes to `section` of _prof."""
+        t1 = time.perf_counter()
+        if section is not None:
+            self._prof[section] = self._prof.get(section, 0.0) + t1 - self._prof_t0
+        self._prof_t0 = t1
+
+    def _passes_of(self, batches):
+        """Message-passing passes of every batch: the formula's diameter (adaptive) or the number of layers."""
+        m = self.model
+        passes = [RGCNQueryDataset.query_diameters[b['formula'].query_type] if m.adaptive else m.num_layers for b in batches]
+        if self.learned and m.readout_str == 'concat' and any(p != m.num_layers for p in passes):
             raise ValueError('concat readout: every batch must run num_layers passes (adaptive=False)')
-        nl = min(self.num_lanes, nb)
-        graphs = sum(_bsize(b) for b in batches)
-        chain = (not (self.flags & _capi.STEP_NO_CHAIN) and m.emb_dim in (64, 128, 256)
-                 and graphs <= CHAIN_MAX_GRAPHS and max(passes_of) <= 5)
-        if chain:
-            # chain form: one launch sequence per step on the caller's stream whatever the split (the library ignores it;
-            # batch order is kept)
-            members = [list(range(nb))]
-        else:
-            load = [0.0] * nl
-            members = [[] for _ in range(nl)]
-            for i in sorted(range(nb), key=lambda i: (-passes_of[i], -_batch_work(batches[i]['formula'].query_type,
-                                                                                    passes_of[i]))):
-                l = min(range(nl), key=lambda l: load[l])
-                members[l].append(i)
-                load[l] += _batch_work(batches[i]['formula'].query_type, passes_of[i]) * _bsize(batches[i])
-        members = [sorted(mm) for mm in members if mm]
-        order = [i for mm in members for i in mm]
-        lane_begin = [0]
-        for mm in members:
-            lane_begin.append(lane_begin[-1] + len(mm))
-        batches = [batches[i] for i in order]
-        # descriptors: per (formula, passes) everything that does not depend on the ids is cached (a training run
-        # draws from a finite set of formulas); ids go straight into ONE pinned staging buffer (numpy views, no
-        # per-batch tensors) and to the device in ONE copy: [anchors (slot-major per batch) | targets | negatives]
-        prof = getattr(self, '_prof', None)       # (tools/pack_profile.py: seconds per section, or None)
-        t0 = time.perf_counter() if prof is not None else 0.0
-        SB = (_capi.StepBatch * nb)()
-        sizes, acols = [], []
+        return passes
+
+    def _descriptors(self, ps, batches, passes):
+        """The library's descriptor of every batch (ps.batches; batches: in library order, passes: in the caller's), their
+        sizes and the step's graph count. Per (formula, passes) everything that does not depend on the ids is cached (a
+        training run draws from a finite set of formulas). Returns the number of anchor ids of the step."""
+        order = ps.order
+        SB = (_capi.StepBatch * len(batches))()
+        sizes, na = [], 0
         for i, b in enumerate(batches):
             f = b['formula']
-            passes = passes_of[order[i]]
-            key = (f, passes)
+            key = (f, passes[order[i]])
             proto = self._desc_cache.get(key)
             if proto is None:
-                info = _template_info(f.query_type)
-                if m.adaptive and passes > len(m.layers):
-                    raise ValueError(f'RGCN is adaptive with {len(m.layers)}'
-                                     f' layers, but query requires {passes}.')
-                nodes, rels = f.get_nodes(), f.get_rels()
-                edge_type = [m.rel_ids[(rels[info.rel_label[e]][2], rels[info.rel_label[e]][1],
-                                        rels[info.rel_label[e]][0])] for e in range(info.num_edges)]
-                var_ids = [m.mode_ids[nodes[info.var_node[k]]] for k in range(info.num_vars)]
-                proto = (_capi.make_step_batch(f.query_type, passes, 1, edge_type, var_ids,
-                                               [m.mode_ids[x] for x in f.anchor_modes], m.mode_ids[f.target_mode], 1.0),
-                         info.num_anchors)
-                if len(self._desc_cache) > 65536:
-                    self._desc_cache.clear()
-                self._desc_cache[key] = proto
+                proto = self._desc_cache_add(key)
             B = _bsize(b)
             ctypes.memmove(ctypes.addressof(SB[i]), ctypes.addressof(proto[0]), ctypes.sizeof(_capi.StepBatch))
             SB[i].batch_size = B
             SB[i].weight = float(b.get('weight', 1.0))
             sizes.append(B)
-            acols.append(proto[1])
-        if prof is not None:
-            t1 = time.perf_counter(); prof['descriptors'] = prof.get('descriptors', 0.0) + t1 - t0; t0 = t1
-        na, ngr = sum(B * A for B, A in zip(sizes, acols)), sum(sizes)
-        ps = PackedStep()
-        ps.lanes = None
-        if len(members) > 1:
-            L = _capi.StepLanes()
-            L.num_lanes = len(members)
-            for i, v in enumerate(lane_begin):
-                L.batch_begin[i] = v
-            L.fork_event = self._fork.cuda_event
-            for l in range(1, len(members)):
-                L.aux_stream[l] = self._streams[l].cuda_stream
-                L.join_event[l] = self._joins[l].cuda_event
-            ps.lanes = ctypes.pointer(L)
-        # sizes: functions of the descriptors alone -- cached per descriptor set (one planning pass on a miss; the
-        # step's first run takes that plan over)
-        # where the touch plan is built: inside the step (nothing id-dependent left for pack), or here
-        mode = self.touch_mode
-        external = isinstance(ids, str)
-        if mode == 'step' and (not chain or na + 2 * ngr > _capi.TSORT_MAX_ENTRIES):
-            # (the level form has no use for a plan: a step whose ids are named per run carries none)
-            mode = None if (external and not chain) else 'pack'
-        if mode == 'step' and self._pack_touch_sets and (bytes(SB), tuple(lane_begin)) in self._pack_touch_sets:
-            mode = 'pack'
-        ps.touch_mode = mode
-        ps.step_flags = _capi.STEP_BUILD_TOUCH if mode == 'step' else 0
-        skey = (bytes(SB), tuple(lane_begin), mode)
+            na += B * proto[1]
+        ps.batches, ps.sizes, ps.num_graphs = SB, sizes, int(sum(sizes))
+        return na
+
+    def _desc_cache_add(self, key):
+        """A formula's descriptor at batch size 1 and weight 1, with its number of anchors: (StepBatch, A)."""
+        m, (f, passes) = self.model, key
+        info = _template_info(f.query_type)
+        if m.adaptive and passes > len(m.layers):
+            raise ValueError(f'RGCN is adaptive with {len(m.layers)}'
+                             f' layers, but query requires {passes}.')
+        nodes, rels = f.get_nodes(), f.get_rels()
+        edge_type = [m.rel_ids[(rels[info.rel_label[e]][2], rels[info.rel_label[e]][1],
+                                rels[info.rel_label[e]][0])] for e in range(info.num_edges)]
+        var_ids = [m.mode_ids[nodes[info.var_node[k]]] for k in range(info.num_vars)]
+        proto = (_capi.make_step_batch(f.query_type, passes, 1, edge_type, var_ids,
+                                       [m.mode_ids[x] for x in f.anchor_modes], m.mode_ids[f.target_mode], 1.0),
+                 info.num_anchors)
+        if len(self._desc_cache) > 65536:
+            self._desc_cache.clear()
+        self._desc_cache[key] = proto
+        return proto
+
+    def _lanes_struct(self, lane_begin):
+        """mpqe_step_lanes_t of a split into more than one lane (streams and events are the step object's), else None."""
+        nl = len(lane_begin) - 1
+        if nl <= 1:
+            return None
+        L = _capi.StepLanes()
+        L.num_lanes = nl
+        for i, v in enumerate(lane_begin):
+            L.batch_begin[i] = v
+        L.fork_event = self._fork.cuda_event
+        for l in range(1, nl):
+            L.aux_stream[l] = self._streams[l].cuda_stream
+            L.join_event[l] = self._joins[l].cuda_event
+        return ctypes.pointer(L)
+
+    def _sizes(self, ps, skey):
+        """Workspace, descriptor-table and touch-plan sizes: functions of the descriptors alone -- cached per descriptor
+        set (one planning pass on a miss; the step's first run takes that plan over)."""
         sz = self._size_cache.get(skey)
         if sz is None:
-            lib = ops.lib()
-            self.P.flags = self.flags | ps.step_flags         # (the launch plan, hence the sizes, depend on it)
-            sz = (lib.mpqe_step_workspace_bytes(ctypes.byref(self.P), SB, nb, ps.lanes),
-                  lib.mpqe_step_desc_bytes(ctypes.byref(self.P), SB, nb, ps.lanes),
-                  lib.mpqe_step_touch_bytes(ctypes.byref(self.P), SB, nb),
-                  lib.mpqe_step_touch_workspace_bytes(ctypes.byref(self.P), SB, nb),
+            lib, P, SB, nb = ops.lib(), ctypes.byref(self.P), ps.batches, ps.nb
+            self._call_flags(ps)                  # (the launch plan, hence the sizes, depend on them)
+            sz = (lib.mpqe_step_workspace_bytes(P, SB, nb, ps.lanes), lib.mpqe_step_desc_bytes(P, SB, nb, ps.lanes),
+                  lib.mpqe_step_touch_bytes(P, SB, nb), lib.mpqe_step_touch_workspace_bytes(P, SB, nb),
                   int(lib.mpqe_step_touch_entries(SB, nb)))
             if sz[0] == 0:
                 raise _capi.MpqeError('mpqe_step_workspace_bytes rejected the step descriptors')
             if len(self._size_cache) > 4096:
                 self._size_cache.clear()
             self._size_cache[skey] = sz
-        ps.ws_bytes, ps.desc_bytes = sz[0], sz[1]
-        # Buffers of this packed step (StepBuffers): from the free list of its descriptor set, or new. The descriptor table
-        # is a function of the set alone (not of the ids), so a buffer set whose packed step is gone serves the next step
-        # as it is -- table resident, hand-off epochs carried on (they only ever grow): a training loop that draws fresh
-        # ids for a recurring set of formulas uploads nothing. (One stream per FusedTrainStep, as for the workspace: a
-        # re-used buffer's previous step is ordered before the next one.)
+        ps.ws_bytes, ps.desc_bytes, ps.touch_sizes, ps.touch_entries = sz[0], sz[1], (sz[2], sz[3]), sz[4]
+
+    def _take_buffers(self, ps, skey):
+        """Buffers of this packed step (StepBuffers): from the free list of its descriptor set, or new. The descriptor table
+        is a function of the set alone (not of the ids), so a buffer set whose packed step is gone serves the next step
+        as it is -- table resident, hand-off epochs carried on (they only ever grow): a training loop that draws fresh
+        ids for a recurring set of formulas uploads nothing. (One stream per FusedTrainStep, as for the workspace: a
+        re-used buffer's previous step is ordered before the next one.)"""
         free = self._pool.get(skey)
         if free is None:
             if len(self._pool) > 1024:
@@ -449,85 +514,91 @@ class FusedTrainStep(object):
             bufs.desc = torch.empty(ps.desc_bytes + 256, dtype=torch.uint8, device=self.device)
         ps.bufs, ps.owner = bufs, self
         ps.desc = bufs.desc
-        ps.desc_ptr = (ps.desc.data_ptr() + 255) // 256 * 256
-        ps.batches, ps.nb, ps.sizes = SB, nb, sizes
-        ps.order, ps.lane_begin = order, lane_begin
-        ps.num_graphs = int(ngr)
-        ps.touch_entries = sz[4]
-        ps.touch_sizes = (sz[2], sz[3])
+        ps.desc_ptr = _align256(ps.desc.data_ptr())
         ps.touch, ps.touch_ptr = None, None
-        ps.captured = False
+
+    def _place_ids(self, ps, batches, ids, na):
+        """Where the kernels read the step's ids: nowhere yet (ids='external'), in the caller's device tensor, or in this
+        packed step's own buffer (ids from the host: _host_ids). na: anchor ids of the step."""
+        ngr = ps.num_graphs
         n_ids = na + 2 * ngr
         if isinstance(ids, str):
             if ids != 'external':
                 raise ValueError("ids: an id array, or 'external' (the ids' addresses are handed to run(id_ptrs=...))")
             # descriptors and buffers only: every run names the three id arrays itself (mpqe_amd/dropin.py: the calls of one
             # training step append their ids to pinned arenas the kernels read in place)
-            ps.ids_ref = dev = None
-        elif ids is not None and torch.is_tensor(ids) and ids.is_cuda:
+            ps.ids_ref = ps.anchor_ids = ps.targets = ps.negs = None
+            return
+        if ids is not None and torch.is_tensor(ids) and ids.is_cuda:
             if not (ids.dtype == torch.long and ids.is_contiguous() and ids.numel() == n_ids and ids.device == self.device):
                 raise ValueError('ids: a contiguous int64 tensor of %d ids (flatten_ids layout)' % n_ids)
             ps.ids_ref = dev = ids
         else:
-            # ids from the host. 'direct': into the PINNED buffer this packed step owns (pooled with its other buffers); the
-            # kernels read it in place -- pinned host memory is mapped into the device's address space --, so there is no
-            # copy to launch, to order or to wait for. The buffer is refilled only after the step that read it last has
-            # finished (an event per buffer set; three sets take turns, so the wait is over before it is asked for).
-            # 'copy': pinned staging ring -> ONE host-to-device copy in stream order (behind the step that read this id
-            # buffer last, in front of the one that will). (A separate copy stream with events both ways was measured
-            # too: the loop is host-bound either way and the copy sometimes queued behind the running step -- 0.078 or
-            # 0.185 ms per step by run.)
-            direct = self.host_ids == 'direct'
-            if direct:
-                if bufs.stage is None or bufs.stage.numel() < n_ids:
-                    bufs.stage = torch.empty(max(n_ids, 1 << 12), dtype=torch.long, pin_memory=True)
-                    bufs.last_use = None
-                if bufs.last_use is not None:
-                    bufs.last_use.synchronize()
-                stage = bufs.stage[:n_ids]
-            else:
-                stage = self._staging(n_ids)
-            if ids is None:
-                self.flatten_ids(batches, out=stage.numpy())
-            else:
-                h = ids.numpy() if torch.is_tensor(ids) else ids
-                if not (isinstance(h, np.ndarray) and h.dtype == np.int64 and h.shape == (n_ids,)):
-                    raise ValueError('ids: an int64 array of %d ids (flatten_ids layout)' % n_ids)
-                np.copyto(stage.numpy(), h)
-            if prof is not None:
-                t1 = time.perf_counter(); prof['ids to staging'] = prof.get('ids to staging', 0.0) + t1 - t0; t0 = t1
-            if direct:
-                dev = stage
-                ps.ids_ref = bufs.stage
-            else:
-                if bufs.ids is None or bufs.ids.numel() < n_ids:
-                    bufs.ids = torch.empty(n_ids, dtype=torch.long, device=self.device)
-                dev = bufs.ids[:n_ids]
-                cs = torch.cuda.current_stream(self.device)
-                # (the library's own hipMemcpyAsync wrapper: copy_ through torch is ~3x the host time)
-                st = ops.lib().mpqe_copy_to_device(dev.data_ptr(), stage.data_ptr(), 8 * n_ids, cs.cuda_stream)
-                _capi.check(ops.lib(), st, 'mpqe_copy_to_device')
-                self._stage_events[self._stage_next].record(cs)      # the staging buffer is free again once this copy has run
-                ps.ids_ref = bufs.ids
-                if prof is not None:
-                    t1 = time.perf_counter(); prof['copy to device'] = prof.get('copy to device', 0.0) + t1 - t0; t0 = t1
-        if dev is None:
-            ps.anchor_ids = ps.targets = ps.negs = None
+            dev = self._host_ids(ps, batches, ids, n_ids)
+        ps.anchor_ids, ps.targets, ps.negs = dev[:na], dev[na:na + ngr], dev[na + ngr:]
+
+    def _host_ids(self, ps, batches, ids, n_ids):
+        """Ids from the host (ids: None = those of the batches, else one array in flatten_ids' layout); returns the tensor
+        the kernels read. 'direct': into the PINNED buffer this packed step owns (pooled with its other buffers); the
+        kernels read it in place -- pinned host memory is mapped into the device's address space --, so there is no
+        copy to launch, to order or to wait for. The buffer is refilled only after the step that read it last has
+        finished (an event per buffer set; three sets take turns, so the wait is over before it is asked for).
+        'copy': pinned staging ring -> ONE host-to-device copy in stream order (behind the step that read this id
+        buffer last, in front of the one that will). (A separate copy stream with events both ways was measured
+        too: the loop is host-bound either way and the copy sometimes queued behind the running step -- 0.078 or
+        0.185 ms per step by run.)"""
+        bufs, prof = ps.bufs, self._prof
+        direct = self.host_ids == 'direct'
+        if direct:
+            if bufs.stage is None or bufs.stage.numel() < n_ids:
+                bufs.stage = torch.empty(max(n_ids, 1 << 12), dtype=torch.long, pin_memory=True)
+                bufs.last_use = None
+            if bufs.last_use is not None:
+                bufs.last_use.synchronize()
+            stage = bufs.stage[:n_ids]
         else:
-            ps.anchor_ids, ps.targets, ps.negs = dev[:na], dev[na:na + ngr], dev[na + ngr:]
-        if self.touch and mode is not None:
-            if bufs.touch is None:
-                # (zero-filled once: the step reads plan entries before it knows whether its own build finished, include/mpqe_amd.h)
-                bufs.touch = torch.zeros(sz[2] + 256, dtype=torch.uint8, device=self.device)
-                bufs.touch_ptr = (bufs.touch.data_ptr() + 255) // 256 * 256
-            ps.touch, ps.touch_ptr = bufs.touch, bufs.touch_ptr
-            if mode == 'pack':
-                if dev is None:
-                    raise ValueError("ids='external' needs the in-step touch plan (touch='step')")
-                self.build_touch(ps)
-            if prof is not None:
-                t1 = time.perf_counter(); prof['touch plan'] = prof.get('touch plan', 0.0) + t1 - t0
-        return ps
+            stage = self._staging(n_ids)
+        if ids is None:
+            self.flatten_ids(batches, out=stage.numpy())
+        else:
+            h = ids.numpy() if torch.is_tensor(ids) else ids
+            if not (isinstance(h, np.ndarray) and h.dtype == np.int64 and h.shape == (n_ids,)):
+                raise ValueError('ids: an int64 array of %d ids (flatten_ids layout)' % n_ids)
+            np.copyto(stage.numpy(), h)
+        if prof is not None:
+            self._tick('ids to staging')
+        if direct:
+            ps.ids_ref = bufs.stage
+            return stage
+        if bufs.ids is None or bufs.ids.numel() < n_ids:
+            bufs.ids = torch.empty(n_ids, dtype=torch.long, device=self.device)
+        dev = bufs.ids[:n_ids]
+        cs = torch.cuda.current_stream(self.device)
+        # (the library's own hipMemcpyAsync wrapper: copy_ through torch is ~3x the host time)
+        st = ops.lib().mpqe_copy_to_device(dev.data_ptr(), stage.data_ptr(), 8 * n_ids, cs.cuda_stream)
+        _capi.check(ops.lib(), st, 'mpqe_copy_to_device')
+        self._stage_events[self._stage_next].record(cs)      # the staging buffer is free again once this copy has run
+        ps.ids_ref = bufs.ids
+        if prof is not None:
+            self._tick('copy to device')
+        return dev
+
+    def _touch_plan(self, ps):
+        """The packed step's touch-plan buffer (pooled with its other buffers), and the plan itself when pack builds it."""
+        if not self.touch or ps.touch_mode is None:
+            return
+        bufs = ps.bufs
+        if bufs.touch is None:
+            # (zero-filled once: the step reads plan entries before it knows whether its own build finished, include/mpqe_amd.h)
+            bufs.touch = torch.zeros(ps.touch_sizes[0] + 256, dtype=torch.uint8, device=self.device)
+            bufs.touch_ptr = _align256(bufs.touch.data_ptr())
+        ps.touch, ps.touch_ptr = bufs.touch, bufs.touch_ptr
+        if ps.touch_mode == 'pack':
+            if ps.anchor_ids is None:
+                raise ValueError("ids='external' needs the in-step touch plan (touch='step')")
+            self.build_touch(ps)
+        if self._prof is not None:
+            self._tick('touch plan')
 
     def build_touch(self, ps, library_sort=False, id_ptrs=None):
         """The touch plan of the packed step's ids (include/mpqe_amd.h: mpqe_step_touch_build): which looked-up
@@ -542,29 +613,27 @@ class FusedTrainStep(object):
             raise _capi.MpqeError('mpqe_step_touch_bytes rejected the step descriptors')
         if ps.touch is None:
             ps.touch = torch.zeros(nbytes + 256, dtype=torch.uint8, device=self.device)
-            ps.touch_ptr = (ps.touch.data_ptr() + 255) // 256 * 256
+            ps.touch_ptr = _align256(ps.touch.data_ptr())
         # (build workspace: ONE buffer per step object, grown on demand -- every build runs on the current stream, so the
         # next build's kernels are ordered behind this one's; pack time is host time, and an allocation + record_stream
         # per pack was a quarter of the touch plan's)
-        ws = getattr(self, '_touch_ws', None)
+        ws = self._touch_ws
         if ws is None or ws.numel() < wbytes + 256:
             ws = self._touch_ws = torch.empty(max(wbytes + 256, 1 << 20), dtype=torch.uint8, device=self.device)
         stream = torch.cuda.current_stream(self.device)
-        if getattr(self, '_touch_ws_stream', None) not in (None, stream.cuda_stream):
+        if self._touch_ws_stream not in (None, stream.cuda_stream):
             stream.wait_stream(self._touch_ws_stream_obj)      # (a caller that switched streams: order the re-use)
         self._touch_ws_stream, self._touch_ws_stream_obj = stream.cuda_stream, stream
         if id_ptrs is None:
             id_ptrs = (ps.anchor_ids.data_ptr(), ps.targets.data_ptr(), ps.negs.data_ptr())
         with torch.cuda.device(self.device):
             st = L.mpqe_step_touch_build(ctypes.byref(self.P), ps.batches, ps.nb, id_ptrs[0], id_ptrs[1], id_ptrs[2],
-                                         ps.touch_ptr, nbytes, (ws.data_ptr() + 255) // 256 * 256, wbytes, stream.cuda_stream)
+                                         ps.touch_ptr, nbytes, _align256(ws.data_ptr()), wbytes, stream.cuda_stream)
         _capi.check(L, st, 'mpqe_step_touch_build')
 
     def _staging(self, n):
         """A pinned host buffer of >= n int64 from a small ring (allocating pinned memory costs more than the rest of
         pack()); a buffer is handed out again only after the copy that read it last has completed."""
-        if not hasattr(self, '_stage_ring'):
-            self._stage_ring, self._stage_events, self._stage_next = [None] * 4, [None] * 4, -1
         k = self._stage_next = (self._stage_next + 1) % 4
         if self._stage_events[k] is not None:
             self._stage_events[k].synchronize()
@@ -576,13 +645,12 @@ class FusedTrainStep(object):
 
     def uses_chain_dims(self):
         """True when steps of this model run the chain kernels (whatever the batches: at most 5 passes assumed)."""
-        return not (self.flags & _capi.STEP_NO_CHAIN) and self.model.emb_dim in (64, 128, 256)
+        return chain_form(self.flags, self.model.emb_dim, self.learned, graphs=0, max_passes=0)
 
     def uses_chain(self, packed):
         """True when the library runs the graph-block chain kernels for this step (csrc/step.hip)."""
         passes = max(int(packed.batches[i].num_passes) for i in range(packed.nb))
-        return (not (self.flags & _capi.STEP_NO_CHAIN) and self.model.emb_dim in (64, 128, 256)
-                and packed.num_graphs <= CHAIN_MAX_GRAPHS and passes <= (3 if self.learned else 5))
+        return chain_form(self.flags, self.model.emb_dim, self.learned, packed.num_graphs, passes)
 
     def merged(self, packed):
         """True when the weight-gradient tiles and the backward post-pass ride in the chain launch (two launches per
@@ -590,12 +658,31 @@ class FusedTrainStep(object):
         if not self.uses_chain(packed) or len(packed.lane_begin) > 2 or self.merge_tail is False:
             return False
         blocks = sum((int(b) + 15) // 16 for b in packed.sizes)
-        return bool(self.merge_tail) or blocks <= 256 + 256 // 8
+        return bool(self.merge_tail) or blocks <= MERGE_MAX_BLOCKS
 
     def _workspace(self, nbytes):
         if self._ws is None or self._ws.numel() < nbytes + 256:
             self._ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.device)
-        return (self._ws.data_ptr() + 255) // 256 * 256
+        return _align256(self._ws.data_ptr())
+
+    def _call_flags(self, packed, zero_grads=False):
+        """Set the flags of the next library call on `packed`: the step object's switches, the packed step's, and whether the
+        call zero-fills the gradient buffers itself (one launch with its other prologue work)."""
+        self.P.flags = self.flags | packed.step_flags | (_capi.STEP_ZERO_GRADS if zero_grads else 0)
+
+    def _step_call(self, packed, id_ptrs, backward, out, desc, ws, stream, lanes=None, events=None, touch_ptr=None, extra=None):
+        """The entry point and the argument tuple of one step (include/mpqe_amd.h: mpqe_step_forward_backward, or _ex with
+        `extra`). out: (loss, scores_pos, scores_neg) tensors, scores None = not wanted; desc: (address, bytes, upload the
+        table first) of the descriptor table; ws: (address, bytes) of the workspace."""
+        loss, sp, sn = out
+        L = ops.lib()
+        args = (ctypes.byref(self.P), packed.batches, packed.nb, id_ptrs[0], id_ptrs[1], id_ptrs[2], self.margin,
+                ctypes.byref(self.G), 1 if backward else 0, loss.data_ptr(), None if sp is None else sp.data_ptr(),
+                None if sn is None else sn.data_ptr(), desc[0], desc[1], 1 if desc[2] else 0, ws[0], ws[1],
+                self.err.data_ptr(), lanes, events, 0 if events is None else len(events), touch_ptr, stream.cuda_stream)
+        if extra is None:
+            return L.mpqe_step_forward_backward, args
+        return L.mpqe_step_forward_backward_ex, args + (ctypes.byref(extra),)
 
     def run(self, packed, backward=True, zero_grad=True, scores=False, events=None, workspace=None, checked=False,
             id_ptrs=None, extra=None, out=None):
@@ -619,8 +706,7 @@ class FusedTrainStep(object):
         wanted)."""
         if backward:
             self.bind_grads()
-        # the library zero-fills the gradient buffers itself (one launch with its other prologue work)
-        self.P.flags = self.flags | packed.step_flags | (_capi.STEP_ZERO_GRADS if (backward and zero_grad) else 0)
+        self._call_flags(packed, backward and zero_grad)
         bufs = packed.bufs
         stream = torch.cuda.current_stream(self.device)
         sp = sn = None
@@ -643,18 +729,11 @@ class FusedTrainStep(object):
         else:
             if workspace.numel() < packed.ws_bytes + 256 or workspace.device != self.device:
                 raise ValueError('workspace too small for this packed step')
-            wptr = (workspace.data_ptr() + 255) // 256 * 256
+            wptr = _align256(workspace.data_ptr())
         L = ops.lib()
-        args = (ctypes.byref(self.P), packed.batches, packed.nb, id_ptrs[0], id_ptrs[1], id_ptrs[2], self.margin,
-                ctypes.byref(self.G),
-                1 if backward else 0, loss.data_ptr(), None if sp is None else sp.data_ptr(),
-                None if sn is None else sn.data_ptr(), packed.desc_ptr, packed.desc_bytes,
-                0 if bufs.desc_resident else 1, wptr, packed.ws_bytes, self.err.data_ptr(), packed.lanes,
-                events, 0 if events is None else len(events), packed.touch_ptr,
-                stream.cuda_stream)
-        fn = L.mpqe_step_forward_backward
-        if extra is not None:
-            fn, args = L.mpqe_step_forward_backward_ex, args + (ctypes.byref(extra),)
+        fn, args = self._step_call(packed, id_ptrs, backward, (loss, sp, sn),
+                                   (packed.desc_ptr, packed.desc_bytes, not bufs.desc_resident), (wptr, packed.ws_bytes),
+                                   stream, packed.lanes, events, packed.touch_ptr, extra)
         if torch.cuda.current_device() != self.device.index:        # (the context manager costs ~10 us of host time)
             with torch.cuda.device(self.device):
                 st = fn(*args)
@@ -669,7 +748,7 @@ class FusedTrainStep(object):
                 self.touch_retries += 1
                 self._pack_touch_sets.add((bytes(packed.batches), tuple(packed.lane_begin)))
                 self.build_touch(packed, library_sort=True, id_ptrs=id_ptrs)
-                self.P.flags = self.flags | packed.step_flags | (_capi.STEP_ZERO_GRADS if zero_grad else 0)
+                self._call_flags(packed, zero_grad)
                 with torch.cuda.device(self.device):
                     st = L.mpqe_step_table_rows(ctypes.byref(self.P), packed.batches, packed.nb, ctypes.byref(self.G),
                                                 packed.desc_ptr, wptr, packed.ws_bytes, packed.touch_ptr, stream.cuda_stream)
@@ -709,13 +788,10 @@ class FusedTrainStep(object):
             raise _capi.MpqeError('the level form rejected the step descriptors')
         ws = torch.empty(wsb + 256, dtype=torch.uint8, device=self.device)
         desc = torch.empty(dsb + 256, dtype=torch.uint8, device=self.device)
-        args = (ctypes.byref(self.P), packed.batches, packed.nb, id_ptrs[0], id_ptrs[1], id_ptrs[2], self.margin,
-                ctypes.byref(self.G), 1, loss.data_ptr(),
-                None if sp is None else sp.data_ptr(), None if sn is None else sn.data_ptr(),
-                (desc.data_ptr() + 255) // 256 * 256, dsb, 1, (ws.data_ptr() + 255) // 256 * 256, wsb, self.err.data_ptr(), None,
-                None, 0, None, stream.cuda_stream, None if extra is None else ctypes.byref(extra))
+        fn, args = self._step_call(packed, id_ptrs, True, (loss, sp, sn), (_align256(desc.data_ptr()), dsb, True),
+                                   (_align256(ws.data_ptr()), wsb), stream, extra=extra)
         with torch.cuda.device(self.device):
-            st = L.mpqe_step_forward_backward_ex(*args)
+            st = fn(*args)
         _capi.check(L, st, 'mpqe_step_forward_backward (level form)')
         torch.cuda.synchronize(self.device)          # (ws / desc are this call's own: they must outlive its launches)
 

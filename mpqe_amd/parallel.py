@@ -436,7 +436,7 @@ class StepExchange(object):
             wbytes = L.mpqe_rows_plan_workspace_bytes(ep.entries, self.row_bits + 5)
             ep.plan_sizes = (nbytes, wbytes)
             ep.plan = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.dev)
-            ep.plan_ptr = (ep.plan.data_ptr() + 255) // 256 * 256
+            ep.plan_ptr = _capi._align256(ep.plan.data_ptr())
             ep.plan_ws = torch.empty(wbytes + 256, dtype=torch.uint8, device=self.dev)
             ep.send_keys = torch.full((ep.cap,), -1, dtype=torch.int64, device=self.dev)
             ep.all_keys = torch.empty(self.world * ep.cap, dtype=torch.int64, device=self.dev)
@@ -474,11 +474,11 @@ class StepExchange(object):
         nbytes = L.mpqe_rows_plan_bytes(ep.entries)
         wbytes = L.mpqe_rows_plan_workspace_bytes(ep.entries, self.row_bits + 5)
         ep.plan = torch.empty(nbytes + 256, dtype=torch.uint8, device=self.dev)
-        ep.plan_ptr = (ep.plan.data_ptr() + 255) // 256 * 256
+        ep.plan_ptr = _capi._align256(ep.plan.data_ptr())
         ws = torch.empty(wbytes + 256, dtype=torch.uint8, device=self.dev)
         with torch.cuda.device(self.dev):
             st = L.mpqe_rows_plan_build(allk.data_ptr(), ep.entries, self.row_bits, self.row_bits + 5, ep.plan_ptr, nbytes,
-                                        (ws.data_ptr() + 255) // 256 * 256, wbytes, torch.cuda.current_stream().cuda_stream)
+                                        _capi._align256(ws.data_ptr()), wbytes, torch.cuda.current_stream().cuda_stream)
         _capi.check(L, st, 'mpqe_rows_plan_build')
         ws.record_stream(torch.cuda.current_stream())
         tab = uk >> self.row_bits
@@ -567,7 +567,7 @@ class StepExchange(object):
         nbytes, wbytes = ep.plan_sizes
         with torch.cuda.device(self.dev):
             st = L.mpqe_rows_plan_build(ep.all_keys.data_ptr(), ep.entries, self.row_bits, self.row_bits + 5, ep.plan_ptr,
-                                        nbytes, (ep.plan_ws.data_ptr() + 255) // 256 * 256, wbytes,
+                                        nbytes, _capi._align256(ep.plan_ws.data_ptr()), wbytes,
                                         torch.cuda.current_stream().cuda_stream)
         _capi.check(L, st, 'mpqe_rows_plan_build')
 

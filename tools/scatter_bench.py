@@ -23,9 +23,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 def run(qt, D, B, R, dev, iters=20):
     from mpqe_amd.model import RGCNConv
-    from mpqe_amd.fused import _TEMPLATES            # query type -> (anchors, nodes, [(src, dst)])
-    _, N, edges = _TEMPLATES[qt]
-    src, dst = np.array([e[0] for e in edges]), np.array([e[1] for e in edges])
+    from mpqe_amd import ops
+    info = ops.template_info(qt)                     # the library's template tables (include/mpqe_amd.h)
+    N = info.num_nodes
+    src, dst = np.array(info.src[:info.num_edges]), np.array(info.dst[:info.num_edges])
     offs = (np.arange(B, dtype=np.int64) * N)[:, None]
     ei = np.stack([(src[None] + offs).reshape(-1), (dst[None] + offs).reshape(-1)])
     et = np.random.RandomState(0).randint(0, R, size=ei.shape[1]).astype(np.int64)
