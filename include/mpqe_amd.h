@@ -601,6 +601,34 @@ int mpqe_adam_rows_step(const void *touch, int64_t num_entries /* of the plan: m
                         float *const *exp_avg_sq, int num_modes, int64_t dim, double lr, double beta1, double beta2,
                         double eps, int64_t step, void *stream);
 
+/* ---- the same three updates, refused on the device when the step flagged a fault ------------------------------------
+ * reference train_helpers.py:119-120: `loss.backward(); optimizer.step()` (the optimisers of train.py:83-88). The
+ * reference's lookups raise IndexError on a bad id BEFORE optimizer.step() is reached; the fused step never raises, it ORs
+ * MPQE_FLAG_* into its 4-byte error word, which the host reads when asked -- in the unchecked loop one call late, after
+ * the update. These entry points take that word, so a flagged step's gradients (garbage, or table rows missing) never
+ * reach the parameters or the moments, with no host synchronisation:
+ *   guard    device word, required (NULL: MPQE_ERR_INVALID_ARG). Every workgroup reads it once, before its first
+ *            store. Non-zero when the launch executes: the launch writes NOTHING -- param, exp_avg, exp_avg_sq and
+ *            *applied keep their bits -- and the call still returns MPQE_OK (the refusal is the device's; the host
+ *            learns of it from the word, as before). Zero: exactly the bits the unguarded entry point writes (one
+ *            kernel serves both; the unguarded calls pass no word).
+ *   applied  optional (NULL: not counted) device counter of the updates that really happened: with a clean word exactly
+ *            ONE thread of the launch adds 1 to it, whatever the grid size. An update of several launches passes it to
+ *            one of them only.
+ * The word must not be written by work that runs CONCURRENTLY with the launch (another stream without an event in
+ * between, a peer): workgroups would disagree and the update would be torn. Work earlier on the same stream -- the
+ * step itself -- is what it is for. The word is sticky: every guarded update is refused until the host clears it.
+ * Everything else (arguments, their checks, the update rules) as in the unguarded calls above.                       */
+int mpqe_adam_step_guarded(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, double lr,
+                           double beta1, double beta2, double eps, double weight_decay, int64_t step,
+                           const int32_t *guard, int64_t *applied, void *stream);
+int mpqe_sgd_step_guarded(float *param, const float *grad, int64_t n, double lr, double weight_decay,
+                          const int32_t *guard, int64_t *applied, void *stream);
+int mpqe_adam_rows_step_guarded(const void *touch, int64_t num_entries, float *const *params, const float *const *grads,
+                                float *const *exp_avg, float *const *exp_avg_sq, int num_modes, int64_t dim, double lr,
+                                double beta1, double beta2, double eps, int64_t step, const int32_t *guard,
+                                int64_t *applied, void *stream);
+
 /* ---- data-parallel exchange of entity-table gradient rows ("exchange touched rows only") ---------
  * Every rank all-gathers the (table, row) keys its packed step touches (key = table << row_bits | row, ~0 = none: the
  * touch plan's sorted keys without repeats, padded) ONCE at pack time and builds one plan over all ranks' keys

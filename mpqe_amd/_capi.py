@@ -115,6 +115,10 @@ PROTOTYPES = {
     'mpqe_sgd_step': (I, [P, P, L, DBL, DBL, P]),
     'mpqe_adam_rows_step': (I, [P, L, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p),
                                 ctypes.POINTER(c_void_p), I, L, DBL, DBL, DBL, DBL, L, P]),
+    'mpqe_adam_step_guarded': (I, [P, P, P, P, L, DBL, DBL, DBL, DBL, DBL, L, P, P, P]),
+    'mpqe_sgd_step_guarded': (I, [P, P, L, DBL, DBL, P, P, P]),
+    'mpqe_adam_rows_step_guarded': (I, [P, L, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p),
+                                        ctypes.POINTER(c_void_p), I, L, DBL, DBL, DBL, DBL, L, P, P, P]),
     'mpqe_step_workspace_bytes': (Z, [ctypes.POINTER(StepParams), ctypes.POINTER(StepBatch), I, ctypes.POINTER(StepLanes)]),
     'mpqe_step_desc_bytes': (Z, [ctypes.POINTER(StepParams), ctypes.POINTER(StepBatch), I, ctypes.POINTER(StepLanes)]),
     'mpqe_step_states_layout': (I, [ctypes.POINTER(StepParams), ctypes.POINTER(StepBatch), I, ctypes.POINTER(StepLanes),

@@ -19,10 +19,21 @@ __device__ __forceinline__ void adam_one(float &p, float g, float &m, float &v, 
     p -= step_size * (m / denom);
 }
 
+// The guarded entry points (include/mpqe_amd.h: mpqe_*_step_guarded) run the SAME kernels with the step's error word:
+// every workgroup reads it once, before its first store, from one address (a scalar load, a uniform branch); non-zero =
+// the whole launch writes nothing. With a clean word one thread of the launch counts the update in *applied.
+__device__ __forceinline__ bool update_refused(const int32_t *guard, long long *applied) {
+    if (guard && *guard != 0) return true;
+    if (applied && blockIdx.x == 0 && threadIdx.x == 0) *applied += 1;
+    return false;
+}
+
 __global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, const float *__restrict__ g,
                                                    float *__restrict__ m, float *__restrict__ v, long long n,
                                                    float omb1, float b2, float omb2, float eps, float wd,
-                                                   float step_size, float sqrt_bc2, int vec) {
+                                                   float step_size, float sqrt_bc2, int vec,
+                                                   const int32_t *__restrict__ guard, long long *__restrict__ applied) {
+    if (update_refused(guard, applied)) return;
     const long long tid = (long long)blockIdx.x * 256 + threadIdx.x, stride = (long long)gridDim.x * 256;
     if (vec) {
         for (long long i = tid * 4; i < n; i += stride * 4) {
@@ -52,7 +63,9 @@ __global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, const 
 
 // torch.optim.SGD (momentum = 0, dampening = 0, nesterov = False):  p -= lr * (g + wd * p)
 __global__ __launch_bounds__(256) void sgd_kernel(float *__restrict__ p, const float *__restrict__ g, long long n,
-                                                  float lr, float wd) {
+                                                  float lr, float wd, const int32_t *__restrict__ guard,
+                                                  long long *__restrict__ applied) {
+    if (update_refused(guard, applied)) return;
     const long long tid = (long long)blockIdx.x * 256 + threadIdx.x, stride = (long long)gridDim.x * 256;
     for (long long i = tid; i < n; i += stride) p[i] -= lr * (g[i] + wd * p[i]);
 }
@@ -63,9 +76,9 @@ static unsigned optim_grid(int64_t n, int per_thread) {
     return (unsigned)(blocks < 1 ? 1 : blocks);
 }
 
-extern "C" int mpqe_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
-                              double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step,
-                              void *stream) {
+static int adam_launch(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, double lr,
+                       double beta1, double beta2, double eps, double weight_decay, int64_t step, const int32_t *guard,
+                       int64_t *applied, void *stream) {
     if (!param || !grad || !exp_avg || !exp_avg_sq || n <= 0 || step < 1) return MPQE_ERR_INVALID_ARG;
     if (!(beta1 >= 0. && beta1 < 1. && beta2 >= 0. && beta2 < 1.)) return MPQE_ERR_INVALID_ARG;
     // bias corrections in double on the host, as torch does with python floats
@@ -76,15 +89,40 @@ extern "C" int mpqe_adam_step(float *param, const float *grad, float *exp_avg, f
     const int vec = ((uintptr_t)param % 16 == 0) && ((uintptr_t)grad % 16 == 0) && ((uintptr_t)exp_avg % 16 == 0) &&
                     ((uintptr_t)exp_avg_sq % 16 == 0);
     hipLaunchKernelGGL(adam_kernel, dim3(optim_grid(n, 4)), dim3(256), 0, as_stream(stream), param, grad, exp_avg,
-                       exp_avg_sq, (long long)n, omb1, (float)beta2, omb2, (float)eps, (float)weight_decay, step_size, sqrt_bc2, vec);
+                       exp_avg_sq, (long long)n, omb1, (float)beta2, omb2, (float)eps, (float)weight_decay, step_size, sqrt_bc2, vec,
+                       guard, reinterpret_cast<long long *>(applied));
+    return mpqe_launch_status();
+}
+
+extern "C" int mpqe_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
+                              double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step,
+                              void *stream) {
+    return adam_launch(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, nullptr, nullptr, stream);
+}
+
+extern "C" int mpqe_adam_step_guarded(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
+                                      double lr, double beta1, double beta2, double eps, double weight_decay, int64_t step,
+                                      const int32_t *guard, int64_t *applied, void *stream) {
+    if (!guard) return MPQE_ERR_INVALID_ARG;
+    return adam_launch(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, guard, applied, stream);
+}
+
+static int sgd_launch(float *param, const float *grad, int64_t n, double lr, double weight_decay, const int32_t *guard,
+                      int64_t *applied, void *stream) {
+    if (!param || !grad || n <= 0) return MPQE_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(sgd_kernel, dim3(optim_grid(n, 1)), dim3(256), 0, as_stream(stream), param, grad, (long long)n,
+                       (float)lr, (float)weight_decay, guard, reinterpret_cast<long long *>(applied));
     return mpqe_launch_status();
 }
 
 extern "C" int mpqe_sgd_step(float *param, const float *grad, int64_t n, double lr, double weight_decay, void *stream) {
-    if (!param || !grad || n <= 0) return MPQE_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(sgd_kernel, dim3(optim_grid(n, 1)), dim3(256), 0, as_stream(stream), param, grad, (long long)n,
-                       (float)lr, (float)weight_decay);
-    return mpqe_launch_status();
+    return sgd_launch(param, grad, n, lr, weight_decay, nullptr, nullptr, stream);
+}
+
+extern "C" int mpqe_sgd_step_guarded(float *param, const float *grad, int64_t n, double lr, double weight_decay,
+                                     const int32_t *guard, int64_t *applied, void *stream) {
+    if (!guard) return MPQE_ERR_INVALID_ARG;
+    return sgd_launch(param, grad, n, lr, weight_decay, guard, applied, stream);
 }
 
 // ------------------------------------------------------------------------------------ negative sampling

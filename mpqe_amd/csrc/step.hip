@@ -1137,7 +1137,11 @@ struct RowAdamPtrs {
 };
 __global__ __launch_bounds__(256) void adam_rows_kernel(const TouchHeader *__restrict__ th, const tkey_t *__restrict__ keys,
                                                         int D, RowAdamPtrs rp, float omb1, float omb2, float eps,
-                                                        float neg_step_size) {
+                                                        float neg_step_size, const int32_t *__restrict__ guard,
+                                                        long long *__restrict__ applied) {
+    // (mpqe_adam_rows_step_guarded: the step's error word, read once per workgroup before any store -- csrc/optim.hip)
+    if (guard && *guard != 0) return;
+    if (applied && blockIdx.x == 0 && threadIdx.x == 0) *applied += 1;
     // one group of D / 4 lanes per sorted position; the first position of a run of equal keys owns the row
     const int lpr = D / 4, per = 256 / lpr;
     const long long k = (long long)blockIdx.x * per + threadIdx.x / lpr;
@@ -1278,10 +1282,10 @@ extern "C" int mpqe_step_table_rows(const mpqe_step_params_t *P, const mpqe_step
     return mpqe_launch_status();
 }
 
-extern "C" int mpqe_adam_rows_step(const void *touch, int64_t num_entries, float *const *params,
-                                   const float *const *grads, float *const *exp_avg, float *const *exp_avg_sq,
-                                   int num_modes, int64_t dim, double lr, double beta1, double beta2, double eps,
-                                   int64_t step, void *stream) {
+static int adam_rows_launch(const void *touch, int64_t num_entries, float *const *params, const float *const *grads,
+                            float *const *exp_avg, float *const *exp_avg_sq, int num_modes, int64_t dim, double lr,
+                            double beta1, double beta2, double eps, int64_t step, const int32_t *guard, int64_t *applied,
+                            void *stream) {
     if (!touch || num_entries <= 0 || !params || !grads || !exp_avg || !exp_avg_sq || step < 1) return MPQE_ERR_INVALID_ARG;
     if (num_modes <= 0 || num_modes > MPQE_STEP_MAX_MODES || dim <= 0 || dim % 4 != 0 || dim > 1024 || 256 % (dim / 4) != 0)
         return MPQE_ERR_UNSUPPORTED;
@@ -1305,8 +1309,26 @@ extern "C" int mpqe_adam_rows_step(const void *touch, int64_t num_entries, float
     const long long per = 256 / (dim / 4);
     hipLaunchKernelGGL(adam_rows_kernel, dim3((unsigned)((M + per - 1) / per)), dim3(256), 0, as_stream(stream),
                        reinterpret_cast<const TouchHeader *>(tb), reinterpret_cast<const tkey_t *>(tb + L.keys), (int)dim, rp,
-                       (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, neg_step);
+                       (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, neg_step, guard,
+                       reinterpret_cast<long long *>(applied));
     return mpqe_launch_status();
+}
+
+extern "C" int mpqe_adam_rows_step(const void *touch, int64_t num_entries, float *const *params,
+                                   const float *const *grads, float *const *exp_avg, float *const *exp_avg_sq,
+                                   int num_modes, int64_t dim, double lr, double beta1, double beta2, double eps,
+                                   int64_t step, void *stream) {
+    return adam_rows_launch(touch, num_entries, params, grads, exp_avg, exp_avg_sq, num_modes, dim, lr, beta1, beta2, eps,
+                            step, nullptr, nullptr, stream);
+}
+
+extern "C" int mpqe_adam_rows_step_guarded(const void *touch, int64_t num_entries, float *const *params,
+                                           const float *const *grads, float *const *exp_avg, float *const *exp_avg_sq,
+                                           int num_modes, int64_t dim, double lr, double beta1, double beta2, double eps,
+                                           int64_t step, const int32_t *guard, int64_t *applied, void *stream) {
+    if (!guard) return MPQE_ERR_INVALID_ARG;
+    return adam_rows_launch(touch, num_entries, params, grads, exp_avg, exp_avg_sq, num_modes, dim, lr, beta1, beta2, eps,
+                            step, guard, applied, stream);
 }
 
 // sum_i ||p_i||_2 of up to four parameter tensors and its backward (the regulariser of margin_loss, reference

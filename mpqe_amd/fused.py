@@ -744,7 +744,7 @@ class FusedTrainStep(object):
         if checked:
             flags = int(self.err.item())                  # (synchronises)
             if flags & _capi.FLAG_TOUCH_RETRY and backward and packed.touch_ptr is not None:
-                self.err.fill_(flags & ~_capi.FLAG_TOUCH_RETRY)
+                ops.clear_flags(self.err, flags & ~_capi.FLAG_TOUCH_RETRY)
                 self.touch_retries += 1
                 self._pack_touch_sets.add((bytes(packed.batches), tuple(packed.lane_begin)))
                 self.build_touch(packed, library_sort=True, id_ptrs=id_ptrs)
@@ -760,7 +760,7 @@ class FusedTrainStep(object):
                 # trusted; the LEVEL form (one launch per message-passing level, include/mpqe_amd.h MPQE_STEP_NO_CHAIN) hands
                 # nothing from workgroup to workgroup inside a launch: the step runs again there, into the same buffers --
                 # slower, never wrong. (Without the call's own zero fill the garbage cannot be taken back: that raises.)
-                self.err.fill_(flags & ~(_capi.FLAG_INTERNAL | 0xff00))
+                ops.clear_flags(self.err, flags & ~(_capi.FLAG_INTERNAL | 0xff00))
                 self.handoff_retries += 1
                 self._rerun_level_form(packed, loss, sp, sn, stream, id_ptrs, extra)
                 flags = int(self.err.item())

@@ -50,12 +50,23 @@ def new_error_word(device):
     return torch.zeros(1, dtype=torch.int32, device=device)
 
 
+flag_clears = 0       # how often the host has rewritten a non-zero error word (clear_flags): FlatOptimizer(guard=True) re-reads
+                      # its device count of applied updates when this has moved -- updates may have been refused meanwhile
+
+
+def clear_flags(err, value=0):
+    """Rewrite an error word the host has read as non-zero (value: the bits that stay). Every such site goes through here."""
+    global flag_clears
+    err.fill_(value)
+    flag_clears += 1
+
+
 def raise_on_flags(err):
     """One 4-byte D2H read (synchronises). Mirrors the IndexError the reference's
     index_select / nn.Embedding raise on a bad id."""
     flags = int(err.item())
     if flags:
-        err.zero_()
+        clear_flags(err)
         names = [n for bit, n in ((1, 'entity id outside node_map / not of this mode'),
                                   (2, 'edge endpoint outside [0, num_nodes)'),
                                   (4, 'edge type outside [0, num_relations)'),

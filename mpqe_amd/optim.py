@@ -22,6 +22,13 @@ rule of torch.optim.SparseAdam on the per-row gradient sums) and everything else
 
 Deviation from the reference's dense Adam, stated: a row no step touches keeps its moments undecayed and does not move
 (dense Adam decays every row's m, v every step and keeps moving rows whose m is non-zero).
+
+A flagged step is refused on the device. The fused step records a bad entity id (or a fault of its own) in its error word
+`FusedTrainStep.err`, which the unchecked loop reads one call late -- after `opt.step()`. `FlatOptimizer(step, guard=True)`,
+the default, hands that word to the update's launches (`mpqe_*_step_guarded`): while it is non-zero they write nothing, so
+the parameters and both moments still hold what they held when the host learns of the fault (IndexError, as the reference's
+lookup raises before its optimizer.step()). For a clean word the written bits are those of `guard=False`. No host sync, no
+extra launch; `steps_applied()` reads the device's count of the updates that really happened.
 """
 import ctypes
 
@@ -32,7 +39,7 @@ from . import _capi, ops
 
 class FlatOptimizer(object):
     def __init__(self, fused_step, lr=0.01, opt='adam', betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
-                 sparse_tables=False):
+                 sparse_tables=False, guard=True):
         if opt not in ('adam', 'sgd'):
             raise ValueError('opt must be adam or sgd')           # reference train.py:83-88
         if sparse_tables and (opt != 'adam' or weight_decay != 0.0):
@@ -45,6 +52,11 @@ class FlatOptimizer(object):
         self.t = 0
         params = fused_step.params
         dev = fused_step.device
+        # guard: the update's launches read fused_step.err and write nothing while it is non-zero; `applied` counts, on the
+        # device, the updates that did happen. The host's t (the bias corrections) follows it: see step().
+        self.guard = bool(guard)
+        self.applied = torch.zeros(1, dtype=torch.int64, device=dev) if self.guard else None
+        self._clears_seen = ops.flag_clears
         total = fused_step.flat_grad.numel()
         self.flat_param = torch.empty(total, dtype=torch.float32, device=dev)
         off = 0
@@ -83,34 +95,63 @@ class FlatOptimizer(object):
     def step(self, packed=None, rows_plan=None):
         """packed: with sparse_tables, the packed step whose gradients are being applied (its touch plan lists the
         table rows to update). rows_plan: under data parallelism the (plan pointer, entries) of the row exchange
-        (mpqe_amd.parallel.StepExchange): the rows ANY rank touched -- every replica updates the same rows."""
+        (mpqe_amd.parallel.StepExchange): the rows ANY rank touched -- every replica updates the same rows.
+
+        guard=True: every launch of the update reads the step's error word and writes nothing while it is set, so the
+        gradients of a flagged step are never folded in; the word stays set (and every later update refused) until the
+        host reads and clears it (FusedTrainStep.check(), the drop-in's next margin_loss, run(checked=True)). The bias
+        corrections use the host's t: once the host HAS cleared a word, the next step() reads the device's count of applied
+        updates (8 bytes, that path only) and continues from t = applied + 1. A clean loop never reads anything.
+        Under data parallelism the guard is THIS rank's own word: it keeps a rank's own fault out of its own replica.
+        Agreement between ranks stays StepExchange.check() before opt.step(), as before."""
+        if self.guard and self._clears_seen != ops.flag_clears:
+            self._clears_seen = ops.flag_clears
+            self.t = int(self.applied.item())
         self.t += 1
         self.fused.param_epoch += 1            # (the parameters are written behind autograd's version counters: dropin.py's lanes)
-        g = self.fused.flat_grad
+        if self.sparse_tables and (packed is None or packed.touch_ptr is None):
+            raise ValueError('sparse_tables: step(packed) needs the packed step (with its touch plan)')
+        L = ops.lib()
         with torch.cuda.device(self.fused.device):
-            stream = torch.cuda.current_stream().cuda_stream
-            if self.opt == 'adam' and self.sparse_tables:
-                if packed is None or packed.touch_ptr is None:
-                    raise ValueError('sparse_tables: step(packed) needs the packed step (with its touch plan)')
-                L = ops.lib()
-                st = 0
-                for o, n in self.dense_runs:
-                    st = st or L.mpqe_adam_step(self.flat_param.data_ptr() + 4 * o, g.data_ptr() + 4 * o,
-                                                self.exp_avg.data_ptr() + 4 * o, self.exp_avg_sq.data_ptr() + 4 * o, n,
-                                                self.lr, self.betas[0], self.betas[1], self.eps, 0.0, self.t, stream)
-                plan_ptr, entries = rows_plan if rows_plan is not None else (packed.touch_ptr, packed.touch_entries)
-                st = st or L.mpqe_adam_rows_step(plan_ptr, entries, self._tab_p, self._tab_g,
-                                                 self._tab_m, self._tab_v, len(self.table_slices),
-                                                 self.fused.model.emb_dim, self.lr, self.betas[0], self.betas[1],
-                                                 self.eps, self.t, stream)
-            elif self.opt == 'adam':
-                st = ops.lib().mpqe_adam_step(self.flat_param.data_ptr(), g.data_ptr(), self.exp_avg.data_ptr(),
-                                              self.exp_avg_sq.data_ptr(), g.numel(), self.lr, self.betas[0],
-                                              self.betas[1], self.eps, self.weight_decay, self.t, stream)
+            st = self._launch(L, packed, rows_plan, torch.cuda.current_stream().cuda_stream)
+        _capi.check(L, st, 'optimiser step')
+
+    def _launch(self, L, packed, rows_plan, stream):
+        """The launches of one update on `stream`; returns the first non-zero status. guard: the guarded entry point of each
+        with the step's error word; `applied` goes to the LAST launch only (nothing writes the word in between, so all
+        launches of one update decide alike, and the update is counted once)."""
+        g = self.fused.flat_grad
+        b1, b2 = self.betas
+        calls = []
+        if self.opt == 'adam' and self.sparse_tables:
+            for o, n in self.dense_runs:
+                calls.append(('mpqe_adam_step', (self.flat_param.data_ptr() + 4 * o, g.data_ptr() + 4 * o,
+                                                 self.exp_avg.data_ptr() + 4 * o, self.exp_avg_sq.data_ptr() + 4 * o, n,
+                                                 self.lr, b1, b2, self.eps, 0.0, self.t)))
+            plan_ptr, entries = rows_plan if rows_plan is not None else (packed.touch_ptr, packed.touch_entries)
+            calls.append(('mpqe_adam_rows_step', (plan_ptr, entries, self._tab_p, self._tab_g, self._tab_m, self._tab_v,
+                                                  len(self.table_slices), self.fused.model.emb_dim, self.lr, b1, b2,
+                                                  self.eps, self.t)))
+        elif self.opt == 'adam':
+            calls.append(('mpqe_adam_step', (self.flat_param.data_ptr(), g.data_ptr(), self.exp_avg.data_ptr(),
+                                             self.exp_avg_sq.data_ptr(), g.numel(), self.lr, b1, b2, self.eps,
+                                             self.weight_decay, self.t)))
+        else:
+            calls.append(('mpqe_sgd_step', (self.flat_param.data_ptr(), g.data_ptr(), g.numel(), self.lr, self.weight_decay)))
+        st = 0
+        for i, (name, args) in enumerate(calls):
+            if self.guard:
+                counter = self.applied.data_ptr() if i == len(calls) - 1 else None
+                st = st or getattr(L, name + '_guarded')(*(args + (self.fused.err.data_ptr(), counter, stream)))
             else:
-                st = ops.lib().mpqe_sgd_step(self.flat_param.data_ptr(), g.data_ptr(), g.numel(), self.lr,
-                                             self.weight_decay, stream)
-        _capi.check(ops.lib(), st, 'optimiser step')
+                st = st or getattr(L, name)(*(args + (stream,)))
+        return st
+
+    def steps_applied(self):
+        """The device's count of the updates that really happened (synchronises: one 8-byte read). guard=True only."""
+        if not self.guard:
+            raise ValueError('steps_applied: FlatOptimizer(guard=True) keeps the count')
+        return int(self.applied.item())
 
     def zero_grad(self, set_to_none=True):
         """torch.optim's call (reference train_helpers.py:78) for the drop-in entry points (mpqe_amd/dropin.py): one zero fill
@@ -124,6 +165,9 @@ class FlatOptimizer(object):
 
     def load_state_dict(self, sd):
         self.t = int(sd['t'])
+        if self.guard:
+            self.applied.fill_(self.t)
+            self._clears_seen = ops.flag_clears
         if self.opt == 'adam':
             self.exp_avg.copy_(sd['exp_avg'])
             self.exp_avg_sq.copy_(sd['exp_avg_sq'])
@@ -159,11 +203,14 @@ class _Switch(object):
         plain = ((kind == 'adam' and not kwargs.get('amsgrad') and not kwargs.get('maximize'))
                  or (kind == 'sgd' and not kwargs.get('momentum') and not kwargs.get('nesterov') and not kwargs.get('dampening')
                      and not kwargs.get('maximize')))
+        kwargs = dict(kwargs)
+        guard = kwargs.pop('guard', True)        # FlatOptimizer's; the torch optimisers have no such argument
         known = {'betas', 'eps', 'weight_decay', 'momentum', 'nesterov', 'dampening', 'amsgrad', 'maximize'}
         if (d is not None and plain and set(kwargs) <= known and len(params) == len(d.step.params)
                 and {id(p) for p in params} == {id(p) for p in d.step.params}):
             self._impl = FlatOptimizer(d.step, lr=lr, opt=kind, betas=kwargs.get('betas', (0.9, 0.999)),
-                                       eps=kwargs.get('eps', 1e-8), weight_decay=kwargs.get('weight_decay', 0.0))
+                                       eps=kwargs.get('eps', 1e-8), weight_decay=kwargs.get('weight_decay', 0.0),
+                                       guard=guard)
             self._flat = True
             self.param_groups = [dict(params=params, lr=lr)]
         else:
@@ -193,14 +240,17 @@ class _Switch(object):
 
 
 class Adam(_Switch):
-    """torch.optim.Adam(params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0) at the reference's call."""
+    """torch.optim.Adam(params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0) at the reference's call.
+    guard=True (keyword only): on the flat update, FlatOptimizer's guard -- a step whose error word is set is not applied.
+    On the torch fallback the keyword is accepted and ignored (torch's optimiser knows no error word)."""
 
     def __init__(self, params, lr=1e-3, **kwargs):
         super(Adam, self).__init__('adam', params, torch.optim.Adam, lr, kwargs)
 
 
 class SGD(_Switch):
-    """torch.optim.SGD(params, lr, momentum=0, weight_decay=0) at the reference's call."""
+    """torch.optim.SGD(params, lr, momentum=0, weight_decay=0) at the reference's call. guard=True: as for Adam (accepted
+    and ignored on the torch fallback)."""
 
     def __init__(self, params, lr=1e-3, **kwargs):
         super(SGD, self).__init__('sgd', params, torch.optim.SGD, lr, kwargs)

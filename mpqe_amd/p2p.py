@@ -157,7 +157,7 @@ class PeerExchange(object):
             ref = r.cpu()
         good = flags == 0 and bool(torch.allclose(got, ref, rtol=1e-6, atol=1e-6))
         if not good:
-            self.err.zero_()
+            ops.clear_flags(self.err)
             self.reason = 'self test: flags %d, max abs diff %.3g' % (flags, float((got - ref).abs().max()))
         return self._all_agree(good)
 

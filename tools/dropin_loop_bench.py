@@ -129,10 +129,12 @@ def loop(model, optimizer, steps, iters, warmup):
 class _FlatAdapter(object):
     """mpqe_amd.optim.FlatOptimizer behind torch.optim's two calls (one launch per step over the flat buffers)."""
 
+    guard = True            # (--unguarded: the update through the entry points that take no error word)
+
     def __init__(self, model, lr):
         from mpqe_amd.optim import FlatOptimizer
         self.model = model
-        self.opt = FlatOptimizer(model.dropin().step, lr=lr, opt='adam')
+        self.opt = FlatOptimizer(model.dropin().step, lr=lr, opt='adam', guard=self.guard)
 
     def zero_grad(self):
         self.opt.zero_grad()
@@ -187,7 +189,9 @@ if __name__ == '__main__':
     ap.add_argument('--module-iters', type=int, default=10)
     ap.add_argument('--optimizer', default='flat', choices=['flat', 'torch', 'none'])
     ap.add_argument('--profile', action='store_true', help='cProfile of the fused loop (host side)')
+    ap.add_argument('--unguarded', action='store_true', help='FlatOptimizer(guard=False)')
     a = ap.parse_args()
+    _FlatAdapter.guard = not a.unguarded
     torch.cuda.set_device(0)
     if a.profile:
         import cProfile
