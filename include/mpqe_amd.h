@@ -704,6 +704,51 @@ int mpqe_sample_negatives(const int64_t *cand, int64_t n_cand, const int64_t *of
                           const int64_t *qidx, int64_t nq, uint64_t seed, int64_t *out, int32_t *err,
                           void *stream);
 
+/* ---- the GQE baseline: bilinear metapath decoder + set intersection, one launch per formula batch ------------------
+ * reference: QueryEncoderDecoder.forward model.py:70-116, BilinearMetapathDecoder decoders.py:123-150, SetIntersection /
+ * SimpleSetIntersection decoders.py:270-319, DirectEncoder encoders.py:42-43 (added under ABI 7: entries only).
+ * The host compiles a formula into `prog_host`, MPQE_GQE_PROG_INTS int32:
+ *   [0] form: 0 = chain (model.py:78-83: the n = B + sum(L) target / negative rows pass through the matrices, row r is
+ *       scored against anchor row qrow[r]), 1 = intersection (model.py:84-116: the B queries' anchors pass through the
+ *       matrices, query q is scored against row q and rows B + neg_off[q] .. B + neg_off[q + 1] - 1)
+ *   [1] branches (1..3)   [2] aggregate over the branches: 0 mean, 1 min   [3] / [4] index of the pre / post matrix of the
+ *       intersection (-1: none -- SimpleSetIntersection)   [5] products after the intersection (0..3)
+ *   [6] table (mode) of the rows scored against   [8 + 5 b] table of branch b's ids, [9 + 5 b] its products (0..3),
+ *       [10 + 5 b ..] their codes; [24 ..] the codes of the products after the intersection.
+ *   A code is 2 * matrix index + T: T = 0 multiplies the row by M (decoders.py:145), T = 1 by M^T (project, decoders.py:150).
+ * tables_host / mats_host: host arrays of device pointers ([rows, dim] tables by mode; [dim, dim] matrices), 16-byte
+ * aligned. p_ids [branches, p_rows]: the ids that pass through the matrices (chain form: p_rows = n; intersection form:
+ * p_rows = B, n >= B); e_ids [e_rows] the other side (chain form: the B anchors; intersection form: e_rows = n). scores [n].
+ * dim: a multiple of 16 up to 256, one for every table (MPQE_ERR_UNSUPPORTED otherwise). The cosine and its eps are
+ * mpqe_cosine_fwd's; ids are checked as in mpqe_embed_l2norm_fwd (MPQE_FLAG_BAD_NODE_ID, the row becomes zeros), row map
+ * entries outside their range OR MPQE_FLAG_BAD_INDEX. save_states != 0 keeps in `workspace` (mpqe_gqe_workspace_bytes,
+ * 256-byte aligned) what mpqe_gqe_bwd reads: the input rows of every product, the rows under the aggregate and the
+ * scored rows, each [p_rows rounded up to 16, dim]; 0: inference, the workspace is not touched.
+ * mpqe_gqe_bwd (same arguments, the workspace of the forward): state gradients in one launch; grad_mats_host[m] +=
+ * the products' weight gradients site after site in programme order on mpqe_linear_bwd's fixed-order tiles;
+ * grad_tables_host[mode] += per looked-up row the sum of its entries in entry order (one writer per row). No float
+ * atomics: the same bits every run. NULL entries are not computed. Arguments are checked before any launch
+ * (MPQE_ERR_INVALID_ARG; a short workspace MPQE_ERR_WORKSPACE). */
+#define MPQE_GQE_PROG_INTS 32
+size_t mpqe_gqe_workspace_bytes(const int32_t *prog_host, int64_t p_rows, int64_t n, int64_t dim);
+int mpqe_gqe_fwd(const int32_t *prog_host, const float *const *tables_host, const int64_t *table_rows_host, int num_tables,
+                 const int64_t *node_map, int64_t node_map_len, const float *const *mats_host, int num_mats, int64_t dim,
+                 const int64_t *p_ids, int64_t p_rows, const int64_t *e_ids, int64_t e_rows, const int64_t *qrow,
+                 const int64_t *neg_off, int64_t n, float eps, int save_states, float *scores, void *workspace,
+                 size_t workspace_bytes, int32_t *err, void *stream);
+int mpqe_gqe_bwd(const int32_t *prog_host, const float *const *tables_host, const int64_t *table_rows_host, int num_tables,
+                 const int64_t *node_map, int64_t node_map_len, const float *const *mats_host, int num_mats, int64_t dim,
+                 const int64_t *p_ids, int64_t p_rows, const int64_t *e_ids, int64_t e_rows, const int64_t *qrow,
+                 const int64_t *neg_off, int64_t n, float eps, const float *grad_scores, float *const *grad_tables_host,
+                 float *const *grad_mats_host, void *workspace, size_t workspace_bytes, int32_t *err, void *stream);
+
+/* The aggregate of the intersection on its own (decoders.py:293-298, 313-318: torch.stack + agg_func(dim = 0)): out[i] =
+ * mean (agg 0) / min (agg 1) of x0[i], x1[i] and, unless NULL, x2[i]; count elements. Backward: the mean's gradient in equal
+ * parts, the minimum's to the first branch that holds it; NULL gradient pointers are not written. */
+int mpqe_branch_agg_fwd(const float *x0, const float *x1, const float *x2, int64_t count, int agg, float *out, void *stream);
+int mpqe_branch_agg_bwd(const float *x0, const float *x1, const float *x2, int64_t count, int agg, const float *grad_out,
+                        float *grad_x0, float *grad_x1, float *grad_x2, void *stream);
+
 /* Diagnostics, not part of the data path: while `device_buffer` (8 int64 per workgroup, num_blocks
  * workgroups) is set, every chain-kernel launch with at most num_blocks workgroups writes per workgroup the
  * device wall clock (100 MHz) at its phase boundaries [0..6] and HW_ID | XCC_ID << 32 in [7]; workgroup g of a

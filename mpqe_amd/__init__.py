@@ -3,15 +3,22 @@ hot path behind the reference's own module interface. See DESIGN.md."""
 from .graph import Formula, Graph, Query  # noqa: F401
 
 __all__ = ['Formula', 'Graph', 'Query', 'RGCNConv', 'RGCNEncoderDecoder', 'DirectEncoder',
-           'RGCNQueryDataset', 'MLPReadout', 'TargetMLPReadout']
+           'RGCNQueryDataset', 'MLPReadout', 'TargetMLPReadout', 'QueryEncoderDecoder', 'BilinearMetapathDecoder',
+           'SetIntersection', 'SimpleSetIntersection', 'get_metapath_decoder', 'get_intersection_decoder']
 
 
 def __getattr__(name):
     # torch-dependent modules are imported on first use so that `import mpqe_amd.graph`
     # (pure python) stays cheap
-    if name in ('RGCNConv', 'RGCNEncoderDecoder', 'MLPReadout', 'TargetMLPReadout'):
+    if name in ('RGCNConv', 'RGCNEncoderDecoder', 'MLPReadout', 'TargetMLPReadout', 'QueryEncoderDecoder'):
         from . import model
         return getattr(model, name)
+    if name in ('BilinearMetapathDecoder', 'SetIntersection', 'SimpleSetIntersection'):
+        from . import decoders
+        return getattr(decoders, name)
+    if name in ('get_metapath_decoder', 'get_intersection_decoder'):
+        from . import utils
+        return getattr(utils, name)
     if name == 'DirectEncoder':
         from .encoders import DirectEncoder
         return DirectEncoder

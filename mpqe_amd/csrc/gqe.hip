@@ -1,0 +1,751 @@
+// The GQE baseline (reference model.py:57-134, decoders.py:123-150, 270-319) as one launch per formula batch.
+//
+// The host compiles a formula into a programme of MPQE_GQE_PROG_INTS ints (include/mpqe_amd.h): up to three branches,
+// each a looked-up, L2-normalised embedding row taken through up to three [D, D] matrices; for two or three branches the
+// intersection (optional pre matrix + ReLU, mean / min over the branches, optional post matrix); up to three more
+// matrices; then the cosine against the rows of the other side. The rows that pass through the matrices are the
+// "P side", the plain embedding rows they are scored against the "E side":
+//   chain form   P rows = the n = B + sum(L) target / negative rows, E rows = the B anchors, pair r = (P r, E qrow[r])
+//   inter form   P rows = the B queries, E rows = the n target / negative rows, pair r = (P of r's query, E r); the
+//                negatives of query q are the rows B + neg_off[q] .. B + neg_off[q + 1] - 1
+// As in step_chain.h a workgroup owns 16 P rows and keeps their states in LDS (three tiles: two ping-pong, one for the
+// running aggregate / its gradient); a product is [16 rows] x [D] x [D] on v_mfma_f32_16x16x4_f32, lane l feeding
+// A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15], the matrix read straight from global memory in either
+// orientation. One lane's four consecutive k (one 16-byte LDS read) feed four MFMAs, MFMA u multiplying
+// k = 16 t + 4 (l >> 4) + u: the sum over k is re-ordered, in a fixed order.
+//
+// States the forward keeps for the backward (workspace, floats; Rp16 = P rows rounded up to 16):
+//   X[site]   [Rp16, D]  the input rows of every matrix product (a site = one use of one matrix; at most 16)
+//   T[b]      [Rp16, D]  the rows the aggregate is taken over (after the ReLU), per branch; only with >= 2 branches
+//   Pfin      [Rp16, D]  the rows that are scored
+// and the backward adds
+//   dY[site]  [Rp16, D]  the gradient of every product's output
+//   GE        [nb * Rp16 + n, D]  the gradient w.r.t. every looked-up, normalised row (branch sources, then E rows by pair)
+//   key       [nb * Rp + n] int64  (table, row) of every looked-up row
+// The state gradients are one launch (gqe_bwd_kernel). Matrix gradients are X^T . dY per site on the library's
+// fixed-order weight-gradient tiles (mpqe_linear_bwd, added into the caller's buffer site after site in programme order:
+// a matrix used at two sites gets both terms in that order). Entity-table rows: every looked-up row has one key; the
+// first entry of a key sums the entries of that key in entry order and adds the sum to the table gradient (one writer
+// per row, no float atomics: the same bits every run).
+#include <string.h>
+
+#include "gemm_core.h"
+
+#define GQ_ROWS 16
+#define GQ_MAXD 256
+#define GQ_LDXMAX (GQ_MAXD + 4)
+#define GQ_SITES 16
+#define GQ_SITE_PRE 9
+#define GQ_SITE_POST 12
+#define GQ_SITE_TAIL 13
+
+struct GqeDev {
+    int form, nb, agg, ntail, has_pre, has_post, D, save;
+    int bn[3], bT[3][3], tT[3];
+    const float *tab[4];           // tables of the branch sources, then of the E side
+    float *gtab[4];                // their gradients (backward; NULL = not wanted)
+    long long tab_rows[4];
+    int tmode[4];
+    const float *w[GQ_SITES];
+    long long x_off[GQ_SITES], dy_off[GQ_SITES];
+    long long t_off[3], pfin_off, ge_off, key_off;
+    const long long *node_map;
+    long long map_len;
+    const long long *p_ids, *e_ids, *qrow, *neg_off;
+    long long Rp, Rp16, Re, n;
+    float eps;
+    float *ws;
+    int32_t *err;
+};
+
+__device__ __forceinline__ long long gq_lookup(const long long *node_map, long long map_len, long long id,
+                                               long long table_rows, int32_t *err) {
+    if (!node_map) {
+        if (id < 0 || id >= table_rows) {
+            flag_error(err, MPQE_FLAG_BAD_NODE_ID);
+            return -1;
+        }
+        return id;
+    }
+    if (id < 0 || id >= map_len) {
+        flag_error(err, MPQE_FLAG_BAD_NODE_ID);
+        return -1;
+    }
+    const long long row = node_map[id];
+    if (row < 0 || row >= table_rows) {
+        flag_error(err, MPQE_FLAG_BAD_NODE_ID);
+        return -1;
+    }
+    return row;
+}
+
+// one table row, L2-normalised, 4 floats per lane (lanes with 4 * lane >= D hold zeros): the arithmetic of row_norm_store
+__device__ __forceinline__ f32x4 gq_norm_row(const float *tab, long long row, int D, int lane) {
+    f32x4 q = {0.f, 0.f, 0.f, 0.f};
+    const int c = lane * 4;
+    if (row >= 0 && c < D) q = gload4(tab + row * D + c);
+    const float ss = wave_sum(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    const float nrm = sqrtf(ss);
+    if (row >= 0) {
+        q[0] /= nrm; q[1] /= nrm; q[2] /= nrm; q[3] /= nrm;
+    }
+    return q;
+}
+
+// rows [i0, i0 + 16) of one id list -> tile (rows past `R` and bad ids: zeros)
+__device__ __forceinline__ void gq_gather(const GqeDev &G, float *tile, int LDX, const long long *ids, int slot, long long i0,
+                                          long long R) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int i = wave; i < GQ_ROWS; i += 4) {
+        const long long r = i0 + i;
+        long long row = -1;
+        if (r < R) row = gq_lookup(G.node_map, G.map_len, ids[r], G.tab_rows[slot], lane == 0 ? G.err : nullptr);
+        const f32x4 q = gq_norm_row(G.tab[slot], row, G.D, lane);
+        if (lane * 4 < G.D) *reinterpret_cast<f32x4 *>(tile + i * LDX + lane * 4) = q;
+    }
+}
+
+// dst = [relu](src . M) (T = 0) or src . M^T (T = 1), M [D, D] row-major in global memory
+__device__ __forceinline__ void gq_mm(const float *src, float *dst, const float *W, int D, int LDX, int T, int relu) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int j = lane & 15, kq = lane >> 4;
+    for (int cb = wave; cb < D / 16; cb += 4) {
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        const int col = cb * 16 + j;
+        for (int t = 0; t < D / 16; ++t) {
+            const int k0 = 16 * t + 4 * kq;
+            const f32x4 a = *reinterpret_cast<const f32x4 *>(src + j * LDX + k0);
+            f32x4 b;
+            if (T) {
+                b = gload4(W + (long long)col * D + k0);
+            } else {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) b[u] = gload1(W + (long long)(k0 + u) * D + col);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], b[u], acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            float v = acc[r];
+            if (relu) v = v > 0.f ? v : 0.f;
+            dst[(4 * kq + r) * LDX + col] = v;
+        }
+    }
+}
+
+// tile -> rows [i0, i0 + 16) of a [Rp16, D] state
+__device__ __forceinline__ void gq_store(const float *tile, int LDX, float *g, long long i0, int D) {
+    const int per = D / 4;
+    for (int e = threadIdx.x; e < GQ_ROWS * per; e += 256) {
+        const int i = e / per, c = (e % per) * 4;
+        *reinterpret_cast<f32x4 *>(g + (i0 + i) * D + c) = *reinterpret_cast<const f32x4 *>(tile + i * LDX + c);
+    }
+}
+__device__ __forceinline__ void gq_load(float *tile, int LDX, const float *g, long long i0, int D) {
+    const int per = D / 4;
+    for (int e = threadIdx.x; e < GQ_ROWS * per; e += 256) {
+        const int i = e / per, c = (e % per) * 4;
+        *reinterpret_cast<f32x4 *>(tile + i * LDX + c) = gload4(g + (i0 + i) * D + c);
+    }
+}
+
+// the E row of pair r, normalised (zeros for a bad id / a bad row map entry)
+__device__ __forceinline__ f32x4 gq_e_row(const GqeDev &G, long long r, int lane) {
+    long long row = -1;
+    if (r < G.n) {
+        long long e = r;
+        if (G.form == 0) {
+            e = G.qrow[r];
+            if (e < 0 || e >= G.Re) {
+                if (lane == 0) flag_error(G.err, MPQE_FLAG_BAD_INDEX);
+                e = -1;
+            }
+        }
+        if (e >= 0) row = gq_lookup(G.node_map, G.map_len, G.e_ids[e], G.tab_rows[3], lane == 0 ? G.err : nullptr);
+    }
+    return gq_norm_row(G.tab[3], row, G.D, lane);
+}
+
+// the negatives of query q: rows [lo, hi) of the pair list
+__device__ __forceinline__ void gq_neg_range(const GqeDev &G, long long q, int lane, long long &lo, long long &hi) {
+    lo = hi = 0;
+    const long long nneg = G.n - G.Rp;
+    if (!G.neg_off || q >= G.Rp) return;
+    long long a = G.neg_off[q], b = G.neg_off[q + 1];
+    if (a < 0 || b < a || b > nneg) {
+        if (lane == 0) flag_error(G.err, MPQE_FLAG_BAD_INDEX);
+        a = a < 0 ? 0 : (a > nneg ? nneg : a);
+        b = b < a ? a : (b > nneg ? nneg : b);
+    }
+    lo = G.Rp + a;
+    hi = G.Rp + b;
+}
+
+// the score of (p, e) by mpqe_cosine_fwd's definition; with g != NULL also the two gradients
+__device__ __forceinline__ float gq_cos(const f32x4 p, const f32x4 e, float eps, const float *g, f32x4 *gp, f32x4 *ge) {
+    const float dot = wave_sum(p[0] * e[0] + p[1] * e[1] + p[2] * e[2] + p[3] * e[3]);
+    const float qq = wave_sum(p[0] * p[0] + p[1] * p[1] + p[2] * p[2] + p[3] * p[3]);
+    const float tt = wave_sum(e[0] * e[0] + e[1] * e[1] + e[2] * e[2] + e[3] * e[3]);
+    const float rq = sqrtf(qq), rt = sqrtf(tt);
+    const float nq = fmaxf(rq, eps), nt = fmaxf(rt, eps);
+    if (!g) return dot / (nq * nt);
+    const float inv = 1.f / (nq * nt);
+    const float s = dot * inv;
+    const float kq = rq > eps ? s / (nq * nq) : 0.f;
+    const float kt = rt > eps ? s / (nt * nt) : 0.f;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        (*gp)[u] = *g * (e[u] * inv - kq * p[u]);
+        (*ge)[u] = *g * (p[u] * inv - kt * e[u]);
+    }
+    return s;
+}
+
+__global__ __launch_bounds__(256) void gqe_fwd_kernel(GqeDev G, float *__restrict__ scores) {
+    __shared__ __attribute__((aligned(16))) float lds[3 * GQ_ROWS * GQ_LDXMAX];
+    const int D = G.D, LDX = D + 4, per = D / 4;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long i0 = (long long)blockIdx.x * GQ_ROWS;
+    float *cur = lds, *nxt = lds + GQ_ROWS * LDX, *agg = lds + 2 * GQ_ROWS * LDX;
+
+    for (int b = 0; b < G.nb; ++b) {
+        gq_gather(G, cur, LDX, G.p_ids + (long long)b * G.Rp, b, i0, G.Rp);
+        __syncthreads();
+        for (int s = 0; s < G.bn[b]; ++s) {
+            const int site = 3 * b + s;
+            if (G.save) gq_store(cur, LDX, G.ws + G.x_off[site], i0, D);
+            gq_mm(cur, nxt, G.w[site], D, LDX, G.bT[b][s], 0);
+            __syncthreads();
+            float *t = cur; cur = nxt; nxt = t;
+        }
+        if (G.nb < 2) break;
+        if (G.has_pre) {
+            if (G.save) gq_store(cur, LDX, G.ws + G.x_off[GQ_SITE_PRE + b], i0, D);
+            gq_mm(cur, nxt, G.w[GQ_SITE_PRE + b], D, LDX, 1, 1);
+            __syncthreads();
+            float *t = cur; cur = nxt; nxt = t;
+        }
+        if (G.save) gq_store(cur, LDX, G.ws + G.t_off[b], i0, D);
+        for (int e = threadIdx.x; e < GQ_ROWS * per; e += 256) {
+            const int o = (e / per) * LDX + (e % per) * 4;
+            f32x4 v = *reinterpret_cast<const f32x4 *>(cur + o);
+            if (b > 0) {
+                const f32x4 a = *reinterpret_cast<const f32x4 *>(agg + o);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) v[u] = G.agg ? (v[u] < a[u] ? v[u] : a[u]) : a[u] + v[u];
+            }
+            if (!G.agg && b == G.nb - 1) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) v[u] /= (float)G.nb;
+            }
+            *reinterpret_cast<f32x4 *>(agg + o) = v;
+        }
+        __syncthreads();
+    }
+    if (G.nb >= 2) {
+        // (the aggregate becomes the current tile; the two others are free)
+        float *t = cur; cur = agg; agg = t;
+        if (G.has_post) {
+            if (G.save) gq_store(cur, LDX, G.ws + G.x_off[GQ_SITE_POST], i0, D);
+            gq_mm(cur, nxt, G.w[GQ_SITE_POST], D, LDX, 1, 0);
+            __syncthreads();
+            t = cur; cur = nxt; nxt = t;
+        }
+    }
+    for (int s = 0; s < G.ntail; ++s) {
+        const int site = GQ_SITE_TAIL + s;
+        if (G.save) gq_store(cur, LDX, G.ws + G.x_off[site], i0, D);
+        gq_mm(cur, nxt, G.w[site], D, LDX, G.tT[s], 0);
+        __syncthreads();
+        float *t = cur; cur = nxt; nxt = t;
+    }
+    if (G.save) gq_store(cur, LDX, G.ws + G.pfin_off, i0, D);
+
+    for (int i = wave; i < GQ_ROWS; i += 4) {
+        const long long q = i0 + i;
+        f32x4 p = {0.f, 0.f, 0.f, 0.f};
+        if (lane * 4 < D) p = *reinterpret_cast<const f32x4 *>(cur + i * LDX + lane * 4);
+        if (G.form == 0) {
+            if (q < G.n) {
+                const float s = gq_cos(p, gq_e_row(G, q, lane), G.eps, nullptr, nullptr, nullptr);
+                if (lane == 0) scores[q] = s;
+            }
+        } else if (q < G.Rp) {
+            long long lo, hi;
+            gq_neg_range(G, q, lane, lo, hi);
+            for (long long r = q;;) {
+                const float s = gq_cos(p, gq_e_row(G, r, lane), G.eps, nullptr, nullptr, nullptr);
+                if (lane == 0) scores[r] = s;
+                r = r == q ? lo : r + 1;
+                if (r >= hi) break;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void gqe_bwd_kernel(GqeDev G, const float *__restrict__ gs) {
+    __shared__ __attribute__((aligned(16))) float lds[3 * GQ_ROWS * GQ_LDXMAX];
+    const int D = G.D, LDX = D + 4, per = D / 4;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long i0 = (long long)blockIdx.x * GQ_ROWS;
+    float *cur = lds, *nxt = lds + GQ_ROWS * LDX, *ga = lds + 2 * GQ_ROWS * LDX;
+    float *GE = G.ws + G.ge_off;
+    const long long ge_e0 = (long long)G.nb * G.Rp16;      // first E entry row of GE
+
+    // scores: the gradient of the scored rows -> cur, of the E rows -> GE
+    for (int i = wave; i < GQ_ROWS; i += 4) {
+        const long long q = i0 + i;
+        f32x4 p = {0.f, 0.f, 0.f, 0.f}, gp = {0.f, 0.f, 0.f, 0.f};
+        if (lane * 4 < D) p = gload4(G.ws + G.pfin_off + q * D + lane * 4);
+        if (G.form == 0) {
+            if (q < G.n) {
+                f32x4 ge;
+                const float g = gs[q];
+                gq_cos(p, gq_e_row(G, q, lane), G.eps, &g, &gp, &ge);
+                if (lane * 4 < D) *reinterpret_cast<f32x4 *>(GE + (ge_e0 + q) * D + lane * 4) = ge;
+            }
+        } else if (q < G.Rp) {
+            long long lo, hi;
+            gq_neg_range(G, q, lane, lo, hi);
+            for (long long r = q;;) {
+                f32x4 g1, ge;
+                const float g = gs[r];
+                gq_cos(p, gq_e_row(G, r, lane), G.eps, &g, &g1, &ge);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) gp[u] += g1[u];
+                if (lane * 4 < D) *reinterpret_cast<f32x4 *>(GE + (ge_e0 + r) * D + lane * 4) = ge;
+                r = r == q ? lo : r + 1;
+                if (r >= hi) break;
+            }
+        }
+        if (lane * 4 < D) *reinterpret_cast<f32x4 *>(cur + i * LDX + lane * 4) = gp;
+    }
+    __syncthreads();
+
+    for (int s = G.ntail - 1; s >= 0; --s) {
+        const int site = GQ_SITE_TAIL + s;
+        gq_store(cur, LDX, G.ws + G.dy_off[site], i0, D);
+        gq_mm(cur, nxt, G.w[site], D, LDX, !G.tT[s], 0);
+        __syncthreads();
+        float *t = cur; cur = nxt; nxt = t;
+    }
+    if (G.nb >= 2) {
+        if (G.has_post) {
+            gq_store(cur, LDX, G.ws + G.dy_off[GQ_SITE_POST], i0, D);
+            gq_mm(cur, nxt, G.w[GQ_SITE_POST], D, LDX, 0, 0);
+            __syncthreads();
+            float *t = cur; cur = nxt; nxt = t;
+        }
+        float *t = cur; cur = ga; ga = t;       // ga: the gradient of the aggregate, kept over the branches
+    }
+    for (int b = 0; b < G.nb; ++b) {
+        if (G.nb >= 2) {
+            for (int e = threadIdx.x; e < GQ_ROWS * per; e += 256) {
+                const int i = e / per, c = (e % per) * 4;
+                const f32x4 g = *reinterpret_cast<const f32x4 *>(ga + i * LDX + c);
+                f32x4 tv[3];
+                for (int k = 0; k < G.nb; ++k) tv[k] = gload4(G.ws + G.t_off[k] + (i0 + i) * D + c);
+                f32x4 v;
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    float x;
+                    if (G.agg) {
+                        // min: the gradient goes to the first branch that holds the minimum
+                        int win = 0;
+                        float m = tv[0][u];
+                        for (int k = 1; k < G.nb; ++k)
+                            if (tv[k][u] < m) {
+                                m = tv[k][u];
+                                win = k;
+                            }
+                        x = win == b ? g[u] : 0.f;
+                    } else {
+                        x = g[u] / (float)G.nb;
+                    }
+                    if (G.has_pre && !(tv[b][u] > 0.f)) x = 0.f;
+                    v[u] = x;
+                }
+                *reinterpret_cast<f32x4 *>(cur + i * LDX + c) = v;
+            }
+            __syncthreads();
+            if (G.has_pre) {
+                gq_store(cur, LDX, G.ws + G.dy_off[GQ_SITE_PRE + b], i0, D);
+                gq_mm(cur, nxt, G.w[GQ_SITE_PRE + b], D, LDX, 0, 0);
+                __syncthreads();
+                float *t = cur; cur = nxt; nxt = t;
+            }
+        }
+        for (int s = G.bn[b] - 1; s >= 0; --s) {
+            const int site = 3 * b + s;
+            gq_store(cur, LDX, G.ws + G.dy_off[site], i0, D);
+            gq_mm(cur, nxt, G.w[site], D, LDX, !G.bT[b][s], 0);
+            __syncthreads();
+            float *t = cur; cur = nxt; nxt = t;
+        }
+        gq_store(cur, LDX, GE + (long long)b * G.Rp16 * D, i0, D);
+        __syncthreads();
+    }
+}
+
+// entry e of the looked-up rows: branch sources (b, i) in branch order, then the E row of every pair
+__device__ __forceinline__ void gq_entry(const GqeDev &G, long long e, int &slot, long long &id_pos, long long &ge_row) {
+    const long long np = (long long)G.nb * G.Rp;
+    if (e < np) {
+        slot = (int)(e / G.Rp);
+        id_pos = e;
+        ge_row = (long long)slot * G.Rp16 + e % G.Rp;
+    } else {
+        slot = 3;
+        id_pos = e - np;
+        ge_row = (long long)G.nb * G.Rp16 + (e - np);
+    }
+}
+
+__global__ __launch_bounds__(256) void gqe_keys_kernel(GqeDev G, long long n_ent) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n_ent) return;
+    int slot;
+    long long pos, ge_row;
+    gq_entry(G, e, slot, pos, ge_row);
+    long long key = -1;
+    if (G.gtab[slot]) {
+        long long id = -1;
+        bool ok = true;
+        if (slot < 3) id = G.p_ids[pos];
+        else if (G.form == 0) {
+            const long long q = G.qrow[pos];
+            ok = q >= 0 && q < G.Re;
+            if (ok) id = G.e_ids[q];
+        } else id = G.e_ids[pos];
+        if (ok) {
+            const long long row = gq_lookup(G.node_map, G.map_len, id, G.tab_rows[slot], nullptr);     // (flagged by the forward)
+            if (row >= 0) key = ((long long)G.tmode[slot] << 40) | row;
+        }
+    }
+    reinterpret_cast<long long *>(G.ws + G.key_off)[e] = key;
+}
+
+// y = v / |v|: dv = (g - y (y . g)) / |v| per entry; one wave per entry, the first entry of a key sums the key's entries
+__global__ __launch_bounds__(256) void gqe_rows_kernel(GqeDev G, long long n_ent) {
+    const long long e = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (e >= n_ent) return;
+    const long long *keys = reinterpret_cast<const long long *>(G.ws + G.key_off);
+    const long long key = keys[e];
+    if (key < 0) return;
+    float earlier = 0.f;
+    for (long long j0 = 0; j0 < e; j0 += 64) {
+        const long long j = j0 + lane;
+        if (j < e && keys[j] == key) earlier = 1.f;
+    }
+    if (wave_sum(earlier) > 0.f) return;
+    const int D = G.D, c = lane * 4;
+    const long long row = key & ((1ll << 40) - 1);
+    int slot0;
+    long long pos0, ger0;
+    gq_entry(G, e, slot0, pos0, ger0);
+    const float *GE = G.ws + G.ge_off;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (c < D) v = gload4(G.tab[slot0] + row * D + c);
+    const float nrm = sqrtf(wave_sum(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]));
+    const float inv = 1.f / nrm;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (long long j0 = e; j0 < n_ent; j0 += 64) {
+        const long long j = j0 + lane;
+        const float mine = (j < n_ent && keys[j] == key) ? 1.f : 0.f;
+        if (!(wave_sum(mine) > 0.f)) continue;
+        for (int l = 0; l < 64; ++l) {
+            if (!(__shfl(mine, l, 64) > 0.f)) continue;
+            int slot;
+            long long pos, ger;
+            gq_entry(G, j0 + l, slot, pos, ger);
+            f32x4 g = {0.f, 0.f, 0.f, 0.f};
+            if (c < D) g = gload4(GE + ger * D + c);
+            const float ydotg = wave_sum(v[0] * g[0] + v[1] * g[1] + v[2] * g[2] + v[3] * g[3]) * inv;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) acc[u] += (g[u] - (v[u] / nrm) * ydotg) * inv;
+        }
+    }
+    if (c < D) {
+        float *o = G.gtab[slot0] + row * D + c;
+        f32x4 old = *reinterpret_cast<const f32x4 *>(o);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) old[u] += acc[u];
+        *reinterpret_cast<f32x4 *>(o) = old;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ host side
+struct GqeHost {
+    GqeDev G;
+    int site_mat[GQ_SITES];       // matrix index of every site, -1 = unused
+    int site_T[GQ_SITES];
+    size_t lin_off, lin_bytes, total;
+};
+
+static int gqe_step(int code, int num_mats, int *mat, int *T) {
+    if (code < 0) return 1;
+    *mat = code >> 1;
+    *T = code & 1;
+    return num_mats >= 0 && *mat >= num_mats;
+}
+
+// programme + sizes -> device record and workspace layout; num_mats < 0: the sizes only (no bound on matrix indices)
+static int gqe_plan(const int32_t *prog, int num_tables, int num_mats, int64_t dim, int64_t p_rows, int64_t e_rows, int64_t n,
+                    GqeHost *H) {
+    if (!prog || p_rows < 1 || n < 1 || dim <= 0) return MPQE_ERR_INVALID_ARG;
+    if (dim % 16 != 0 || dim > GQ_MAXD) return MPQE_ERR_UNSUPPORTED;
+    if (p_rows >= (1ll << 31) || n >= (1ll << 31)) return MPQE_ERR_UNSUPPORTED;
+    memset(H, 0, sizeof(*H));
+    GqeDev &G = H->G;
+    G.form = prog[0];
+    G.nb = prog[1];
+    G.agg = prog[2];
+    G.ntail = prog[5];
+    G.D = (int)dim;
+    if (G.form < 0 || G.form > 1 || G.nb < 1 || G.nb > 3 || G.agg < 0 || G.agg > 1 || G.ntail < 0 || G.ntail > 3)
+        return MPQE_ERR_INVALID_ARG;
+    if (G.form == 0 ? (p_rows != n || e_rows < 1) : (e_rows != n || n < p_rows)) return MPQE_ERR_INVALID_ARG;
+    if (G.nb == 1 && (prog[3] >= 0 || prog[4] >= 0)) return MPQE_ERR_INVALID_ARG;
+    for (int s = 0; s < GQ_SITES; ++s) H->site_mat[s] = -1;
+    for (int t = 0; t < 4; ++t) {
+        const int mode = t < 3 ? (t < G.nb ? prog[8 + 5 * t] : 0) : prog[6];
+        if (num_tables >= 0 && (mode < 0 || mode >= num_tables)) return MPQE_ERR_INVALID_ARG;
+        G.tmode[t] = mode;
+    }
+    for (int b = 0; b < G.nb; ++b) {
+        G.bn[b] = prog[9 + 5 * b];
+        if (G.bn[b] < 0 || G.bn[b] > 3) return MPQE_ERR_INVALID_ARG;
+        for (int s = 0; s < G.bn[b]; ++s) {
+            if (gqe_step(prog[10 + 5 * b + s], num_mats, &H->site_mat[3 * b + s], &H->site_T[3 * b + s])) return MPQE_ERR_INVALID_ARG;
+            G.bT[b][s] = H->site_T[3 * b + s];
+        }
+    }
+    if (G.nb >= 2) {
+        if (prog[3] >= 0) {
+            if (num_mats >= 0 && prog[3] >= num_mats) return MPQE_ERR_INVALID_ARG;
+            G.has_pre = 1;
+            for (int b = 0; b < G.nb; ++b) {
+                H->site_mat[GQ_SITE_PRE + b] = prog[3];
+                H->site_T[GQ_SITE_PRE + b] = 1;
+            }
+        }
+        if (prog[4] >= 0) {
+            if (num_mats >= 0 && prog[4] >= num_mats) return MPQE_ERR_INVALID_ARG;
+            G.has_post = 1;
+            H->site_mat[GQ_SITE_POST] = prog[4];
+            H->site_T[GQ_SITE_POST] = 1;
+        }
+    }
+    for (int s = 0; s < G.ntail; ++s) {
+        if (gqe_step(prog[24 + s], num_mats, &H->site_mat[GQ_SITE_TAIL + s], &H->site_T[GQ_SITE_TAIL + s])) return MPQE_ERR_INVALID_ARG;
+        G.tT[s] = H->site_T[GQ_SITE_TAIL + s];
+    }
+    G.Rp = p_rows;
+    G.Rp16 = (p_rows + 15) / 16 * 16;
+    G.Re = e_rows;
+    G.n = n;
+    // workspace (floats; every block a multiple of 64 floats = 256 bytes)
+    const long long blk = G.Rp16 * dim;
+    long long off = 0;
+    for (int s = 0; s < GQ_SITES; ++s) {
+        G.x_off[s] = G.dy_off[s] = -1;
+        if (H->site_mat[s] < 0) continue;
+        G.x_off[s] = off;
+        G.dy_off[s] = off + blk;
+        off += 2 * blk;
+    }
+    for (int b = 0; b < 3; ++b) {
+        G.t_off[b] = -1;
+        if (G.nb >= 2 && b < G.nb) {
+            G.t_off[b] = off;
+            off += blk;
+        }
+    }
+    G.pfin_off = off;
+    off += blk;
+    G.ge_off = off;
+    off += (long long)align_up((size_t)((long long)G.nb * G.Rp16 + n) * (size_t)dim, 64);
+    G.key_off = off;
+    off += (long long)align_up((size_t)((long long)G.nb * p_rows + n) * 2, 64);
+    H->lin_off = (size_t)off * 4;
+    H->lin_bytes = mpqe_linear_bwd_workspace_bytes(p_rows, dim, dim);
+    H->total = H->lin_off + H->lin_bytes + 256;
+    return MPQE_OK;
+}
+
+extern "C" size_t mpqe_gqe_workspace_bytes(const int32_t *prog_host, int64_t p_rows, int64_t n, int64_t dim) {
+    GqeHost H;
+    if (!prog_host) return 0;
+    const int64_t e_rows = prog_host[0] == 0 ? 1 : n;
+    if (gqe_plan(prog_host, -1, -1, dim, p_rows, e_rows, n, &H) != MPQE_OK) return 0;
+    return H.total;
+}
+
+static int gqe_bind(GqeHost *H, const float *const *tables, const int64_t *table_rows, const int64_t *node_map,
+                    int64_t node_map_len, const float *const *mats, const int64_t *p_ids, const int64_t *e_ids,
+                    const int64_t *qrow, const int64_t *neg_off, float eps, void *workspace, int32_t *err) {
+    GqeDev &G = H->G;
+    if (!tables || !table_rows || !mats || !p_ids || !e_ids || node_map_len < 0) return MPQE_ERR_INVALID_ARG;
+    if (G.form == 0 && !qrow) return MPQE_ERR_INVALID_ARG;
+    if (G.form == 1 && G.n > G.Rp && !neg_off) return MPQE_ERR_INVALID_ARG;
+    for (int t = 0; t < 4; ++t) {
+        if (t < 3 && t >= G.nb) continue;
+        G.tab[t] = tables[G.tmode[t]];
+        G.tab_rows[t] = table_rows[G.tmode[t]];
+        if (!G.tab[t] || G.tab_rows[t] < 0 || (uintptr_t)G.tab[t] % 16 != 0) return MPQE_ERR_INVALID_ARG;
+    }
+    for (int s = 0; s < GQ_SITES; ++s) {
+        if (H->site_mat[s] < 0) continue;
+        G.w[s] = mats[H->site_mat[s]];
+        if (!G.w[s] || (uintptr_t)G.w[s] % 16 != 0) return MPQE_ERR_INVALID_ARG;
+    }
+    G.node_map = (const long long *)node_map;
+    G.map_len = node_map_len;
+    G.p_ids = (const long long *)p_ids;
+    G.e_ids = (const long long *)e_ids;
+    G.qrow = (const long long *)qrow;
+    G.neg_off = (const long long *)neg_off;
+    G.eps = eps;
+    G.ws = reinterpret_cast<float *>(workspace);
+    G.err = err;
+    return MPQE_OK;
+}
+
+extern "C" int mpqe_gqe_fwd(const int32_t *prog_host, const float *const *tables_host, const int64_t *table_rows_host,
+                            int num_tables, const int64_t *node_map, int64_t node_map_len, const float *const *mats_host,
+                            int num_mats, int64_t dim, const int64_t *p_ids, int64_t p_rows, const int64_t *e_ids,
+                            int64_t e_rows, const int64_t *qrow, const int64_t *neg_off, int64_t n, float eps, int save_states,
+                            float *scores, void *workspace, size_t workspace_bytes, int32_t *err, void *stream) {
+    if (num_tables < 1 || num_mats < 0 || !scores) return MPQE_ERR_INVALID_ARG;
+    GqeHost H;
+    int st = gqe_plan(prog_host, num_tables, num_mats, dim, p_rows, e_rows, n, &H);
+    if (st != MPQE_OK) return st;
+    st = gqe_bind(&H, tables_host, table_rows_host, node_map, node_map_len, mats_host, p_ids, e_ids, qrow, neg_off, eps,
+                  workspace, err);
+    if (st != MPQE_OK) return st;
+    H.G.save = save_states != 0;
+    if (H.G.save) {
+        if (!workspace || (uintptr_t)workspace % 256 != 0) return MPQE_ERR_INVALID_ARG;
+        if (workspace_bytes < H.total) return MPQE_ERR_WORKSPACE;
+    }
+    hipLaunchKernelGGL(gqe_fwd_kernel, dim3((unsigned)(H.G.Rp16 / GQ_ROWS)), dim3(256), 0, as_stream(stream), H.G, scores);
+    return mpqe_launch_status();
+}
+
+extern "C" int mpqe_gqe_bwd(const int32_t *prog_host, const float *const *tables_host, const int64_t *table_rows_host,
+                            int num_tables, const int64_t *node_map, int64_t node_map_len, const float *const *mats_host,
+                            int num_mats, int64_t dim, const int64_t *p_ids, int64_t p_rows, const int64_t *e_ids,
+                            int64_t e_rows, const int64_t *qrow, const int64_t *neg_off, int64_t n, float eps,
+                            const float *grad_scores, float *const *grad_tables_host, float *const *grad_mats_host,
+                            void *workspace, size_t workspace_bytes, int32_t *err, void *stream) {
+    if (num_tables < 1 || num_mats < 0 || !grad_scores || !grad_tables_host || !grad_mats_host) return MPQE_ERR_INVALID_ARG;
+    GqeHost H;
+    int st = gqe_plan(prog_host, num_tables, num_mats, dim, p_rows, e_rows, n, &H);
+    if (st != MPQE_OK) return st;
+    st = gqe_bind(&H, tables_host, table_rows_host, node_map, node_map_len, mats_host, p_ids, e_ids, qrow, neg_off, eps,
+                  workspace, err);
+    if (st != MPQE_OK) return st;
+    if (!workspace || (uintptr_t)workspace % 256 != 0) return MPQE_ERR_INVALID_ARG;
+    if (workspace_bytes < H.total) return MPQE_ERR_WORKSPACE;
+    GqeDev &G = H.G;
+    bool any_table = false;
+    for (int t = 0; t < 4; ++t) {
+        if (t < 3 && t >= G.nb) continue;
+        G.gtab[t] = grad_tables_host[G.tmode[t]];
+        if (G.gtab[t] && (uintptr_t)G.gtab[t] % 16 != 0) return MPQE_ERR_INVALID_ARG;
+        any_table = any_table || G.gtab[t];
+    }
+    for (int s = 0; s < GQ_SITES; ++s) {
+        float *g = H.site_mat[s] < 0 ? nullptr : grad_mats_host[H.site_mat[s]];
+        if (g && (uintptr_t)g % 16 != 0) return MPQE_ERR_INVALID_ARG;
+    }
+    hipStream_t s = as_stream(stream);
+    hipLaunchKernelGGL(gqe_bwd_kernel, dim3((unsigned)(G.Rp16 / GQ_ROWS)), dim3(256), 0, s, G, grad_scores);
+    if (any_table) {
+        const long long n_ent = (long long)G.nb * G.Rp + G.n;
+        hipLaunchKernelGGL(gqe_keys_kernel, dim3((unsigned)((n_ent + 255) / 256)), dim3(256), 0, s, G, n_ent);
+        hipLaunchKernelGGL(gqe_rows_kernel, dim3((unsigned)((n_ent + 3) / 4)), dim3(256), 0, s, G, n_ent);
+    }
+    st = mpqe_launch_status();
+    if (st != MPQE_OK) return st;
+    // matrix gradients, site after site (stream order = programme order): Y = X . M^T: gM = dY^T . X; Y = X . M: gM = X^T . dY
+    char *lin = reinterpret_cast<char *>(workspace) + H.lin_off;
+    for (int site = 0; site < GQ_SITES; ++site) {
+        if (H.site_mat[site] < 0) continue;
+        float *gm = grad_mats_host[H.site_mat[site]];
+        if (!gm) continue;
+        const float *X = G.ws + G.x_off[site], *dY = G.ws + G.dy_off[site];
+        const bool T = H.site_T[site] != 0;
+        st = mpqe_linear_bwd(T ? X : dY, p_rows, G.w[site], dim, nullptr, T ? dY : X, dim, dim, 0, 0, nullptr, gm, dim, nullptr,
+                             lin, H.lin_bytes, stream);
+        if (st != MPQE_OK) return st;
+    }
+    return MPQE_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ branch aggregate alone
+// out = mean / min of two or three equally shaped arrays, element by element (decoders.py:293-298, 313-318: torch.stack +
+// agg_func(dim=0)); the backward gives a minimum's gradient to the first branch that holds it. The composed path's op.
+__global__ __launch_bounds__(256) void branch_agg_fwd_kernel(const float *__restrict__ x0, const float *__restrict__ x1,
+                                                             const float *__restrict__ x2, long long count, int agg,
+                                                             float *__restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    const float a = x0[i], b = x1[i];
+    float v;
+    if (agg) {
+        v = b < a ? b : a;
+        if (x2) v = x2[i] < v ? x2[i] : v;
+    } else {
+        v = x2 ? (a + b + x2[i]) / 3.f : (a + b) / 2.f;
+    }
+    out[i] = v;
+}
+__global__ __launch_bounds__(256) void branch_agg_bwd_kernel(const float *__restrict__ x0, const float *__restrict__ x1,
+                                                             const float *__restrict__ x2, long long count, int agg,
+                                                             const float *__restrict__ g, float *__restrict__ g0,
+                                                             float *__restrict__ g1, float *__restrict__ g2) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    const float gi = g[i];
+    float r0, r1, r2;
+    if (agg) {
+        int win = 0;
+        float m = x0[i];
+        if (x1[i] < m) {
+            m = x1[i];
+            win = 1;
+        }
+        if (x2 && x2[i] < m) win = 2;
+        r0 = win == 0 ? gi : 0.f;
+        r1 = win == 1 ? gi : 0.f;
+        r2 = win == 2 ? gi : 0.f;
+    } else {
+        r0 = r1 = r2 = gi / (x2 ? 3.f : 2.f);
+    }
+    if (g0) g0[i] = r0;
+    if (g1) g1[i] = r1;
+    if (g2 && x2) g2[i] = r2;
+}
+
+extern "C" int mpqe_branch_agg_fwd(const float *x0, const float *x1, const float *x2, int64_t count, int agg, float *out,
+                                   void *stream) {
+    if (count < 0 || agg < 0 || agg > 1) return MPQE_ERR_INVALID_ARG;
+    if (count == 0) return MPQE_OK;
+    if (!x0 || !x1 || !out) return MPQE_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(branch_agg_fwd_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, as_stream(stream), x0, x1,
+                       x2, (long long)count, agg, out);
+    return mpqe_launch_status();
+}
+
+extern "C" int mpqe_branch_agg_bwd(const float *x0, const float *x1, const float *x2, int64_t count, int agg,
+                                   const float *grad_out, float *grad_x0, float *grad_x1, float *grad_x2, void *stream) {
+    if (count < 0 || agg < 0 || agg > 1) return MPQE_ERR_INVALID_ARG;
+    if (count == 0) return MPQE_OK;
+    if (!x0 || !x1 || !grad_out) return MPQE_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(branch_agg_bwd_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, as_stream(stream), x0, x1,
+                       x2, (long long)count, agg, grad_out, grad_x0, grad_x1, grad_x2);
+    return mpqe_launch_status();
+}

@@ -14,6 +14,19 @@ from .data_utils import RGCNQueryDataset
 from .ops import scatter_add, scatter_max, scatter_mean  # noqa: F401  (re-exported like the reference)
 
 
+def sample_negatives(graph, formula, queries, hard_negatives=False):
+    """One negative per query by the reference's three rules (model.py:120-127 = 466-476), on python's `random` stream in
+    the reference's order: shared by RGCNEncoderDecoder and QueryEncoderDecoder."""
+    if "inter" not in formula.query_type and hard_negatives:
+        raise Exception("Hard negative examples can only be used with "
+                        "intersection queries")
+    elif hard_negatives:
+        return [random.choice(query.hard_neg_samples) for query in queries]
+    elif formula.query_type == "1-chain":
+        return [random.choice(graph.full_lists[formula.target_mode]) for _ in queries]
+    return [random.choice(query.neg_samples) for query in queries]
+
+
 class RGCNConv(nn.Module):
     """reference: RGCNConv, model.py:206-310 (a vendored PyG <= 1.4 layer).
 
@@ -440,14 +453,7 @@ class RGCNEncoderDecoder(nn.Module):
 
     def sample_negatives(self, formula, queries, hard_negatives=False):
         """reference: model.py:466-476 (same python `random` stream, so the same draws)."""
-        if "inter" not in formula.query_type and hard_negatives:
-            raise Exception("Hard negative examples can only be used with "
-                            "intersection queries")
-        elif hard_negatives:
-            return [random.choice(query.hard_neg_samples) for query in queries]
-        elif formula.query_type == "1-chain":
-            return [random.choice(self.graph.full_lists[formula.target_mode]) for _ in queries]
-        return [random.choice(query.neg_samples) for query in queries]
+        return sample_negatives(self.graph, formula, queries, hard_negatives)
 
     def margin_loss(self, formula, queries, anchor_ids=None, var_ids=None, q_graphs=None,
                     hard_negatives=False, margin=1):
@@ -521,3 +527,200 @@ class TargetMLPReadout(nn.Module):
         if isinstance(x, tuple):
             x = x[0]
         return x
+
+
+# ------------------------------------------------------------------------------------------------ the GQE baseline
+def _anchor_ids(queries, slot):
+    return [query.anchor_nodes[slot] for query in queries]
+
+
+def gqe_plan(formula):
+    """(form, [(anchor slot or None = the target side, mode, [(relation, transposed)])], intersection mode or None,
+    [(relation, transposed)] after the intersection, mode of the other side): model.py:78-116 as data."""
+    from .graph import reverse_relation as rev
+    qt, rels = formula.query_type, formula.rels
+    if qt in ('1-chain', '2-chain', '3-chain'):
+        return 0, [(None, formula.target_mode, [(tuple(r), False) for r in rels])], None, [], formula.anchor_modes[0]
+    if qt == '3-chain_inter':
+        branches = [(0, formula.anchor_modes[0], [(rev(rels[1][0]), True)]),
+                    (1, formula.anchor_modes[1], [(rev(rels[1][1]), True)])]
+        return 1, branches, rels[0][-1], [(rev(rels[0]), True)], formula.target_mode
+    if qt not in ('2-inter', '3-inter', '3-inter_chain'):
+        raise ValueError('unknown query type %r' % (qt,))
+    branches = [(0, formula.anchor_modes[0], [(rev(rels[0]), True)])]
+    if len(rels[1]) == 2:
+        branches.append((1, formula.anchor_modes[1], [(rev(r), True) for r in rels[1][::-1]]))
+    else:
+        branches.append((1, formula.anchor_modes[1], [(rev(rels[1]), True)]))
+    if qt == '3-inter':
+        branches.append((2, formula.anchor_modes[2], [(rev(rels[2]), True)]))
+    return 1, branches, formula.target_mode, [], formula.target_mode
+
+
+class QueryEncoderDecoder(nn.Module):
+    """reference: QueryEncoderDecoder, model.py:57-134 -- GQE: a path decoder and an intersection decoder over entity
+    embeddings. Same constructor, forward() / margin_loss() signatures and state_dict keys (enc.*, path_dec.*,
+    inter_dec.*).
+
+    fused = True: forward() is ONE ops.gqe_scores call (mpqe_gqe_fwd / mpqe_gqe_bwd, csrc/gqe.hip) and margin_loss() one
+    for targets and negatives together. Taken with a DirectEncoder that has node_maps, a BilinearMetapathDecoder, a
+    SetIntersection / SimpleSetIntersection, parameters on the GPU and a shape the kernel covers (one D for every mode,
+    a multiple of 16 up to 256). Everything else -- and fused = False -- takes the composed path: the decoders' own
+    forward / project, one library call per product."""
+
+    def __init__(self, graph, enc, path_dec, inter_dec):
+        super(QueryEncoderDecoder, self).__init__()
+        self.enc = enc
+        self.path_dec = path_dec
+        self.inter_dec = inter_dec
+        self.graph = graph
+        self.fused = True
+        # one 4-byte D2H read per call to turn a bad id into IndexError (see ops.raise_on_flags)
+        self.validate = True
+        self._err = None
+
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state['_err'] = None
+        return state
+
+    # ------------------------------------------------------------------ helpers
+    def _device(self):
+        return next(self.parameters()).device
+
+    def _error_word(self, device):
+        if self._err is None or self._err.device != device:
+            self._err = ops.new_error_word(device)
+        return self._err
+
+    def _check(self):
+        if self.validate:
+            for err in (self._err, getattr(self.enc, '_err', None)):
+                if err is not None:
+                    ops.raise_on_flags(err)
+
+    def _plan(self, formula):
+        return gqe_plan(formula)
+
+    def _fused_ok(self, plan):
+        from .decoders import BilinearMetapathDecoder, SetIntersection, SimpleSetIntersection
+        enc = self.enc
+        if not self.fused or not (hasattr(enc, 'table') and getattr(enc, 'node_maps', None) is not None):
+            return False
+        if type(self.path_dec) is not BilinearMetapathDecoder or type(self.inter_dec) not in (SetIntersection,
+                                                                                            SimpleSetIntersection):
+            return False
+        if self._device().type != 'cuda':
+            return False
+        form, branches, imode, tail, emode = plan
+        dims = {enc.table(m).shape[1] for _, m, _ in branches} | {enc.table(emode).shape[1]}
+        mats = [self.path_dec.mats[r] for _, _, steps in branches for r, _ in steps] + [self.path_dec.mats[r] for r, _ in tail]
+        if imode is not None and isinstance(self.inter_dec, SetIntersection):
+            mats += [self.inter_dec.pre_mats[imode], self.inter_dec.post_mats[imode]]
+        if len(dims) != 1:
+            return False
+        D = next(iter(dims))
+        return ops.gqe_supported(D) and all(tuple(m.shape) == (D, D) for m in mats)
+
+    def _fused_scores(self, formula, queries, target_nodes, neg_nodes, neg_lengths, plan):
+        from .decoders import SetIntersection
+        form, branches, imode, tail, emode = plan
+        enc, device = self.enc, self._device()
+        modes, mats, mat_ids = [], [], {}
+
+        def table_of(mode):
+            if mode not in modes:
+                modes.append(mode)
+            return modes.index(mode)
+
+        def mat_of(param):
+            if id(param) not in mat_ids:
+                mat_ids[id(param)] = len(mats)
+                mats.append(param)
+            return mat_ids[id(param)]
+
+        B = len(queries)
+        tnodes = list(target_nodes) + (list(neg_nodes) if neg_nodes is not None else [])
+        n = len(tnodes)
+        lengths = np.asarray(neg_lengths, dtype=np.int64) if neg_nodes is not None else np.zeros(B, dtype=np.int64)
+        if neg_nodes is not None and (lengths.shape[0] != B or int(lengths.sum()) != n - B or (lengths < 0).any()):
+            raise ValueError('neg_lengths must hold one length per query and sum to len(neg_nodes)')
+        prog_branches = [(table_of(m), [(mat_of(self.path_dec.mats[r]), t) for r, t in steps]) for _, m, steps in branches]
+        prog_tail = [(mat_of(self.path_dec.mats[r]), t) for r, t in tail]
+        pre = post = -1
+        if imode is not None and isinstance(self.inter_dec, SetIntersection):
+            pre, post = mat_of(self.inter_dec.pre_mats[imode]), mat_of(self.inter_dec.post_mats[imode])
+        agg = self.inter_dec.agg_kind if imode is not None else 'mean'
+        prog = ops.gqe_programme(form, prog_branches, table_of(emode), agg, pre, post, prog_tail)
+        anchors = [_anchor_ids(queries, slot) for slot, _, _ in branches if slot is not None]
+        qrow = neg_off = None
+        if form == 0:
+            p_ids = np.asarray(tnodes, dtype=np.int64).reshape(1, n)
+            e_ids = np.asarray(_anchor_ids(queries, 0), dtype=np.int64)
+            qrow = np.concatenate([np.arange(B, dtype=np.int64), np.repeat(np.arange(B, dtype=np.int64), lengths)])
+        else:
+            p_ids = np.asarray(anchors, dtype=np.int64).reshape(len(branches), B)
+            e_ids = np.asarray(tnodes, dtype=np.int64)
+            if n > B:
+                neg_off = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+        # (one host-to-device copy for all the integer inputs of the call)
+        parts = [p_ids.reshape(-1), e_ids] + [a for a in (qrow, neg_off) if a is not None]
+        flat = torch.from_numpy(np.concatenate(parts)).to(device)
+        cuts = np.cumsum([0] + [p.shape[0] for p in parts])
+        views = [flat[cuts[k]:cuts[k + 1]] for k in range(len(parts))]
+        p_dev, e_dev = views[0].view(p_ids.shape), views[1]
+        rest = views[2:]
+        q_dev = rest.pop(0) if qrow is not None else None
+        o_dev = rest.pop(0) if neg_off is not None else None
+        return ops.gqe_scores(prog, [enc.table(m) for m in modes], mats, enc.node_maps, p_dev, e_dev, q_dev, o_dev, n,
+                              self._error_word(device))
+
+    # ------------------------------------------------------------------ the composed path (model.py:70-116 op by op)
+    def _composed_scores(self, formula, queries, target_nodes, neg_nodes, neg_lengths, plan):
+        form, branches, imode, tail, emode = plan
+        B = len(queries)
+        q_row = None
+        if neg_nodes is not None:
+            target_nodes = list(target_nodes) + list(neg_nodes)
+            lengths = torch.as_tensor(neg_lengths, dtype=torch.long)
+            q_row = torch.cat([torch.arange(B), torch.repeat_interleave(torch.arange(B), lengths)]).to(self._device())
+        target_embeds = self.enc(target_nodes, formula.target_mode)
+        if form == 0:
+            act = target_embeds.t()
+            for rel, _ in branches[0][2]:
+                act = ops.linear(act, self.path_dec.mats[rel].t())
+            anchors = self.enc(_anchor_ids(queries, 0), formula.anchor_modes[0]).t()
+            return ops.cosine(anchors, act, q_row=q_row)
+        embeds = []
+        for slot, mode, steps in branches:
+            e = self.enc(_anchor_ids(queries, slot), mode)
+            for rel, _ in steps:
+                e = self.path_dec.project(e, rel)
+            embeds.append(e)
+        q = self.inter_dec(embeds[0], embeds[1], imode, *embeds[2:])
+        for rel, _ in tail:
+            q = self.path_dec.project(q, rel)
+        return ops.cosine(q.t(), target_embeds.t(), q_row=q_row)
+
+    # ------------------------------------------------------------------ reference entry points
+    def forward(self, formula, queries, target_nodes, neg_nodes=None, neg_lengths=None):
+        plan = self._plan(formula)
+        if self._fused_ok(plan):
+            scores = self._fused_scores(formula, queries, target_nodes, neg_nodes, neg_lengths, plan)
+        else:
+            scores = self._composed_scores(formula, queries, target_nodes, neg_nodes, neg_lengths, plan)
+        self._check()
+        return scores
+
+    def sample_negatives(self, formula, queries, hard_negatives=False):
+        """reference: model.py:120-127 (same python `random` stream, so the same draws)."""
+        return sample_negatives(self.graph, formula, queries, hard_negatives)
+
+    def margin_loss(self, formula, queries, hard_negatives=False, margin=1):
+        """reference: model.py:119-134. The reference scores targets and negatives in two forward() calls; here one call
+        scores both (neg_lengths of 1), which computes the same numbers."""
+        neg_nodes = self.sample_negatives(formula, queries, hard_negatives)
+        targets = [query.target_node for query in queries]
+        B = len(queries)
+        scores = self.forward(formula, queries, targets, neg_nodes=neg_nodes, neg_lengths=[1] * B)
+        return ops.hinge(scores[:B], scores[B:], margin)

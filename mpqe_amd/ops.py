@@ -700,3 +700,126 @@ def l2_norms(params):
 def hinge(pos, neg, margin=1.0):
     """(a7) mean(clamp(margin - (pos - neg), min=0))"""
     return _Hinge.apply(pos, neg, float(margin))
+
+
+# --------------------------------------------------------------------------------------------- GQE baseline
+class _BranchAgg(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, kind, *xs):
+        if kind not in ('mean', 'min') or len(xs) not in (2, 3):
+            raise ValueError('branch_agg: mean / min over two or three branches')
+        xs = [_f(x, 'branch') for x in xs]
+        if any(x.shape != xs[0].shape for x in xs):
+            raise ValueError('branch_agg: branches of different shapes')
+        out = torch.empty_like(xs[0])
+        x2 = xs[2] if len(xs) == 3 else None
+        with torch.cuda.device(out.device):
+            _ck(lib().mpqe_branch_agg_fwd(_p(xs[0]), _p(xs[1]), _p(x2), out.numel(), int(kind == 'min'), _p(out), _stream()),
+                'mpqe_branch_agg_fwd')
+        ctx.kind = kind
+        ctx.save_for_backward(*xs)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        xs = ctx.saved_tensors
+        g = _f(g, 'grad')
+        gs = [torch.empty_like(x) if ctx.needs_input_grad[1 + k] else None for k, x in enumerate(xs)]
+        x2 = xs[2] if len(xs) == 3 else None
+        g2 = gs[2] if len(xs) == 3 else None
+        with torch.cuda.device(g.device):
+            _ck(lib().mpqe_branch_agg_bwd(_p(xs[0]), _p(xs[1]), _p(x2), g.numel(), int(ctx.kind == 'min'), _p(g), _p(gs[0]),
+                                          _p(gs[1]), _p(g2), _stream()), 'mpqe_branch_agg_bwd')
+        return (None,) + tuple(gs)
+
+
+def branch_agg(xs, kind):
+    """mean / min over two or three equally shaped tensors, element by element (reference decoders.py:293-298: torch.stack +
+    agg_func(dim=0)); a minimum's gradient goes to the first branch that holds it."""
+    return _BranchAgg.apply(kind, *xs)
+
+
+GQE_PROG_INTS = 32
+GQE_MAX_DIM = 256
+
+
+def gqe_programme(form, branches, e_table, agg='mean', pre=-1, post=-1, tail=()):
+    """The int32 programme of mpqe_gqe_fwd / bwd (include/mpqe_amd.h). branches: [(table index, [(matrix index, transposed)])],
+    tail: [(matrix index, transposed)] after the intersection; form 0 = chain, 1 = intersection."""
+    prog = np.full(GQE_PROG_INTS, -1, dtype=np.int32)
+    prog[0], prog[1], prog[2], prog[3], prog[4], prog[5], prog[6], prog[7] = (form, len(branches), int(agg == 'min'), pre, post,
+                                                                             len(tail), e_table, 0)
+    for b, (table, steps) in enumerate(branches):
+        prog[8 + 5 * b], prog[9 + 5 * b] = table, len(steps)
+        for s, (m, t) in enumerate(steps):
+            prog[10 + 5 * b + s] = 2 * m + int(bool(t))
+    for s, (m, t) in enumerate(tail):
+        prog[24 + s] = 2 * m + int(bool(t))
+    return prog
+
+
+def gqe_supported(dim):
+    return dim % 16 == 0 and 16 <= dim <= GQE_MAX_DIM
+
+
+class _GqeScores(torch.autograd.Function):
+    """One mpqe_gqe_fwd per forward, one mpqe_gqe_bwd per backward; the differentiable inputs are the entity tables and the
+    matrices the programme names (`params` = tables, then matrices)."""
+
+    @staticmethod
+    def forward(ctx, spec, num_tables, *params):
+        import ctypes
+        tables = [_f(t, 'embedding table') for t in params[:num_tables]]
+        mats = [_f(m, 'matrix') for m in params[num_tables:]]
+        D = tables[0].shape[1]
+        if any(t.dim() != 2 or t.shape[1] != D for t in tables) or any(tuple(m.shape) != (D, D) for m in mats):
+            raise ValueError('gqe_scores: every table [rows, D] and every matrix [D, D] with one D')
+        prog, node_map, p_ids, e_ids, qrow, neg_off, n, err, eps = spec
+        p_ids, e_ids = _i(p_ids, 'p_ids'), _i(e_ids, 'e_ids')
+        node_map = None if node_map is None else _i(node_map, 'node_map')
+        qrow = None if qrow is None else _i(qrow, 'qrow')
+        neg_off = None if neg_off is None else _i(neg_off, 'neg_off')
+        prog = np.ascontiguousarray(prog, dtype=np.int32)
+        dev = tables[0].device
+        p_rows = p_ids.shape[1]
+        save = any(ctx.needs_input_grad[2:])
+        L = lib()
+        tab_arr = (ctypes.c_void_p * len(tables))(*[_p(t) for t in tables])
+        rows_arr = (ctypes.c_int64 * len(tables))(*[t.shape[0] for t in tables])
+        mat_arr = (ctypes.c_void_p * max(len(mats), 1))(*[_p(m) for m in mats])
+        scores = torch.empty((n,), dtype=torch.float32, device=dev)
+        ws, wb = None, 0
+        with torch.cuda.device(dev):
+            if save:
+                wb = L.mpqe_gqe_workspace_bytes(prog.ctypes.data, p_rows, n, D)
+                if wb == 0:
+                    raise ValueError('gqe_scores: shape outside what the kernel covers')
+                ws = _ws(wb + 256, dev)
+            wp = None if ws is None else _capi._align256(ws.data_ptr())
+            args = (prog.ctypes.data, tab_arr, rows_arr, len(tables), _p(node_map), 0 if node_map is None else node_map.shape[0],
+                    mat_arr, len(mats), D, _p(p_ids), p_rows, _p(e_ids), e_ids.shape[0], _p(qrow), _p(neg_off), n, eps)
+            _ck(L.mpqe_gqe_fwd(*(args + (int(save), _p(scores), wp, wb, _p(err), _stream()))), 'mpqe_gqe_fwd')
+        ctx.call = (args, wp, wb, err, num_tables, (prog, tab_arr, rows_arr, mat_arr, ws, p_ids, e_ids, qrow, neg_off, node_map))
+        ctx.save_for_backward(*(tables + mats))
+        return scores
+
+    @staticmethod
+    def backward(ctx, gs):
+        import ctypes
+        args, wp, wb, err, num_tables, _keep = ctx.call
+        params = ctx.saved_tensors
+        gs = _f(gs, 'grad_scores')
+        grads = [torch.zeros_like(p) if ctx.needs_input_grad[2 + k] else None for k, p in enumerate(params)]
+        gt = (ctypes.c_void_p * num_tables)(*[_p(g) for g in grads[:num_tables]])
+        gm = (ctypes.c_void_p * max(len(params) - num_tables, 1))(*[_p(g) for g in grads[num_tables:]])
+        with torch.cuda.device(gs.device):
+            _ck(lib().mpqe_gqe_bwd(*(args + (_p(gs), gt, gm, wp, wb, _p(err), _stream()))), 'mpqe_gqe_bwd')
+        return (None, None) + tuple(grads)
+
+
+def gqe_scores(prog, tables, mats, node_map, p_ids, e_ids, qrow, neg_off, n, err=None, eps=1e-8):
+    """The GQE scores of one formula batch in one launch (mpqe_gqe_fwd, include/mpqe_amd.h), differentiable w.r.t. the
+    entity tables and the matrices. p_ids [branches, p_rows], e_ids [e_rows], qrow [n] (chain form) / neg_off [B + 1]
+    (intersection form with negatives) int64 on the device."""
+    spec = (prog, node_map, p_ids, e_ids, qrow, neg_off, int(n), err, float(eps))
+    return _GqeScores.apply(spec, len(tables), *(list(tables) + list(mats)))

@@ -9,6 +9,7 @@ type), loss.backward(), Adam; evaluation by ROC-AUC with one sampled negative pe
 
     python tools/train_synthetic.py --kg aifb --embed-dim 128 --batch-size 512 --steps 300            # GPU only
     python tools/train_synthetic.py --kg small --embed-dim 64 --batch-size 64 --steps 300 --oracle    # both, compared
+    python tools/train_synthetic.py --model gqe --kg small --embed-dim 64 --batch-size 64 --steps 300 # the GQE baseline
 
 Prints one JSON line: loss curves, AUC before / after training on held-out queries of the same KG (both sides).
 Only tests/ and this tool's --oracle leg use oracle/ (the checker, never the thing trained or shipped).
@@ -97,8 +98,15 @@ def main(argv=None):
     ap.add_argument('--dropin', action='store_true',
                     help="train through the reference's own loop body and entry points (model.margin_loss, loss.backward(): "
                          'mpqe_amd/dropin.py) instead of FusedTrainStep.pack / run')
+    ap.add_argument('--model', default='rgcn', choices=['rgcn', 'gqe'],
+                    help="gqe: the baseline QueryEncoderDecoder (the reference's --model gqe) through the reference's loop body")
+    ap.add_argument('--decoder', default='bilinear', help='gqe: metapath decoder (the reference\'s --decoder)')
+    ap.add_argument('--inter-decoder', default='mean', help='gqe: mean | min | mean-simple | min-simple (--inter_decoder)')
     args = ap.parse_args(argv)
-    out = run_dropin(args) if args.dropin else run(args)
+    if args.model == 'gqe':
+        out = run_gqe(args)
+    else:
+        out = run_dropin(args) if args.dropin else run(args)
     print(json.dumps(out))
     return out
 
@@ -311,6 +319,50 @@ def run_dropin(args):
     out.update(oracle_seconds=time.perf_counter() - t0, oracle_loss_first=olosses[0], oracle_loss_last20=float(np.mean(olosses[-20:])),
                oracle_auc_before=float(oauc0), oracle_auc_after=float(oauc1), oracle_loss_curve=olosses)
     return out
+
+
+def run_gqe(args):
+    """The GQE baseline (QueryEncoderDecoder, bilinear paths + set intersection) through the reference's loop body
+    (_reference_loop): margin_loss per batch on the fused kernels, loss.backward(), Adam; ROC-AUC before and after."""
+    import random
+    from mpqe_amd import evaluation, optim
+    from mpqe_amd.model import QueryEncoderDecoder
+    from mpqe_amd.utils import get_intersection_decoder, get_metapath_decoder
+    device = torch.device('cuda:0')
+    schema, graph, node_maps, rgcn, train, test = build(args, device)
+    graph.full_lists = {m: [int(v) for v in ids] for m, ids in graph.full_lists.items()}
+    dims = {m: args.embed_dim for m in schema.modes}
+    torch.manual_seed(args.seed)
+    model = QueryEncoderDecoder(graph, rgcn.enc, get_metapath_decoder(graph, dims, args.decoder),
+                                get_intersection_decoder(graph, dims, args.inter_decoder)).to(device)
+    tq = test_dict(test)
+    order = [qt for qt, _ in __import__('mpqe_amd.synthetic', fromlist=['FULL_MIX']).FULL_MIX]
+    query_types = list(dict.fromkeys(order))
+
+    def batches(qt):
+        rng = np.random.RandomState(args.seed + 11 + query_types.index(qt))
+        pos = [0] * len(train[qt])
+        while True:
+            fi = int(rng.randint(len(train[qt])))
+            f, qs = train[qt][fi]
+            lo = pos[fi] % len(qs)
+            pos[fi] = lo + args.batch_size
+            yield f, qs[lo:lo + args.batch_size]
+    iterators = {qt: batches(qt) for qt in query_types}
+    with torch.no_grad():
+        auc0, _ = evaluation.eval_auc_queries(tq, model, batch_size=128, seed=0)
+    opt = optim.Adam(model.parameters(), lr=args.lr)
+    random.seed(args.seed + 12)
+    t0 = time.perf_counter()
+    losses = _reference_loop(model, iterators, query_types, opt, args.steps,
+                             lambda batch, hard: model.margin_loss(*batch, hard_negatives=hard))
+    torch.cuda.synchronize()
+    train_s = time.perf_counter() - t0
+    with torch.no_grad():
+        auc1, _ = evaluation.eval_auc_queries(tq, model, batch_size=128, seed=0)
+    return dict(model='gqe', decoder=args.decoder, inter_decoder=args.inter_decoder, kg=args.kg, embed_dim=args.embed_dim,
+                batch_size=args.batch_size, steps=args.steps, train_seconds=train_s, loss_first=losses[0],
+                loss_last20=float(np.mean(losses[-20:])), auc_before=float(auc0), auc_after=float(auc1), loss_curve=losses)
 
 
 if __name__ == '__main__':
