@@ -278,9 +278,10 @@ extern "C" int mpqe_readout_bwd(int kind, const float *grad_out, const int32_t *
 }
 
 // ------------------------------------------------------------------------------------ torch_scatter-style reductions
-// Any index order. add/mean accumulate with fp32 atomics; max uses the ordered-int trick.
+// Any index order. add/mean accumulate with fp32 atomics; max uses the ordered-int trick: the branch goes by the sign
+// BIT, so that -0.0 (pattern INT_MIN as an int; the smallest of the negatives as an unsigned) goes with the negatives.
 __device__ __forceinline__ void atomic_max_float(float *addr, float v) {
-    if (v >= 0.f) atomicMax(reinterpret_cast<int *>(addr), __float_as_int(v));
+    if (__float_as_int(v) >= 0) atomicMax(reinterpret_cast<int *>(addr), __float_as_int(v));
     else atomicMin(reinterpret_cast<unsigned int *>(addr), __float_as_uint(v));
 }
 

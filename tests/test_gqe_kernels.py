@@ -9,7 +9,9 @@ checked on the CPU), so nothing is dropped -- the 5 % cap is met with 0. The sam
 cannot meet these tolerances (gqe_common.Problem.well_conditioned: the oracle's own op sequence in float32 must stay
 within half of them) -- judged from the oracle alone.
 Shapes: D 16 / 48 / 128 (one, three and eight column blocks: 48 leaves waves without a block), B 1 / 17 / 33 (a tile
-tail, more than one workgroup), ragged negative lengths 0 .. 20 (one above the 16-row tile), duplicate ids."""
+tail, more than one workgroup), ragged negative lengths 0 .. 20 (one above the 16-row tile), duplicate ids; at B 17 also
+D 64 (exactly one column block per wave), 80 (wave 0 walks two blocks, the others one) and 256 (the largest D: every lane
+holds data, each wave walks four blocks, the static LDS tile is full)."""
 import numpy as np
 import pytest
 
@@ -64,6 +66,10 @@ def _cases():
             for B in (1, 17, 33):
                 for inter in (('mean', 'min') if 'inter' in qt else ('mean',)):
                     out.append((qt, D, B, inter))
+    for qt in TYPES:
+        for D in (64, 80, 256):
+            for inter in (('mean', 'min') if 'inter' in qt else ('mean',)):
+                out.append((qt, D, 17, inter))
     return out
 
 
