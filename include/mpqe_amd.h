@@ -742,6 +742,20 @@ int mpqe_gqe_bwd(const int32_t *prog_host, const float *const *tables_host, cons
                  const int64_t *neg_off, int64_t n, float eps, const float *grad_scores, float *const *grad_tables_host,
                  float *const *grad_mats_host, void *workspace, size_t workspace_bytes, int32_t *err, void *stream);
 
+/* The rows a programme scores, alone (answering a query: every entity of a mode is a candidate, mpqe_rank_entities does
+ * the scoring). The programme's P side exactly as mpqe_gqe_fwd runs it -- lookup, L2 normalisation, the branch products,
+ * the intersection, the products after it -- and the rows the forward would score written to out [p_rows, dim] (16-byte
+ * aligned; exactly p_rows rows): the forward's arithmetic, instruction for instruction. No E side ([6] of the programme
+ * is not read), no workspace, no states. p_ids [branches, p_rows], or NULL with ONE branch: P row r is row r of that
+ * branch's table, 0 <= r < p_rows <= its rows, without an id list or node_map -- a whole mode's table projected with no
+ * lookups. Bad ids as in the forward (MPQE_FLAG_BAD_NODE_ID, the looked-up row becomes zeros, the other rows are
+ * unaffected). Arguments are checked before any launch as in mpqe_gqe_fwd; p_ids == NULL with more than one branch or
+ * p_rows above the table's rows: MPQE_ERR_INVALID_ARG (added under ABI 7: an entry only). */
+int mpqe_gqe_embed(const int32_t *prog_host, const float *const *tables_host, const int64_t *table_rows_host, int num_tables,
+                   const int64_t *node_map, int64_t node_map_len, const float *const *mats_host, int num_mats, int64_t dim,
+                   const int64_t *p_ids /* [branches, p_rows], or NULL */, int64_t p_rows, float *out /* [p_rows, dim] */,
+                   int32_t *err, void *stream);
+
 /* The aggregate of the intersection on its own (decoders.py:293-298, 313-318: torch.stack + agg_func(dim = 0)): out[i] =
  * mean (agg 0) / min (agg 1) of x0[i], x1[i] and, unless NULL, x2[i]; count elements. Backward: the mean's gradient in equal
  * parts, the minimum's to the first branch that holds it; NULL gradient pointers are not written. */

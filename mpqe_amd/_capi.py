@@ -109,6 +109,7 @@ PROTOTYPES = {
     'mpqe_gqe_workspace_bytes': (Z, [P, L, L, L]),
     'mpqe_gqe_fwd': (I, [P, P, P, I, P, L, P, I, L, P, L, P, L, P, P, L, F, I, P, P, Z, P, P]),
     'mpqe_gqe_bwd': (I, [P, P, P, I, P, L, P, I, L, P, L, P, L, P, P, L, F, P, P, P, P, Z, P, P]),
+    'mpqe_gqe_embed': (I, [P, P, P, I, P, L, P, I, L, P, L, P, P, P]),
     'mpqe_branch_agg_fwd': (I, [P, P, P, L, I, P, P]),
     'mpqe_branch_agg_bwd': (I, [P, P, P, L, I, P, P, P, P, P]),
     'mpqe_debug_chain_stamps': (None, [P, Z]),

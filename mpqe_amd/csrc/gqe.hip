@@ -92,14 +92,14 @@ __device__ __forceinline__ f32x4 gq_norm_row(const float *tab, long long row, in
     return q;
 }
 
-// rows [i0, i0 + 16) of one id list -> tile (rows past `R` and bad ids: zeros)
+// rows [i0, i0 + 16) of one id list -> tile (rows past `R` and bad ids: zeros); ids == NULL: row r of the table itself
 __device__ __forceinline__ void gq_gather(const GqeDev &G, float *tile, int LDX, const long long *ids, int slot, long long i0,
                                           long long R) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int i = wave; i < GQ_ROWS; i += 4) {
         const long long r = i0 + i;
         long long row = -1;
-        if (r < R) row = gq_lookup(G.node_map, G.map_len, ids[r], G.tab_rows[slot], lane == 0 ? G.err : nullptr);
+        if (r < R) row = ids ? gq_lookup(G.node_map, G.map_len, ids[r], G.tab_rows[slot], lane == 0 ? G.err : nullptr) : r;
         const f32x4 q = gq_norm_row(G.tab[slot], row, G.D, lane);
         if (lane * 4 < G.D) *reinterpret_cast<f32x4 *>(tile + i * LDX + lane * 4) = q;
     }
@@ -202,31 +202,35 @@ __device__ __forceinline__ float gq_cos(const f32x4 p, const f32x4 e, float eps,
     return s;
 }
 
+// EMBED = 0: the forward. EMBED = 1 (mpqe_gqe_embed): the same P side, then the rows the forward would score go to
+// `scores` as [Rp, D] -- no E side, no states; G.p_ids == NULL (one branch): P row r is row r of the branch's table.
+template <int EMBED>
 __global__ __launch_bounds__(256) void gqe_fwd_kernel(GqeDev G, float *__restrict__ scores) {
     __shared__ __attribute__((aligned(16))) float lds[3 * GQ_ROWS * GQ_LDXMAX];
     const int D = G.D, LDX = D + 4, per = D / 4;
+    const bool save = !EMBED && G.save;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long i0 = (long long)blockIdx.x * GQ_ROWS;
     float *cur = lds, *nxt = lds + GQ_ROWS * LDX, *agg = lds + 2 * GQ_ROWS * LDX;
 
     for (int b = 0; b < G.nb; ++b) {
-        gq_gather(G, cur, LDX, G.p_ids + (long long)b * G.Rp, b, i0, G.Rp);
+        gq_gather(G, cur, LDX, G.p_ids ? G.p_ids + (long long)b * G.Rp : nullptr, b, i0, G.Rp);
         __syncthreads();
         for (int s = 0; s < G.bn[b]; ++s) {
             const int site = 3 * b + s;
-            if (G.save) gq_store(cur, LDX, G.ws + G.x_off[site], i0, D);
+            if (save) gq_store(cur, LDX, G.ws + G.x_off[site], i0, D);
             gq_mm(cur, nxt, G.w[site], D, LDX, G.bT[b][s], 0);
             __syncthreads();
             float *t = cur; cur = nxt; nxt = t;
         }
         if (G.nb < 2) break;
         if (G.has_pre) {
-            if (G.save) gq_store(cur, LDX, G.ws + G.x_off[GQ_SITE_PRE + b], i0, D);
+            if (save) gq_store(cur, LDX, G.ws + G.x_off[GQ_SITE_PRE + b], i0, D);
             gq_mm(cur, nxt, G.w[GQ_SITE_PRE + b], D, LDX, 1, 1);
             __syncthreads();
             float *t = cur; cur = nxt; nxt = t;
         }
-        if (G.save) gq_store(cur, LDX, G.ws + G.t_off[b], i0, D);
+        if (save) gq_store(cur, LDX, G.ws + G.t_off[b], i0, D);
         for (int e = threadIdx.x; e < GQ_ROWS * per; e += 256) {
             const int o = (e / per) * LDX + (e % per) * 4;
             f32x4 v = *reinterpret_cast<const f32x4 *>(cur + o);
@@ -247,7 +251,7 @@ __global__ __launch_bounds__(256) void gqe_fwd_kernel(GqeDev G, float *__restric
         // (the aggregate becomes the current tile; the two others are free)
         float *t = cur; cur = agg; agg = t;
         if (G.has_post) {
-            if (G.save) gq_store(cur, LDX, G.ws + G.x_off[GQ_SITE_POST], i0, D);
+            if (save) gq_store(cur, LDX, G.ws + G.x_off[GQ_SITE_POST], i0, D);
             gq_mm(cur, nxt, G.w[GQ_SITE_POST], D, LDX, 1, 0);
             __syncthreads();
             t = cur; cur = nxt; nxt = t;
@@ -255,12 +259,21 @@ __global__ __launch_bounds__(256) void gqe_fwd_kernel(GqeDev G, float *__restric
     }
     for (int s = 0; s < G.ntail; ++s) {
         const int site = GQ_SITE_TAIL + s;
-        if (G.save) gq_store(cur, LDX, G.ws + G.x_off[site], i0, D);
+        if (save) gq_store(cur, LDX, G.ws + G.x_off[site], i0, D);
         gq_mm(cur, nxt, G.w[site], D, LDX, G.tT[s], 0);
         __syncthreads();
         float *t = cur; cur = nxt; nxt = t;
     }
-    if (G.save) gq_store(cur, LDX, G.ws + G.pfin_off, i0, D);
+    if (save) gq_store(cur, LDX, G.ws + G.pfin_off, i0, D);
+    if (EMBED) {
+        // (the tail tile: rows past Rp are not stored)
+        for (int e = threadIdx.x; e < GQ_ROWS * per; e += 256) {
+            const int i = e / per, c = (e % per) * 4;
+            if (i0 + i < G.Rp)
+                *reinterpret_cast<f32x4 *>(scores + (i0 + i) * D + c) = *reinterpret_cast<const f32x4 *>(cur + i * LDX + c);
+        }
+        return;
+    }
 
     for (int i = wave; i < GQ_ROWS; i += 4) {
         const long long q = i0 + i;
@@ -585,12 +598,16 @@ extern "C" size_t mpqe_gqe_workspace_bytes(const int32_t *prog_host, int64_t p_r
 
 static int gqe_bind(GqeHost *H, const float *const *tables, const int64_t *table_rows, const int64_t *node_map,
                     int64_t node_map_len, const float *const *mats, const int64_t *p_ids, const int64_t *e_ids,
-                    const int64_t *qrow, const int64_t *neg_off, float eps, void *workspace, int32_t *err) {
+                    const int64_t *qrow, const int64_t *neg_off, float eps, void *workspace, int32_t *err,
+                    bool p_only = false) {
     GqeDev &G = H->G;
-    if (!tables || !table_rows || !mats || !p_ids || !e_ids || node_map_len < 0) return MPQE_ERR_INVALID_ARG;
-    if (G.form == 0 && !qrow) return MPQE_ERR_INVALID_ARG;
-    if (G.form == 1 && G.n > G.Rp && !neg_off) return MPQE_ERR_INVALID_ARG;
-    for (int t = 0; t < 4; ++t) {
+    if (!tables || !table_rows || !mats || node_map_len < 0) return MPQE_ERR_INVALID_ARG;
+    if (!p_only) {
+        if (!p_ids || !e_ids) return MPQE_ERR_INVALID_ARG;
+        if (G.form == 0 && !qrow) return MPQE_ERR_INVALID_ARG;
+        if (G.form == 1 && G.n > G.Rp && !neg_off) return MPQE_ERR_INVALID_ARG;
+    }
+    for (int t = 0; t < (p_only ? 3 : 4); ++t) {
         if (t < 3 && t >= G.nb) continue;
         G.tab[t] = tables[G.tmode[t]];
         G.tab_rows[t] = table_rows[G.tmode[t]];
@@ -630,7 +647,28 @@ extern "C" int mpqe_gqe_fwd(const int32_t *prog_host, const float *const *tables
         if (!workspace || (uintptr_t)workspace % 256 != 0) return MPQE_ERR_INVALID_ARG;
         if (workspace_bytes < H.total) return MPQE_ERR_WORKSPACE;
     }
-    hipLaunchKernelGGL(gqe_fwd_kernel, dim3((unsigned)(H.G.Rp16 / GQ_ROWS)), dim3(256), 0, as_stream(stream), H.G, scores);
+    hipLaunchKernelGGL((gqe_fwd_kernel<0>), dim3((unsigned)(H.G.Rp16 / GQ_ROWS)), dim3(256), 0, as_stream(stream), H.G, scores);
+    return mpqe_launch_status();
+}
+
+// the rows a programme scores, alone: the forward's P side with EMBED = 1 (no E side: the programme's [6] is not read)
+extern "C" int mpqe_gqe_embed(const int32_t *prog_host, const float *const *tables_host, const int64_t *table_rows_host,
+                              int num_tables, const int64_t *node_map, int64_t node_map_len, const float *const *mats_host,
+                              int num_mats, int64_t dim, const int64_t *p_ids, int64_t p_rows, float *out, int32_t *err,
+                              void *stream) {
+    if (num_tables < 1 || num_mats < 0 || !out || !prog_host) return MPQE_ERR_INVALID_ARG;
+    int32_t prog[MPQE_GQE_PROG_INTS];
+    memcpy(prog, prog_host, sizeof(prog));
+    prog[6] = prog[8];                  // (the plan checks an E table: branch 0's, which it checks anyway)
+    GqeHost H;
+    int st = gqe_plan(prog, num_tables, num_mats, dim, p_rows, p_rows, p_rows, &H);
+    if (st != MPQE_OK) return st;
+    st = gqe_bind(&H, tables_host, table_rows_host, p_ids ? node_map : nullptr, node_map_len, mats_host, p_ids, nullptr,
+                  nullptr, nullptr, 0.f, nullptr, err, true);
+    if (st != MPQE_OK) return st;
+    if ((uintptr_t)out % 16 != 0) return MPQE_ERR_INVALID_ARG;
+    if (!p_ids && (H.G.nb != 1 || p_rows > H.G.tab_rows[0])) return MPQE_ERR_INVALID_ARG;
+    hipLaunchKernelGGL((gqe_fwd_kernel<1>), dim3((unsigned)(H.G.Rp16 / GQ_ROWS)), dim3(256), 0, as_stream(stream), H.G, out);
     return mpqe_launch_status();
 }
 

@@ -82,7 +82,103 @@ class RGCNConv(nn.Module):
                                                      self.out_channels, self.num_relations)
 
 
-class RGCNEncoderDecoder(nn.Module):
+class _EntityRanking(object):
+    """Answering a query over ALL entities of the target mode, the part RGCNEncoderDecoder and QueryEncoderDecoder share:
+    the row <-> id maps of a mode (cached in self.__dict__['_row_ids'] / ['_maps_np'], which __getstate__ drops), the id
+    translation, the exclusion lists as CSR and the ops.rank_entities call. A model supplies the two operands."""
+
+    def _mode_rows(self, mode, device):
+        """(row -> global id [n] int64 on the device, rows below n that are no entity, the map on the host) of one mode, from
+        graph.full_lists[mode] through enc.node_maps; built once per mode. n = 1 + the last row that is an entity: the
+        tables carry a spare row at the end (data_utils.make_feature_modules), which is never ranked."""
+        cache = self.__dict__.get('_row_ids')
+        if cache is None:
+            cache = self.__dict__['_row_ids'] = {}
+        hit = cache.get(mode)
+        if hit is not None and hit[0].device == device:
+            return hit
+        ids = np.asarray(list(self.graph.full_lists[mode]), dtype=np.int64)
+        maps = self._maps_host()
+        if ids.size == 0 or ids.min() < 0 or ids.max() >= maps.shape[0]:
+            raise IndexError('mpqe_amd: full_lists[%r] is empty or holds ids outside node_maps' % (mode,))
+        rows = maps[ids]
+        if rows.min() < 0 or rows.max() >= self.enc.table(mode).shape[0]:
+            raise IndexError('mpqe_amd: full_lists[%r] holds ids that are not of this mode' % (mode,))
+        row_ids = np.full(int(rows.max()) + 1, -1, dtype=np.int64)
+        row_ids[rows] = ids
+        hit = (torch.from_numpy(row_ids).to(device), np.nonzero(row_ids < 0)[0].astype(np.int64), row_ids)
+        cache[mode] = hit
+        return hit
+
+    def _maps_host(self):
+        # (ONE host copy of node_maps, shared by the row maps of every mode and by the id translation of every call)
+        m = self.__dict__.get('_maps_np')
+        if m is None:
+            m = self.__dict__['_maps_np'] = self.enc.node_maps.detach().cpu().numpy()
+        return m
+
+    def _rank_rows(self, formula, queries, target_nodes, exclude, k, operands):
+        """Every entity of formula.target_mode ranked for each query: (ids [B, k] or None, scores, ranks [B] or None).
+        operands(n) -> (q [B, D], candidates [n, D]): the two sides of ops.rank_entities over the mode's first n rows."""
+        enc = self.enc
+        if not (hasattr(enc, 'table') and getattr(enc, 'node_maps', None) is not None):
+            raise NotImplementedError('answering a query needs the entity tables (DirectEncoder with node_maps)')
+        device = self._device()
+        B = len(queries)
+        mode = formula.target_mode
+        row_ids, holes, row_ids_host = self._mode_rows(mode, device)
+        n = row_ids.shape[0]
+        err = self._error_word(device)
+        maps_host = self._maps_host()
+
+        def rows_of(ids):
+            # an id of another mode (node_maps gives it a row of ITS table), of no mode or outside node_maps becomes row n:
+            # outside the ranked rows, so the kernel flags it and _check raises
+            ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+            inside = (ids >= 0) & (ids < maps_host.shape[0])
+            cand = np.where(inside, maps_host[np.where(inside, ids, 0)], -1)
+            ok = (cand >= 0) & (cand < n)
+            ok &= row_ids_host[np.where(ok, cand, 0)] == ids
+            return np.where(ok, cand, n)
+
+        target_rows = None
+        if target_nodes is not None:
+            t = target_nodes.detach().cpu().numpy() if torch.is_tensor(target_nodes) else target_nodes
+            target_rows = torch.from_numpy(rows_of(t)).to(device)
+            if target_rows.shape[0] != B:
+                raise ValueError('one target per query')
+        csr = None
+        if exclude is not None:
+            if len(exclude) != B:
+                raise ValueError('exclude must hold one id list per query')
+            # one translation and one sort for the whole batch: keys (query, row), unique, then the segment bounds
+            lens = np.fromiter((len(e) for e in exclude), dtype=np.int64, count=B)
+            flat = np.fromiter((x for e in exclude for x in e), dtype=np.int64, count=int(lens.sum()))
+            rows = np.concatenate([rows_of(flat), np.tile(holes, B)])
+            owner = np.concatenate([np.repeat(np.arange(B, dtype=np.int64), lens),
+                                    np.repeat(np.arange(B, dtype=np.int64), holes.size)])
+            keys = np.unique(owner * (n + 1) + rows)
+            off = np.searchsorted(keys, np.arange(B + 1, dtype=np.int64) * (n + 1)).astype(np.int64)
+            csr = (torch.from_numpy(off), torch.from_numpy(keys % (n + 1)))
+        elif holes.size:
+            # rows of the table that are no entity: the same list for every query, kept on the device for the LAST batch size
+            # seen per mode (one entry per mode: an evaluation loop's ragged last batch rebuilds it once, nothing accumulates)
+            cache = self.__dict__['_row_ids']
+            hit = cache.get(('holes', mode))
+            if hit is None or hit[0] != B or hit[1][0].device != device:
+                off = torch.arange(B + 1, dtype=torch.int64) * holes.size
+                hit = cache[('holes', mode)] = (B, (off.to(device), torch.from_numpy(np.tile(holes, B)).to(device)))
+            csr = hit[1]
+        q, table = operands(n)
+        topr, tops, rank, _ = ops.rank_entities(q, table, target_rows, csr, k, err=err)
+        self._check()
+        ids = None
+        if topr is not None:
+            ids = torch.where(topr >= 0, row_ids[topr.clamp(min=0)], topr)
+        return ids, tops, rank
+
+
+class RGCNEncoderDecoder(nn.Module, _EntityRanking):
     """reference: RGCNEncoderDecoder, model.py:313-494."""
 
     def __init__(self, graph, enc, readout='mp', scatter_op='add', dropout=0, weight_decay=1e-3,
@@ -331,36 +427,6 @@ class RGCNEncoderDecoder(nn.Module):
         return scores
 
     # ------------------------------------------------------------------ answering a query (no counterpart in the reference)
-    def _mode_rows(self, mode, device):
-        """(row -> global id [n] int64 on the device, rows below n that are no entity, the map on the host) of one mode, from
-        graph.full_lists[mode] through enc.node_maps; built once per mode. n = 1 + the last row that is an entity: the
-        tables carry a spare row at the end (data_utils.make_feature_modules), which is never ranked."""
-        cache = self.__dict__.get('_row_ids')
-        if cache is None:
-            cache = self.__dict__['_row_ids'] = {}
-        hit = cache.get(mode)
-        if hit is not None and hit[0].device == device:
-            return hit
-        ids = np.asarray(list(self.graph.full_lists[mode]), dtype=np.int64)
-        maps = self._maps_host()
-        if ids.size == 0 or ids.min() < 0 or ids.max() >= maps.shape[0]:
-            raise IndexError('mpqe_amd: full_lists[%r] is empty or holds ids outside node_maps' % (mode,))
-        rows = maps[ids]
-        if rows.min() < 0 or rows.max() >= self.enc.table(mode).shape[0]:
-            raise IndexError('mpqe_amd: full_lists[%r] holds ids that are not of this mode' % (mode,))
-        row_ids = np.full(int(rows.max()) + 1, -1, dtype=np.int64)
-        row_ids[rows] = ids
-        hit = (torch.from_numpy(row_ids).to(device), np.nonzero(row_ids < 0)[0].astype(np.int64), row_ids)
-        cache[mode] = hit
-        return hit
-
-    def _maps_host(self):
-        # (ONE host copy of node_maps, shared by the row maps of every mode and by the id translation of every call)
-        m = self.__dict__.get('_maps_np')
-        if m is None:
-            m = self.__dict__['_maps_np'] = self.enc.node_maps.detach().cpu().numpy()
-        return m
-
     def _query_embeddings(self, formula, queries, anchor_ids, var_ids, q_graphs):
         d = self.dropin()
         if d is not None and self._fused_covers(d, formula, len(queries)):
@@ -370,63 +436,10 @@ class RGCNEncoderDecoder(nn.Module):
         return self.encode(formula, queries, anchor_ids, var_ids, q_graphs)
 
     def _rank_all(self, formula, queries, target_nodes, exclude, k, anchor_ids, var_ids, q_graphs):
-        enc = self.enc
-        if not (hasattr(enc, 'table') and getattr(enc, 'node_maps', None) is not None):
-            raise NotImplementedError('answering a query needs the entity tables (DirectEncoder with node_maps)')
-        device = self._device()
-        B = len(queries)
-        mode = formula.target_mode
-        row_ids, holes, row_ids_host = self._mode_rows(mode, device)
-        n = row_ids.shape[0]
-        err = self._error_word(device)
-        maps_host = self._maps_host()
-
-        def rows_of(ids):
-            # an id of another mode (node_maps gives it a row of ITS table), of no mode or outside node_maps becomes row n:
-            # outside the ranked rows, so the kernel flags it and _check raises
-            ids = np.asarray(ids, dtype=np.int64).reshape(-1)
-            inside = (ids >= 0) & (ids < maps_host.shape[0])
-            cand = np.where(inside, maps_host[np.where(inside, ids, 0)], -1)
-            ok = (cand >= 0) & (cand < n)
-            ok &= row_ids_host[np.where(ok, cand, 0)] == ids
-            return np.where(ok, cand, n)
-
-        target_rows = None
-        if target_nodes is not None:
-            t = target_nodes.detach().cpu().numpy() if torch.is_tensor(target_nodes) else target_nodes
-            target_rows = torch.from_numpy(rows_of(t)).to(device)
-            if target_rows.shape[0] != B:
-                raise ValueError('one target per query')
-        csr = None
-        if exclude is not None:
-            if len(exclude) != B:
-                raise ValueError('exclude must hold one id list per query')
-            # one translation and one sort for the whole batch: keys (query, row), unique, then the segment bounds
-            lens = np.fromiter((len(e) for e in exclude), dtype=np.int64, count=B)
-            flat = np.fromiter((x for e in exclude for x in e), dtype=np.int64, count=int(lens.sum()))
-            rows = np.concatenate([rows_of(flat), np.tile(holes, B)])
-            owner = np.concatenate([np.repeat(np.arange(B, dtype=np.int64), lens),
-                                    np.repeat(np.arange(B, dtype=np.int64), holes.size)])
-            keys = np.unique(owner * (n + 1) + rows)
-            off = np.searchsorted(keys, np.arange(B + 1, dtype=np.int64) * (n + 1)).astype(np.int64)
-            csr = (torch.from_numpy(off), torch.from_numpy(keys % (n + 1)))
-        elif holes.size:
-            # rows of the table that are no entity: the same list for every query, kept on the device for the LAST batch size
-            # seen per mode (one entry per mode: an evaluation loop's ragged last batch rebuilds it once, nothing accumulates)
-            cache = self.__dict__['_row_ids']
-            hit = cache.get(('holes', mode))
-            if hit is None or hit[0] != B or hit[1][0].device != device:
-                off = torch.arange(B + 1, dtype=torch.int64) * holes.size
-                hit = cache[('holes', mode)] = (B, (off.to(device), torch.from_numpy(np.tile(holes, B)).to(device)))
-            csr = hit[1]
-        q = self._query_embeddings(formula, queries, anchor_ids, var_ids, q_graphs)
-        table = enc.table(mode).detach()[:n]
-        topr, tops, rank, _ = ops.rank_entities(q, table, target_rows, csr, k, err=err)
-        self._check()
-        ids = None
-        if topr is not None:
-            ids = torch.where(topr >= 0, row_ids[topr.clamp(min=0)], topr)
-        return ids, tops, rank
+        def operands(n):
+            q = self._query_embeddings(formula, queries, anchor_ids, var_ids, q_graphs)
+            return q, self.enc.table(formula.target_mode).detach()[:n]
+        return self._rank_rows(formula, queries, target_nodes, exclude, k, operands)
 
     def answer(self, formula, queries, k=10, exclude=None, anchor_ids=None, var_ids=None, q_graphs=None):
         """The k entities of formula.target_mode the model proposes for each query, best first:
@@ -557,7 +570,7 @@ def gqe_plan(formula):
     return 1, branches, formula.target_mode, [], formula.target_mode
 
 
-class QueryEncoderDecoder(nn.Module):
+class QueryEncoderDecoder(nn.Module, _EntityRanking):
     """reference: QueryEncoderDecoder, model.py:57-134 -- GQE: a path decoder and an intersection decoder over entity
     embeddings. Same constructor, forward() / margin_loss() signatures and state_dict keys (enc.*, path_dec.*,
     inter_dec.*).
@@ -566,7 +579,17 @@ class QueryEncoderDecoder(nn.Module):
     for targets and negatives together. Taken with a DirectEncoder that has node_maps, a BilinearMetapathDecoder, a
     SetIntersection / SimpleSetIntersection, parameters on the GPU and a shape the kernel covers (one D for every mode,
     a multiple of 16 up to 256). Everything else -- and fused = False -- takes the composed path: the decoders' own
-    forward / project, one library call per product."""
+    forward / project, one library call per product.
+
+    answer() / rank_targets() (no counterpart in the reference) score every entity of the target mode in one
+    ops.rank_entities call, as on RGCNEncoderDecoder. An intersection formula's B query embeddings come from
+    ops.gqe_embed (mpqe_gqe_embed: the forward's P side alone) and are ranked against the mode's table. In a chain formula
+    the rows that pass through the matrices are the candidates, and they depend on the formula alone: the mode's table is
+    projected ONCE ([n, D], not once per query) and the B normalised anchors are ranked against it. In eval() mode that
+    projection is kept for the next call (one entry, self.__dict__['_cand']: copies and pickles drop it), keyed on the
+    chain's relations, the target mode, the device and data_ptr() / _version of the table and of every matrix used; in
+    train() mode it is always recomputed. Code that writes parameters through raw pointers (no version bump) must switch
+    to train() or set model.__dict__['_cand'] = None."""
 
     def __init__(self, graph, enc, path_dec, inter_dec):
         super(QueryEncoderDecoder, self).__init__()
@@ -582,7 +605,18 @@ class QueryEncoderDecoder(nn.Module):
     def __getstate__(self):
         state = self.__dict__.copy()
         state['_err'] = None
+        state['_row_ids'] = None        # (what answer() caches on the device: the row -> id maps, a chain's projected candidates)
+        state['_maps_np'] = None
+        state['_cand'] = None
         return state
+
+    def _apply(self, fn, *args, **kwargs):
+        # (.to() / .cuda() / .float(): the parameters move)
+        out = super(QueryEncoderDecoder, self)._apply(fn, *args, **kwargs)
+        self.__dict__['_row_ids'] = None
+        self.__dict__['_maps_np'] = None
+        self.__dict__['_cand'] = None
+        return out
 
     # ------------------------------------------------------------------ helpers
     def _device(self):
@@ -622,10 +656,10 @@ class QueryEncoderDecoder(nn.Module):
         D = next(iter(dims))
         return ops.gqe_supported(D) and all(tuple(m.shape) == (D, D) for m in mats)
 
-    def _fused_scores(self, formula, queries, target_nodes, neg_nodes, neg_lengths, plan):
+    def _programme(self, plan):
+        """(programme of mpqe_gqe_fwd / mpqe_gqe_embed, the modes of its tables, its matrices) of one plan."""
         from .decoders import SetIntersection
         form, branches, imode, tail, emode = plan
-        enc, device = self.enc, self._device()
         modes, mats, mat_ids = [], [], {}
 
         def table_of(mode):
@@ -639,19 +673,24 @@ class QueryEncoderDecoder(nn.Module):
                 mats.append(param)
             return mat_ids[id(param)]
 
-        B = len(queries)
-        tnodes = list(target_nodes) + (list(neg_nodes) if neg_nodes is not None else [])
-        n = len(tnodes)
-        lengths = np.asarray(neg_lengths, dtype=np.int64) if neg_nodes is not None else np.zeros(B, dtype=np.int64)
-        if neg_nodes is not None and (lengths.shape[0] != B or int(lengths.sum()) != n - B or (lengths < 0).any()):
-            raise ValueError('neg_lengths must hold one length per query and sum to len(neg_nodes)')
         prog_branches = [(table_of(m), [(mat_of(self.path_dec.mats[r]), t) for r, t in steps]) for _, m, steps in branches]
         prog_tail = [(mat_of(self.path_dec.mats[r]), t) for r, t in tail]
         pre = post = -1
         if imode is not None and isinstance(self.inter_dec, SetIntersection):
             pre, post = mat_of(self.inter_dec.pre_mats[imode]), mat_of(self.inter_dec.post_mats[imode])
         agg = self.inter_dec.agg_kind if imode is not None else 'mean'
-        prog = ops.gqe_programme(form, prog_branches, table_of(emode), agg, pre, post, prog_tail)
+        return ops.gqe_programme(form, prog_branches, table_of(emode), agg, pre, post, prog_tail), modes, mats
+
+    def _fused_scores(self, formula, queries, target_nodes, neg_nodes, neg_lengths, plan):
+        form, branches, imode, tail, emode = plan
+        enc, device = self.enc, self._device()
+        B = len(queries)
+        tnodes = list(target_nodes) + (list(neg_nodes) if neg_nodes is not None else [])
+        n = len(tnodes)
+        lengths = np.asarray(neg_lengths, dtype=np.int64) if neg_nodes is not None else np.zeros(B, dtype=np.int64)
+        if neg_nodes is not None and (lengths.shape[0] != B or int(lengths.sum()) != n - B or (lengths < 0).any()):
+            raise ValueError('neg_lengths must hold one length per query and sum to len(neg_nodes)')
+        prog, modes, mats = self._programme(plan)
         anchors = [_anchor_ids(queries, slot) for slot, _, _ in branches if slot is not None]
         qrow = neg_off = None
         if form == 0:
@@ -691,6 +730,11 @@ class QueryEncoderDecoder(nn.Module):
                 act = ops.linear(act, self.path_dec.mats[rel].t())
             anchors = self.enc(_anchor_ids(queries, 0), formula.anchor_modes[0]).t()
             return ops.cosine(anchors, act, q_row=q_row)
+        return ops.cosine(self._composed_query(queries, plan).t(), target_embeds.t(), q_row=q_row)
+
+    def _composed_query(self, queries, plan):
+        """[D, B]: an intersection formula's query embeddings from the decoders' own pieces (model.py:84-116)."""
+        form, branches, imode, tail, emode = plan
         embeds = []
         for slot, mode, steps in branches:
             e = self.enc(_anchor_ids(queries, slot), mode)
@@ -700,7 +744,7 @@ class QueryEncoderDecoder(nn.Module):
         q = self.inter_dec(embeds[0], embeds[1], imode, *embeds[2:])
         for rel, _ in tail:
             q = self.path_dec.project(q, rel)
-        return ops.cosine(q.t(), target_embeds.t(), q_row=q_row)
+        return q
 
     # ------------------------------------------------------------------ reference entry points
     def forward(self, formula, queries, target_nodes, neg_nodes=None, neg_lengths=None):
@@ -711,6 +755,79 @@ class QueryEncoderDecoder(nn.Module):
             scores = self._composed_scores(formula, queries, target_nodes, neg_nodes, neg_lengths, plan)
         self._check()
         return scores
+
+    # ------------------------------------------------------------------ answering a query (no counterpart in the reference)
+    def _chain_candidates(self, plan, n, project):
+        """[n, D]: the first n rows of the target mode's table as a chain formula scores them (normalised, then taken
+        through the chain's matrices). project(): computes them. In eval() mode the last result is kept (class docstring)."""
+        if self.training:
+            self.__dict__['_cand'] = None
+            return project()
+        steps = plan[1][0][2]
+        table = self.enc.table(plan[1][0][1])
+        used = [table] + [self.path_dec.mats[r] for r, _ in steps]
+        key = (tuple(r for r, _ in steps), plan[1][0][1], str(table.device), n, bool(self._fused_ok(plan)),
+               tuple((t.data_ptr(), t._version) for t in used))
+        hit = self.__dict__.get('_cand')
+        if hit is None or hit[0] != key:
+            hit = self.__dict__['_cand'] = (key, project())
+        return hit[1]
+
+    def _rank_operands(self, formula, queries, n):
+        """(q [B, D], candidates [n, D]) for ops.rank_entities: cos(q, candidate) is the score forward() gives the pair."""
+        plan = self._plan(formula)
+        form, branches, imode, tail, emode = plan
+        enc, device = self.enc, self._device()
+        err = self._error_word(device)
+        B = len(queries)
+        fused = self._fused_ok(plan)
+        if form == 1:
+            if fused:
+                prog, modes, mats = self._programme(plan)
+                p_ids = np.asarray([_anchor_ids(queries, slot) for slot, _, _ in branches], dtype=np.int64).reshape(-1, B)
+                q = ops.gqe_embed(prog, [enc.table(m) for m in modes], mats, enc.node_maps,
+                                  torch.from_numpy(p_ids).to(device), B, err)
+            else:
+                q = self._composed_query(queries, plan).t()
+            return q, enc.table(formula.target_mode).detach()[:n]
+        steps = branches[0][2]
+        table = enc.table(formula.target_mode).detach()
+
+        def project():
+            if fused:
+                prog, modes, mats = self._programme(plan)
+                return ops.gqe_embed(prog, [enc.table(m) for m in modes], mats, None, None, n, err)
+            act = ops.embed_l2norm(table, None, torch.arange(n, device=device), err)
+            for rel, _ in steps:
+                act = ops.linear(act, self.path_dec.mats[rel].detach().t())
+            return act
+        cand = self._chain_candidates(plan, n, project)
+        return enc(_anchor_ids(queries, 0), formula.anchor_modes[0]).t(), cand
+
+    def _rank_all(self, formula, queries, target_nodes, exclude, k):
+        return self._rank_rows(formula, queries, target_nodes, exclude, k, lambda n: self._rank_operands(formula, queries, n))
+
+    def answer(self, formula, queries, k=10, exclude=None):
+        """The k entities of formula.target_mode the model proposes for each query, best first:
+        (ids [B, k] int64 global entity ids, scores [B, k] float32), -1 / -inf past the last eligible entity. The score is
+        the one forward() gives a candidate. `exclude`: one list of entity ids per query that must not be returned.
+        Every entity of the mode is scored (mpqe_rank_entities); k <= ops.RANK_MAX_K."""
+        if k < 1:
+            raise ValueError('answer: k must be at least 1')
+        with torch.no_grad():
+            ids, scores, _ = self._rank_all(formula, queries, None, exclude, k)
+        return ids, scores
+
+    def rank_targets(self, formula, queries, target_nodes=None, exclude=None):
+        """ranks [B] int64: 1 + the number of entities of formula.target_mode, other than the target and those in
+        `exclude`, that the model places before each query's target (default: query.target_node); ties go to the entity
+        with the smaller table row. The target is never excluded, listed or not (the filtered setting passes every known
+        answer)."""
+        if target_nodes is None:
+            target_nodes = [query.target_node for query in queries]
+        with torch.no_grad():
+            _, _, rank = self._rank_all(formula, queries, target_nodes, exclude, 0)
+        return rank
 
     def sample_negatives(self, formula, queries, hard_negatives=False):
         """reference: model.py:120-127 (same python `random` stream, so the same draws)."""

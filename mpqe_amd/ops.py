@@ -823,3 +823,33 @@ def gqe_scores(prog, tables, mats, node_map, p_ids, e_ids, qrow, neg_off, n, err
     (intersection form with negatives) int64 on the device."""
     spec = (prog, node_map, p_ids, e_ids, qrow, neg_off, int(n), err, float(eps))
     return _GqeScores.apply(spec, len(tables), *(list(tables) + list(mats)))
+
+
+def gqe_embed(prog, tables, mats, node_map, p_ids, p_rows, err=None):
+    """The rows a GQE programme scores, [p_rows, D] float32 on the tables' device (mpqe_gqe_embed, include/mpqe_amd.h):
+    the P side of gqe_scores alone -- lookup, normalisation, the products, the intersection -- with the forward's
+    arithmetic. p_ids [branches, p_rows] int64 on the device, or None with one branch: row r of that branch's table is P
+    row r (no ids, no node_map). Inference only: the inputs are detached, nothing here is differentiated."""
+    import ctypes
+    tables = [_f(t.detach(), 'embedding table') for t in tables]
+    mats = [_f(m.detach(), 'matrix') for m in mats]
+    D = tables[0].shape[1]
+    if any(t.dim() != 2 or t.shape[1] != D for t in tables) or any(tuple(m.shape) != (D, D) for m in mats):
+        raise ValueError('gqe_embed: every table [rows, D] and every matrix [D, D] with one D')
+    p_rows = int(p_rows)
+    if p_ids is not None:
+        p_ids = _i(p_ids, 'p_ids')
+        if p_ids.dim() != 2 or p_ids.shape[1] != p_rows:
+            raise ValueError('gqe_embed: p_ids must be [branches, p_rows]')
+    node_map = None if node_map is None or p_ids is None else _i(node_map, 'node_map')
+    prog = np.ascontiguousarray(prog, dtype=np.int32)
+    dev = tables[0].device
+    tab_arr = (ctypes.c_void_p * len(tables))(*[_p(t) for t in tables])
+    rows_arr = (ctypes.c_int64 * len(tables))(*[t.shape[0] for t in tables])
+    mat_arr = (ctypes.c_void_p * max(len(mats), 1))(*[_p(m) for m in mats])
+    out = torch.empty((p_rows, D), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _ck(lib().mpqe_gqe_embed(prog.ctypes.data, tab_arr, rows_arr, len(tables), _p(node_map),
+                                 0 if node_map is None else node_map.shape[0], mat_arr, len(mats), D, _p(p_ids), p_rows,
+                                 _p(out), _p(err), _stream()), 'mpqe_gqe_embed')
+    return out

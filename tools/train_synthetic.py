@@ -321,21 +321,36 @@ def run_dropin(args):
     return out
 
 
-def run_gqe(args):
-    """The GQE baseline (QueryEncoderDecoder, bilinear paths + set intersection) through the reference's loop body
-    (_reference_loop): margin_loss per batch on the fused kernels, loss.backward(), Adam; ROC-AUC before and after."""
-    import random
-    from mpqe_amd import evaluation, optim
+def build_gqe(args, device):
+    """build() with the GQE baseline in the R-GCN model's place: the same KG, entity tables and queries."""
     from mpqe_amd.model import QueryEncoderDecoder
     from mpqe_amd.utils import get_intersection_decoder, get_metapath_decoder
-    device = torch.device('cuda:0')
     schema, graph, node_maps, rgcn, train, test = build(args, device)
     graph.full_lists = {m: [int(v) for v in ids] for m, ids in graph.full_lists.items()}
     dims = {m: args.embed_dim for m in schema.modes}
     torch.manual_seed(args.seed)
     model = QueryEncoderDecoder(graph, rgcn.enc, get_metapath_decoder(graph, dims, args.decoder),
                                 get_intersection_decoder(graph, dims, args.inter_decoder)).to(device)
+    return schema, graph, node_maps, model, train, test
+
+
+def known_answers(args, schema, tq):
+    """{query: every entity the KG's adjacency gives as an answer}: what the filtered ranking metrics exclude."""
+    from mpqe_amd import synthetic
+    adj = synthetic.make_adjacency(schema, degree=args.degree, seed=args.seed)
+    return {q: synthetic._answers(adj, f, list(q.anchor_nodes))[0] for f in tq for q in tq[f]}
+
+
+def run_gqe(args):
+    """The GQE baseline (QueryEncoderDecoder, bilinear paths + set intersection) through the reference's loop body
+    (_reference_loop): margin_loss per batch on the fused kernels, loss.backward(), Adam; ROC-AUC and the filtered ranking
+    metrics over all entities (evaluation.eval_rank_queries: MRR, hits@10) before and after."""
+    import random
+    from mpqe_amd import evaluation, optim
+    device = torch.device('cuda:0')
+    schema, graph, node_maps, model, train, test = build_gqe(args, device)
     tq = test_dict(test)
+    known = known_answers(args, schema, tq)
     order = [qt for qt, _ in __import__('mpqe_amd.synthetic', fromlist=['FULL_MIX']).FULL_MIX]
     query_types = list(dict.fromkeys(order))
 
@@ -351,6 +366,8 @@ def run_gqe(args):
     iterators = {qt: batches(qt) for qt in query_types}
     with torch.no_grad():
         auc0, _ = evaluation.eval_auc_queries(tq, model, batch_size=128, seed=0)
+    rank0 = evaluation.eval_rank_queries(tq, model.eval(), batch_size=128, ks=(10,), known_answers=known)
+    model.train()
     opt = optim.Adam(model.parameters(), lr=args.lr)
     random.seed(args.seed + 12)
     t0 = time.perf_counter()
@@ -360,9 +377,12 @@ def run_gqe(args):
     train_s = time.perf_counter() - t0
     with torch.no_grad():
         auc1, _ = evaluation.eval_auc_queries(tq, model, batch_size=128, seed=0)
+    rank1 = evaluation.eval_rank_queries(tq, model.eval(), batch_size=128, ks=(10,), known_answers=known)
     return dict(model='gqe', decoder=args.decoder, inter_decoder=args.inter_decoder, kg=args.kg, embed_dim=args.embed_dim,
                 batch_size=args.batch_size, steps=args.steps, train_seconds=train_s, loss_first=losses[0],
-                loss_last20=float(np.mean(losses[-20:])), auc_before=float(auc0), auc_after=float(auc1), loss_curve=losses)
+                loss_last20=float(np.mean(losses[-20:])), auc_before=float(auc0), auc_after=float(auc1),
+                filtered_mrr_before=rank0['mrr'], filtered_mrr_after=rank1['mrr'], filtered_hits10_before=rank0['hits@10'],
+                filtered_hits10_after=rank1['hits@10'], loss_curve=losses)
 
 
 if __name__ == '__main__':
