@@ -26,7 +26,7 @@ __global__ __launch_bounds__(256) void dense_fwd_kernel(const float *__restrict_
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
     LayerLoader<MODE, true> L;      // K runs over din; B[k][n] = W[n][k], tile rows = output columns
-    L.init(kb, x, nullptr, W, rows, 1, din, ldw, dout, b0, n0);
+    L.init(kb, x, nullptr, W, rows, 1, din, ldw, dout, din, b0, n0);      // (the block is W[0:dout, 0:din], ldw >= din)
     gemm_block<false, false>(acc, L, L.spb, smem);
     const int col = n0 + acc_col();
     if (col < dout) {
@@ -59,7 +59,7 @@ __global__ __launch_bounds__(256) void dense_bwd_x_kernel(const float *__restric
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
     LayerLoader<MODE, false> L;
-    L.init(kb, g, mask, W, rows, 1, dout, ldw, dout, b0, n0);
+    L.init(kb, g, mask, W, rows, 1, dout, ldw, dout, din, b0, n0);
     gemm_block<false, true>(acc, L, L.spb, smem);
     const int col = n0 + acc_col();
     if (col < din) {

@@ -47,7 +47,10 @@ template <int MODE, bool TRANS>
 struct LayerLoader {
     KBlocks kb;
     const float *abase, *mask, *wsafe;
-    int K, ldw, wrows;          // A row length; W leading dim (= Dout); rows of W the B tile may touch
+    int K, ldw, wrows, wcols;   // A row length; W row stride; rows and columns of W the B tile may touch. The operand is
+                                // W[0:wrows, 0:wcols]; wcols == ldw for the layer's matrices, less for a column block of
+                                // a wider matrix (dense.hip). TRANS: the load walks a W row along k and is bounded by K;
+                                // wcols is NOT read there (callers pass K's value, the operand's width all the same).
     int spb, ls, left;
     int ca;                     // column of this thread's A slots in the current step: ls*32 + ac
     int bcol0;                  // K-type: n0 + bc (fixed); R-type: bc (column inside the step)
@@ -71,7 +74,7 @@ struct LayerLoader {
 
     __device__ __forceinline__ void init(const KBlocks &blocks, const float *a_, const float *mask_,
                                          const float *wsafe_, long long B, int N, int K_, int ldw_, int wrows_,
-                                         long long b0, int n0) {
+                                         int wcols_, long long b0, int n0) {
         kb = blocks;
         abase = a_;
         mask = mask_;
@@ -79,6 +82,7 @@ struct LayerLoader {
         K = K_;
         ldw = ldw_;
         wrows = wrows_;
+        wcols = wcols_;
         spb = (K + GT_BK - 1) / GT_BK;
         ls = 0;
         left = kb.nk * spb;
@@ -117,10 +121,10 @@ struct LayerLoader {
     __device__ __forceinline__ f32x4 b(int slot, bool &ok) {
         if (!TRANS) {
             const int kk = ls * GT_BK + (slot ? brow1 : brow0);
-            return ld4_pred<MODE>(wsafe, slot ? pb1 : pb0, bcol0, ldw, kk < wrows, ok);
+            return ld4_pred<MODE>(wsafe, slot ? pb1 : pb0, bcol0, wcols, kk < wrows, ok);
         }
         const int nn = slot ? brow1 : brow0;
-        return ld4_pred<MODE>(wsafe, slot ? pb1 : pb0, ls * GT_BK + bcol0, ldw, nn < wrows, ok);
+        return ld4_pred<MODE>(wsafe, slot ? pb1 : pb0, ls * GT_BK + bcol0, K, nn < wrows, ok);
     }
 
     // Written with selects only (the conditions are wave-uniform, so they become s_cselect): a
@@ -175,7 +179,7 @@ __device__ __forceinline__ void tmpl_fwd_tile(const TmplArgs &tp, long long B, c
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
     LayerLoader<MODE, false> L;
-    L.init(kb, x, nullptr, root, B, tp.N, Din, Dout, Din, b0, n0);
+    L.init(kb, x, nullptr, root, B, tp.N, Din, Dout, Din, Dout, b0, n0);
     gemm_block<false, true>(acc, L, kb.nk * L.spb, smem);
     const int col = n0 + acc_col();
     if (col < Dout) {
@@ -224,7 +228,7 @@ __device__ __forceinline__ void tmpl_bwd_x_tile(const TmplArgs &tp, long long B,
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
     LayerLoader<MODE, true> L;      // K runs over Dout; B[k][n] = W[n][k], tile rows = output columns over Din
-    L.init(kb, g, relu ? out : nullptr, root, B, tp.N, Dout, Dout, Din, b0, n0);
+    L.init(kb, g, relu ? out : nullptr, root, B, tp.N, Dout, Dout, Din, Dout, b0, n0);
     gemm_block<false, false>(acc, L, kb.nk * L.spb, smem);
     const int col = n0 + acc_col();
     if (col < Din) {
