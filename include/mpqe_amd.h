@@ -756,6 +756,59 @@ int mpqe_gqe_embed(const int32_t *prog_host, const float *const *tables_host, co
                    const int64_t *p_ids /* [branches, p_rows], or NULL */, int64_t p_rows, float *out /* [p_rows, dim] */,
                    int32_t *err, void *stream);
 
+/* ---- exact answers of a conjunctive query on the knowledge graph (csrc/kg.hip) ------------------------------------
+ * reference: Graph.get_metapath_neighs graph.py:459-473 (the answer set of a chain) and Graph.get_negative_samples
+ * graph.py:263-314 (intersection / union of the branch sets; negatives = full set - answers, hard negatives = union -
+ * intersection). Integer work only; added under ABI 7: entries only.
+ * Row space: everything is in TABLE ROWS of a mode (node_maps[id]), as in mpqe_rank_entities. A set of entities of a mode
+ * with n rows is a bitmap of W = ceil(n / 32) uint32 words, row r = bit r % 32 of word r / 32; bits at or above n are
+ * always written as 0. mode_rows_host [num_modes <= 16]: n per mode, 1 .. 2^30.
+ * Adjacency: one CSR per typed relation (m1, name, m2): rel_offsets_host[i] -> int64 [rows(m1) + 1] and rel_rows_host[i]
+ * -> int64 [rel_edges_host[i]] on the device (the three arrays themselves on the host); values are rows of m2, in any
+ * order, repeats allowed. A row without neighbours has an empty list and contributes nothing (graph.py:467).
+ * Programme: the MPQE_GQE_PROG_INTS int32 layout of mpqe_gqe_fwd -- [1] branches (1..3), [5] hops after the merge (0..1),
+ * [6] target mode, [8 + 5 b] mode of branch b's anchor, [9 + 5 b] its hops (1..3), [10 + 5 b ..] their codes, [24] the
+ * code of the hop after the merge -- with code = relation index << 4 | destination mode where GQE has a matrix code.
+ * Hops walk from the anchors to the target: for a query edge (x, rel, y) the hop uses the CSR of reverse_relation(rel).
+ * The branches must end in one mode and the last hop in the target mode (MPQE_ERR_INVALID_ARG otherwise).
+ *   anchor_rows [branches, Q] int64 (device): the anchors' rows. A row outside its mode ORs MPQE_FLAG_BAD_INDEX into err
+ *               and gives THAT query empty sets; the other queries are unaffected. A CSR offset or row outside
+ *               its range is flagged too and not followed.
+ *   answers [Q, W(target mode)]: the query's exact answer set.
+ *   hard    [Q, W] or NULL: the same programme with the merge taken as OR, minus answers (union_neighs - inter_neighs;
+ *               3-chain_inter: union_pos_nodes - pos_nodes, graph.py:299-311); all zero with one branch.
+ *   counts  [2, Q] int64 or NULL: population counts of answers, then of hard (0 when hard is NULL).
+ *   flags   MPQE_KG_GLOBAL_BITS: keep the working bitmaps in the workspace, not in LDS (the form modes above 77 824 rows
+ *               take anyway; for tests at small shapes).
+ *   workspace: what the size query returns for the same flags (256 when the bitmaps live in LDS: not touched); NOT
+ *               assumed zeroed. Every word of every output is written; the result is a set -- the same bits every run.
+ * num_queries == 0: nothing is launched. Arguments are checked before any launch (MPQE_ERR_INVALID_ARG; a short
+ * workspace MPQE_ERR_WORKSPACE; the size query returns 0). */
+#define MPQE_KG_GLOBAL_BITS 1
+size_t mpqe_kg_workspace_bytes(const int32_t *prog_host, int64_t num_queries, const int64_t *mode_rows_host, int num_modes,
+                               int flags);
+int mpqe_kg_answers(const int32_t *prog_host, const int64_t *const *rel_offsets_host, const int64_t *const *rel_rows_host,
+                    const int64_t *rel_edges_host, int num_rels, const int64_t *mode_rows_host, int num_modes,
+                    const int64_t *anchor_rows /*[branches, Q] device*/, int64_t num_queries, uint32_t *answers /*[Q, W]*/,
+                    uint32_t *hard /*[Q, W] or NULL*/, int64_t *counts /*[2, Q] or NULL*/, int flags, void *workspace,
+                    size_t workspace_bytes, int32_t *err, void *stream);
+
+/* Bitmaps [Q, W] of a mode with n rows -> the CSR mpqe_rank_entities takes as excl_offsets / excl_rows: query q's rows
+ * ascending at rows_out[offsets[q] .. offsets[q + 1]). `select`, with valid [W] (NULL: every row below n) marking the rows
+ * that are entities:   MPQE_KG_ROWS_SET         the set itself
+ *                      MPQE_KG_ROWS_COMPLEMENT  valid & ~bits: the plain negatives (full_sets[mode] - answers); table
+ *                                               holes never become negatives
+ *                      MPQE_KG_ROWS_WITH_HOLES  bits | ~valid: the set and every row below n that is no entity (what a
+ *                                               filtered ranking excludes)
+ * offsets [Q + 1] is the caller's exclusive scan of the lists' lengths (mpqe_kg_answers' counts); rows_cap the slots
+ * behind rows_out. A list that does not fit its segment, or a segment outside [0, rows_cap], ORs MPQE_FLAG_BAD_INDEX
+ * into err and nothing is written outside the segment. */
+#define MPQE_KG_ROWS_SET 0
+#define MPQE_KG_ROWS_COMPLEMENT 1
+#define MPQE_KG_ROWS_WITH_HOLES 2
+int mpqe_kg_rows(const uint32_t *bits, int64_t num_queries, int64_t n, const uint32_t *valid /*[W] or NULL*/, int select,
+                 const int64_t *offsets /*[Q + 1]*/, int64_t *rows_out, int64_t rows_cap, int32_t *err, void *stream);
+
 /* The aggregate of the intersection on its own (decoders.py:293-298, 313-318: torch.stack + agg_func(dim = 0)): out[i] =
  * mean (agg 0) / min (agg 1) of x0[i], x1[i] and, unless NULL, x2[i]; count elements. Backward: the mean's gradient in equal
  * parts, the minimum's to the first branch that holds it; NULL gradient pointers are not written. */

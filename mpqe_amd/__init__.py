@@ -4,7 +4,8 @@ from .graph import Formula, Graph, Query  # noqa: F401
 
 __all__ = ['Formula', 'Graph', 'Query', 'RGCNConv', 'RGCNEncoderDecoder', 'DirectEncoder',
            'RGCNQueryDataset', 'MLPReadout', 'TargetMLPReadout', 'QueryEncoderDecoder', 'BilinearMetapathDecoder',
-           'SetIntersection', 'SimpleSetIntersection', 'get_metapath_decoder', 'get_intersection_decoder']
+           'SetIntersection', 'SimpleSetIntersection', 'get_metapath_decoder', 'get_intersection_decoder',
+           'KGIndex', 'KGAnswers']
 
 
 def __getattr__(name):
@@ -19,6 +20,9 @@ def __getattr__(name):
     if name in ('get_metapath_decoder', 'get_intersection_decoder'):
         from . import utils
         return getattr(utils, name)
+    if name in ('KGIndex', 'KGAnswers'):
+        from . import kg
+        return getattr(kg, name)
     if name == 'DirectEncoder':
         from .encoders import DirectEncoder
         return DirectEncoder

@@ -110,6 +110,9 @@ PROTOTYPES = {
     'mpqe_gqe_fwd': (I, [P, P, P, I, P, L, P, I, L, P, L, P, L, P, P, L, F, I, P, P, Z, P, P]),
     'mpqe_gqe_bwd': (I, [P, P, P, I, P, L, P, I, L, P, L, P, L, P, P, L, F, P, P, P, P, Z, P, P]),
     'mpqe_gqe_embed': (I, [P, P, P, I, P, L, P, I, L, P, L, P, P, P]),
+    'mpqe_kg_workspace_bytes': (Z, [P, L, P, I, I]),
+    'mpqe_kg_answers': (I, [P, P, P, P, I, P, I, P, L, P, P, P, I, P, Z, P, P]),
+    'mpqe_kg_rows': (I, [P, L, L, P, I, P, P, L, P, P]),
     'mpqe_branch_agg_fwd': (I, [P, P, P, L, I, P, P]),
     'mpqe_branch_agg_bwd': (I, [P, P, P, L, I, P, P, P, P, P]),
     'mpqe_debug_chain_stamps': (None, [P, Z]),
@@ -171,6 +174,8 @@ SCATTER_IDS = {'add': 0, 'max': 1, 'mean': 2}
 
 FLAG_BAD_NODE_ID, FLAG_BAD_EDGE, FLAG_BAD_RELATION, FLAG_BAD_INDEX = 1, 2, 4, 8
 FLAG_INTERNAL, FLAG_TOUCH_RETRY = 16, 32
+KG_GLOBAL_BITS = 1                                   # mpqe_kg_answers flags
+KG_ROWS_SET, KG_ROWS_COMPLEMENT, KG_ROWS_WITH_HOLES = 0, 1, 2       # mpqe_kg_rows select
 
 
 def bind(cdll):

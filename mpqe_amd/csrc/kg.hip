@@ -1,0 +1,407 @@
+// Answering a conjunctive query EXACTLY on the knowledge graph: which rows of the target mode's table reach every anchor
+// along the formula's relations. Integer work only: one bitmap of a mode's rows per set (row r = bit r % 32 of word
+// r / 32), one CSR per typed relation, OR along a hop, AND / OR across the branches, population counts.
+//
+// All seven query types are "1-3 branches, each a chain of 1-3 hops from one anchor; merge; then 0-1 hops" (the shape
+// gqe.hip runs with matrices). One workgroup owns one query and walks the programme:
+//   first hop of a branch   a list walk: the workgroup's 256 lanes stride over rows[offsets[a] .. offsets[a + 1])
+//   a later hop             a scan of the frontier bitmap: the waves take its non-empty words in turn; for every set bit
+//                           the wave's 64 lanes stride over that row's list (a row of degree 1 000 does not serialise on
+//                           one lane)
+//   merge                   AND (the answers) and OR (the union flavour the hard negatives come from) of the branches'
+//                           bitmaps, word by word, in the same pass
+//   hop after the merge     ONE scan of the OR bitmap: a set row's list goes to the union's result, and to the answers'
+//                           result too if the row is in the AND bitmap (AND is a subset of OR)
+//   out                     answers = the AND flavour; hard = the OR flavour & ~answers; counts = their population counts
+//
+// Home of the bitmaps. A workgroup keeps four: the ping-pong pair of a branch's hops and the two merge accumulators,
+// each of W = ceil(n / 32) words for the widest mode the programme names. In LDS when W <= KG_LDS_WORDS = 2 432:
+// 4 x 2 432 x 4 B = 38 912 B a workgroup, so four workgroups share a CU's 160 KiB (155 648 B + their 32 B of counters);
+// that covers modes of up to 77 824 rows. Wider modes, and MPQE_KG_GLOBAL_BITS, keep the four bitmaps of query q at
+// workspace[q * 4 * W ..] in HBM instead: the same code with atomicOr on global words, read back at agent scope (the OR
+// is done in L2, so a plain load could meet a stale line of this CU's vector cache).
+//
+// Determinism: the only concurrent writes are integer ORs into a bitmap, whose result does not depend on their order;
+// the output is a set, bit-identical run to run by construction. The workspace need not be zeroed: a bitmap is cleared
+// by the workgroup right before it is ORed into, and every word of every output is written.
+#include <string.h>
+
+#include "common.h"
+
+#define KG_THREADS 256
+#define KG_WAVES 4
+#define KG_LDS_WORDS 2432
+#define KG_MAX_ROWS ((int64_t)1 << 30)
+
+struct KgHop {
+    const long long *off;       // [n_src + 1]
+    const long long *rows;      // [edges], rows of the destination mode
+    long long edges;
+    int n_src, n_dst;
+};
+
+struct KgPlan {
+    int branches, tail, W, n_out, n_merge;
+    int hops[3], anchor_n[3];
+    KgHop hop[3][3];
+    KgHop tail_hop;
+};
+
+__device__ __forceinline__ int kg_words(int n) { return (n + 31) >> 5; }
+
+template <bool G>
+__device__ __forceinline__ uint32_t kg_load(const uint32_t *p) {
+    if (G) return agent_load(p);
+    return *p;
+}
+template <bool G>
+__device__ __forceinline__ void kg_store(uint32_t *p, uint32_t v) {
+    if (G) agent_store(p, v); else *p = v;
+}
+
+template <bool G>
+__device__ __forceinline__ void kg_clear(uint32_t *b, int n) {
+    const int W = kg_words(n);
+    for (int w = threadIdx.x; w < W; w += KG_THREADS) kg_store<G>(b + w, 0u);
+}
+
+// rows[offsets[x] .. offsets[x + 1]) ORed into `out` (and `out2`): entries id, id + stride, ... An offset outside
+// [0, edges] or a row outside the destination mode is flagged and not followed.
+__device__ __forceinline__ void kg_or_list(const KgHop &h, long long x, uint32_t *out, uint32_t *out2, int id, int stride,
+                                           int32_t *err) {
+    long long lo = h.off[x], hi = h.off[x + 1];
+    if (lo < 0 || hi < lo || hi > h.edges) {
+        flag_error(err, MPQE_FLAG_BAD_INDEX);
+        lo = lo < 0 ? 0 : (lo > h.edges ? h.edges : lo);
+        hi = hi < lo ? lo : (hi > h.edges ? h.edges : hi);
+    }
+    for (long long e = lo + id; e < hi; e += stride) {
+        const long long r = h.rows[e];
+        if (r < 0 || r >= h.n_dst) {
+            flag_error(err, MPQE_FLAG_BAD_INDEX);
+            continue;
+        }
+        const uint32_t bit = 1u << (unsigned)(r & 31);
+        atomicOr(out + (r >> 5), bit);
+        if (out2) atomicOr(out2 + (r >> 5), bit);
+    }
+}
+
+// One hop from a frontier bitmap: every set row of `cur` sends its list to `out`; with `sub` (a subset of cur) a row
+// that is in sub sends it to `out2` as well. Every wave reads the bitmap in chunks of 64 words, a lane per word, and ORs
+// "my word is not zero" into a 64-bit mask over the wave: a chunk without a set bit -- nearly all of them on a large mode --
+// costs one read and twelve shuffles. The non-empty words go to the four waves in turn (the k-th to wave k % 4); the
+// owner takes the word from its lane and, for every set bit, its 64 lanes stride over that row's list. Every branch here
+// is uniform in the wave.
+template <bool G>
+__device__ __forceinline__ void kg_scan_hop(const KgHop &h, const uint32_t *cur, const uint32_t *sub, uint32_t *out,
+                                            uint32_t *out2, int32_t *err) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int Ws = kg_words(h.n_src);
+    int k = 0;
+    for (int c = 0; c < Ws; c += 64) {
+        const int w = c + lane;
+        const uint32_t mine = w < Ws ? kg_load<G>(cur + w) : 0u;
+        const uint32_t mine_sub = sub && w < Ws ? kg_load<G>(sub + w) : 0u;
+        int lo = mine && lane < 32 ? (int)(1u << lane) : 0, hi = mine && lane >= 32 ? (int)(1u << (lane - 32)) : 0;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            lo |= __shfl_xor(lo, o, 64);
+            hi |= __shfl_xor(hi, o, 64);
+        }
+        for (int half = 0; half < 2; ++half) {
+            uint32_t words = (uint32_t)(half ? hi : lo);
+            while (words) {
+                const int j = __builtin_ctz(words) + 32 * half;
+                words &= words - 1;
+                if ((k++ & (KG_WAVES - 1)) != wave) continue;
+                uint32_t bits = (uint32_t)__shfl((int)mine, j, 64);
+                const uint32_t also = sub ? (uint32_t)__shfl((int)mine_sub, j, 64) : 0u;
+                while (bits) {
+                    const int b = __builtin_ctz(bits);
+                    bits &= bits - 1;
+                    const long long x = (long long)(c + j) * 32 + b;
+                    if (x >= h.n_src) break;        // (never: bits at or above n are written as 0)
+                    kg_or_list(h, x, out, ((also >> b) & 1u) ? out2 : nullptr, lane, 64, err);
+                }
+            }
+        }
+    }
+}
+
+template <bool G>
+__global__ __launch_bounds__(KG_THREADS) void kg_answers_kernel(KgPlan P, const long long *__restrict__ anchors,
+                                                                long long Q, uint32_t *__restrict__ answers,
+                                                                uint32_t *__restrict__ hard,
+                                                                long long *__restrict__ counts, uint32_t *ws,
+                                                                int32_t *err) {
+    __shared__ uint32_t lds[G ? 1 : 4 * KG_LDS_WORDS];
+    __shared__ int red[2 * KG_WAVES];
+    const long long q = blockIdx.x;
+    const int t = threadIdx.x;
+    uint32_t *base = G ? ws + (size_t)q * 4 * (size_t)P.W : lds;
+    uint32_t *F[2] = {base, base + P.W};        // the ping-pong pair
+    uint32_t *AND = base + 2 * (size_t)P.W, *OR = base + 3 * (size_t)P.W;
+    const int Wout = kg_words(P.n_out);
+    uint32_t *ans = answers + (size_t)q * Wout;
+    uint32_t *hrd = hard ? hard + (size_t)q * Wout : nullptr;
+
+    long long a[3] = {0, 0, 0};
+    bool bad = false;
+    for (int b = 0; b < P.branches; ++b) {
+        a[b] = anchors[(long long)b * Q + q];
+        bad = bad || a[b] < 0 || a[b] >= P.anchor_n[b];
+    }
+    if (bad) {          // (the whole workgroup: no barrier has been met yet) -- this query's sets are empty
+        if (t == 0) flag_error(err, MPQE_FLAG_BAD_INDEX);
+        for (int w = t; w < Wout; w += KG_THREADS) {
+            ans[w] = 0u;
+            if (hrd) hrd[w] = 0u;
+        }
+        if (counts && t == 0) {
+            counts[q] = 0;
+            counts[Q + q] = 0;
+        }
+        return;
+    }
+
+    for (int b = 0; b < P.branches; ++b) {
+        const uint32_t *cur = nullptr;
+        for (int s = 0; s < P.hops[b]; ++s) {
+            const KgHop &h = P.hop[b][s];
+            uint32_t *out = base + (size_t)(s & 1) * (size_t)P.W;
+            kg_clear<G>(out, h.n_dst);
+            __syncthreads();
+            if (s == 0) kg_or_list(h, a[b], out, nullptr, t, KG_THREADS, err);
+            else kg_scan_hop<G>(h, cur, nullptr, out, nullptr, err);
+            __syncthreads();
+            cur = out;
+        }
+        const int Wm = kg_words(P.n_merge);
+        for (int w = t; w < Wm; w += KG_THREADS) {
+            const uint32_t v = kg_load<G>(cur + w);
+            if (b == 0) {
+                kg_store<G>(AND + w, v);
+                kg_store<G>(OR + w, v);
+            } else {
+                kg_store<G>(AND + w, kg_load<G>(AND + w) & v);
+                kg_store<G>(OR + w, kg_load<G>(OR + w) | v);
+            }
+        }
+        __syncthreads();
+    }
+
+    const uint32_t *res_and = AND, *res_or = OR;
+    if (P.tail) {
+        kg_clear<G>(F[0], P.tail_hop.n_dst);
+        if (hrd) kg_clear<G>(F[1], P.tail_hop.n_dst);
+        __syncthreads();
+        if (hrd) kg_scan_hop<G>(P.tail_hop, OR, AND, F[1], F[0], err);
+        else kg_scan_hop<G>(P.tail_hop, AND, nullptr, F[0], nullptr, err);
+        __syncthreads();
+        res_and = F[0];
+        res_or = F[1];
+    }
+
+    int ca = 0, ch = 0;
+    for (int w = t; w < Wout; w += KG_THREADS) {
+        const uint32_t v = kg_load<G>(res_and + w);
+        ans[w] = v;
+        ca += __builtin_popcount(v);
+        if (hrd) {
+            const uint32_t u = kg_load<G>(res_or + w) & ~v;
+            hrd[w] = u;
+            ch += __builtin_popcount(u);
+        }
+    }
+    if (!counts) return;        // (uniform)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        ca += __shfl_xor(ca, o, 64);
+        ch += __shfl_xor(ch, o, 64);
+    }
+    if ((t & 63) == 0) {
+        red[t >> 6] = ca;
+        red[KG_WAVES + (t >> 6)] = ch;
+    }
+    __syncthreads();
+    if (t == 0) {
+        counts[q] = (long long)red[0] + red[1] + red[2] + red[3];
+        counts[Q + q] = (long long)red[4] + red[5] + red[6] + red[7];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- bitmaps -> row lists
+// One workgroup per query, 256 words a round: a lane counts its word, an exclusive scan over the workgroup places the
+// word's rows, so a query's list comes out ascending. A slot outside [offsets[q], offsets[q + 1]) or past `cap` is not
+// written and flagged, as is a list whose length is not what the offsets say.
+__global__ __launch_bounds__(KG_THREADS) void kg_rows_kernel(const uint32_t *__restrict__ bits, long long n,
+                                                             const uint32_t *__restrict__ valid, int select,
+                                                             const long long *__restrict__ offsets,
+                                                             long long *__restrict__ rows_out, long long cap,
+                                                             int32_t *err) {
+    __shared__ int wsum[KG_WAVES];
+    const long long q = blockIdx.x;
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    const long long W = (n + 31) >> 5;
+    const long long lo = offsets[q], hi = offsets[q + 1];
+    if (lo < 0 || hi < lo || hi > cap) {        // (uniform)
+        if (t == 0) flag_error(err, MPQE_FLAG_BAD_INDEX);
+        return;
+    }
+    long long run = lo;
+    bool over = false;
+    for (long long w0 = 0; w0 < W; w0 += KG_THREADS) {
+        const long long w = w0 + t;
+        uint32_t v = 0u;
+        if (w < W) {
+            const uint32_t b = bits[q * W + w];
+            const uint32_t va = valid ? valid[w] : ~0u;
+            v = select == MPQE_KG_ROWS_SET ? b : (select == MPQE_KG_ROWS_COMPLEMENT ? va & ~b : b | ~va);
+            if (w == W - 1 && (n & 31)) v &= (1u << (unsigned)(n & 31)) - 1u;
+        }
+        const int c = __builtin_popcount(v);
+        int incl = c;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int up = __shfl(incl, lane >= o ? lane - o : lane, 64);
+            if (lane >= o) incl += up;
+        }
+        if (lane == 63) wsum[wave] = incl;
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int i = 0; i < KG_WAVES; ++i) {
+            before += i < wave ? wsum[i] : 0;
+            total += wsum[i];
+        }
+        long long p = run + before + incl - c;
+        while (v) {
+            const int b = __builtin_ctz(v);
+            v &= v - 1;
+            if (p < hi) rows_out[p] = w * 32 + b; else over = true;
+            ++p;
+        }
+        run += total;
+        __syncthreads();        // (wsum is rewritten in the next round)
+    }
+    if (over || (t == 0 && run != hi)) flag_error(err, MPQE_FLAG_BAD_INDEX);
+}
+
+// ---------------------------------------------------------------------------------------------- host
+static bool kg_mode_ok(int m, const int64_t *mode_rows, int num_modes) {
+    return m >= 0 && m < num_modes && mode_rows[m] >= 1 && mode_rows[m] <= KG_MAX_ROWS;
+}
+
+// The programme checked and laid out; rel_* may be NULL (the size query: only modes are read). 0 = fine.
+static int kg_compile(const int32_t *prog, const int64_t *const *rel_offsets, const int64_t *const *rel_rows,
+                      const int64_t *rel_edges, int num_rels, const int64_t *mode_rows, int num_modes, KgPlan &P) {
+    memset(&P, 0, sizeof(P));
+    if (!prog || !mode_rows || num_modes < 1 || num_modes > 16) return MPQE_ERR_INVALID_ARG;
+    const int branches = prog[1], tail = prog[5], target = prog[6];
+    if (branches < 1 || branches > 3 || tail < 0 || tail > 1) return MPQE_ERR_INVALID_ARG;
+    if (!kg_mode_ok(target, mode_rows, num_modes)) return MPQE_ERR_INVALID_ARG;
+    int widest = 0, merge = -1;
+    P.branches = branches;
+    P.tail = tail;
+    auto hop = [&](int code, int src_mode, KgHop &h, int &dst_mode) -> bool {
+        if (code < 0) return false;
+        const int rel = code >> 4;
+        dst_mode = code & 15;
+        if (!kg_mode_ok(dst_mode, mode_rows, num_modes)) return false;
+        h.n_src = (int)mode_rows[src_mode];
+        h.n_dst = (int)mode_rows[dst_mode];
+        h.off = h.rows = nullptr;
+        h.edges = 0;
+        if (rel_offsets) {
+            if (rel >= num_rels || !rel_offsets[rel] || rel_edges[rel] < 0) return false;
+            if (rel_edges[rel] > 0 && !rel_rows[rel]) return false;
+            h.off = reinterpret_cast<const long long *>(rel_offsets[rel]);
+            h.rows = reinterpret_cast<const long long *>(rel_rows[rel]);
+            h.edges = rel_edges[rel];
+        }
+        if (h.n_dst > widest) widest = h.n_dst;
+        return true;
+    };
+    for (int b = 0; b < branches; ++b) {
+        int mode = prog[8 + 5 * b];
+        const int hops = prog[9 + 5 * b];
+        if (!kg_mode_ok(mode, mode_rows, num_modes) || hops < 1 || hops > 3) return MPQE_ERR_INVALID_ARG;
+        P.hops[b] = hops;
+        P.anchor_n[b] = (int)mode_rows[mode];
+        for (int s = 0; s < hops; ++s) {
+            int dst;
+            if (!hop(prog[10 + 5 * b + s], mode, P.hop[b][s], dst)) return MPQE_ERR_INVALID_ARG;
+            mode = dst;
+        }
+        if (merge >= 0 && mode != merge) return MPQE_ERR_INVALID_ARG;       // the branches meet in ONE mode
+        merge = mode;
+    }
+    P.n_merge = (int)mode_rows[merge];
+    int last = merge;
+    if (tail) {
+        int dst;
+        if (!hop(prog[24], merge, P.tail_hop, dst)) return MPQE_ERR_INVALID_ARG;
+        last = dst;
+    }
+    if (last != target) return MPQE_ERR_INVALID_ARG;
+    P.n_out = (int)mode_rows[target];
+    P.W = (widest + 31) / 32;
+    return MPQE_OK;
+}
+
+static bool kg_in_lds(const KgPlan &P, int flags) { return P.W <= KG_LDS_WORDS && !(flags & MPQE_KG_GLOBAL_BITS); }
+
+extern "C" size_t mpqe_kg_workspace_bytes(const int32_t *prog_host, int64_t num_queries, const int64_t *mode_rows_host,
+                                          int num_modes, int flags) {
+    KgPlan P;
+    if (num_queries < 0 || num_queries > KG_MAX_ROWS) return 0;
+    if (kg_compile(prog_host, nullptr, nullptr, nullptr, 0, mode_rows_host, num_modes, P) != MPQE_OK) return 0;
+    if (kg_in_lds(P, flags)) return 256;
+    return align_up((size_t)num_queries * 4 * (size_t)P.W * 4, 256) + 256;
+}
+
+extern "C" int mpqe_kg_answers(const int32_t *prog_host, const int64_t *const *rel_offsets_host,
+                               const int64_t *const *rel_rows_host, const int64_t *rel_edges_host, int num_rels,
+                               const int64_t *mode_rows_host, int num_modes, const int64_t *anchor_rows,
+                               int64_t num_queries, uint32_t *answers, uint32_t *hard, int64_t *counts, int flags,
+                               void *workspace, size_t workspace_bytes, int32_t *err, void *stream) {
+    const int64_t Q = num_queries;
+    if (Q < 0 || Q > KG_MAX_ROWS || num_rels < 1 || !rel_offsets_host || !rel_rows_host || !rel_edges_host)
+        return MPQE_ERR_INVALID_ARG;
+    if (flags & ~MPQE_KG_GLOBAL_BITS) return MPQE_ERR_INVALID_ARG;
+    KgPlan P;
+    const int st = kg_compile(prog_host, rel_offsets_host, rel_rows_host, rel_edges_host, num_rels, mode_rows_host,
+                              num_modes, P);
+    if (st != MPQE_OK) return st;
+    if (Q == 0) return MPQE_OK;
+    if (!anchor_rows || !answers) return MPQE_ERR_INVALID_ARG;
+    hipStream_t s = as_stream(stream);
+    const long long *anc = reinterpret_cast<const long long *>(anchor_rows);
+    long long *cnt = reinterpret_cast<long long *>(counts);
+    if (kg_in_lds(P, flags)) {
+        hipLaunchKernelGGL(kg_answers_kernel<false>, dim3((unsigned)Q), dim3(KG_THREADS), 0, s, P, anc, (long long)Q,
+                           answers, hard, cnt, (uint32_t *)nullptr, err);
+        return mpqe_launch_status();
+    }
+    const size_t need = align_up((size_t)Q * 4 * (size_t)P.W * 4, 256);
+    if (!workspace || ((uintptr_t)workspace & 3)) return MPQE_ERR_INVALID_ARG;
+    if (workspace_bytes < need) return MPQE_ERR_WORKSPACE;
+    hipLaunchKernelGGL(kg_answers_kernel<true>, dim3((unsigned)Q), dim3(KG_THREADS), 0, s, P, anc, (long long)Q, answers,
+                       hard, cnt, reinterpret_cast<uint32_t *>(workspace), err);
+    return mpqe_launch_status();
+}
+
+extern "C" int mpqe_kg_rows(const uint32_t *bits, int64_t num_queries, int64_t n, const uint32_t *valid, int select,
+                            const int64_t *offsets, int64_t *rows_out, int64_t rows_cap, int32_t *err, void *stream) {
+    if (num_queries < 0 || num_queries > KG_MAX_ROWS || n < 1 || n > KG_MAX_ROWS || rows_cap < 0)
+        return MPQE_ERR_INVALID_ARG;
+    if (select != MPQE_KG_ROWS_SET && select != MPQE_KG_ROWS_COMPLEMENT && select != MPQE_KG_ROWS_WITH_HOLES)
+        return MPQE_ERR_INVALID_ARG;
+    if (num_queries == 0) return MPQE_OK;
+    if (!bits || !offsets || (rows_cap > 0 && !rows_out)) return MPQE_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(kg_rows_kernel, dim3((unsigned)num_queries), dim3(KG_THREADS), 0, as_stream(stream), bits,
+                       (long long)n, valid, select, reinterpret_cast<const long long *>(offsets),
+                       reinterpret_cast<long long *>(rows_out), (long long)rows_cap, err);
+    return mpqe_launch_status();
+}

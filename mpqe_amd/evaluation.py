@@ -100,7 +100,8 @@ def eval_rank_queries(test_queries, enc_dec, batch_size=128, ks=(1, 3, 10), know
     """Link-prediction metrics over ALL entities of each query's target mode (no counterpart in the reference, whose
     evaluation ranks the target among the negatives stored with the query): the rank of query.target_node from
     `enc_dec.rank_targets`, filtered by `known_answers[query]` (every entity known to answer the query; the target is
-    never filtered out) when given -- the standard filtered setting -- raw otherwise.
+    never filtered out) when given -- the standard filtered setting -- raw otherwise. known_answers may also be a
+    kg.KGIndex: the answers of each batch are then computed on the device (index.answers) and never visit the host.
     -> {'mrr', 'hits@k' for k in ks, 'num_queries', 'per_formula': {formula: {'mrr', 'hits@k', 'num_queries'}}}."""
     def summary(ranks):
         r = np.asarray(ranks, dtype=np.float64)
@@ -110,13 +111,17 @@ def eval_rank_queries(test_queries, enc_dec, batch_size=128, ks=(1, 3, 10), know
         out['num_queries'] = int(r.size)
         return out
 
+    from .kg import KGIndex
     all_ranks, per_formula = [], {}
     for formula in test_queries:
         formula_queries = test_queries[formula]
         formula_ranks = []
         for lo, hi in _batches(formula_queries, batch_size):
             batch_queries = formula_queries[lo:hi]
-            exclude = None if known_answers is None else [list(known_answers[q]) for q in batch_queries]
+            if isinstance(known_answers, KGIndex):
+                exclude = known_answers.answers(formula, batch_queries)
+            else:
+                exclude = None if known_answers is None else [list(known_answers[q]) for q in batch_queries]
             targets = [q.target_node for q in batch_queries]
             ranks = enc_dec.rank_targets(formula, batch_queries, targets, exclude=exclude)
             formula_ranks.extend(int(r) for r in ranks.detach().cpu().tolist())

@@ -1,0 +1,310 @@
+"""Exact answers of conjunctive queries on the knowledge graph, on the device (csrc/kg.hip; include/mpqe_amd.h:
+mpqe_kg_answers, mpqe_kg_rows). The reference keeps this as Python sets (Graph.get_metapath_neighs graph.py:459-473,
+Graph.get_negative_samples graph.py:263-314); here the graph is one CSR per typed relation in HBM, a set of entities is a
+bitmap over a mode's TABLE ROWS (node_maps[id], the row space of ops.rank_entities), and a batch of queries of one formula
+is one launch.
+
+    index = KGIndex.from_graph(graph, enc.node_maps, device)           # once; or KGIndex.from_edges(...) from arrays
+    ans = index.answers(formula, queries, hard=True)                   # KGAnswers: bits / hard_bits / counts on the device
+    model.rank_targets(formula, queries, targets, exclude=ans)         # filtered ranking without host lists
+    eval_rank_queries(test_queries, model, known_answers=index)
+    NegativeSampler.from_csr(ans.negative_csr(), ans.hard_csr(), device)
+"""
+import contextlib
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _capi, ops
+from .graph import reverse_relation
+
+PROG_INTS = ops.GQE_PROG_INTS
+MAX_MODES = 16
+
+
+def query_hops(formula):
+    """([(anchor slot, [relation of each hop])], [relations of the hops after the merge]): the walk from the anchors to the
+    target. A query edge (x, rel, y) is walked from y to x along reverse_relation(rel), whose CSR lists the x of a y
+    (synthetic._answers; reference graph.py:266, 274, 290, 300-307)."""
+    qt, rels = formula.query_type, formula.rels
+    rev = reverse_relation
+    if qt.endswith('-chain'):
+        return [(0, [rev(tuple(r)) for r in reversed(rels)])], []
+    if qt.endswith('-inter'):
+        return [(i, [rev(tuple(r))]) for i, r in enumerate(rels)], []
+    if qt == '3-inter_chain':
+        return [(0, [rev(tuple(rels[0]))]), (1, [rev(tuple(rels[1][1])), rev(tuple(rels[1][0]))])], []
+    if qt == '3-chain_inter':
+        return [(0, [rev(tuple(rels[1][0]))]), (1, [rev(tuple(rels[1][1]))])], [rev(tuple(rels[0]))]
+    raise ValueError('unknown query type %r' % (qt,))
+
+
+def kg_programme(branches, tail, target_mode):
+    """The int32 programme of mpqe_kg_answers: the layout of ops.gqe_programme with code = relation << 4 | destination mode.
+    branches: [(anchor mode, [(relation index, destination mode)])], tail: [(relation index, destination mode)]."""
+    prog = np.full(PROG_INTS, -1, dtype=np.int32)
+    prog[0], prog[1], prog[2], prog[5], prog[6], prog[7] = 1, len(branches), 0, len(tail), target_mode, 0
+    for b, (mode, steps) in enumerate(branches):
+        prog[8 + 5 * b], prog[9 + 5 * b] = mode, len(steps)
+        for s, (rel, dst) in enumerate(steps):
+            prog[10 + 5 * b + s] = (rel << 4) | dst
+    for s, (rel, dst) in enumerate(tail):
+        prog[24 + s] = (rel << 4) | dst
+    return prog
+
+
+def _words(n):
+    return (int(n) + 31) // 32
+
+
+def _bitmap(rows, n):
+    """uint32 words of the set `rows` of a mode with n rows (bit r % 32 of word r / 32), as int32 for torch."""
+    flags = np.zeros(_words(n) * 32, dtype=np.uint8)
+    flags[np.asarray(rows, dtype=np.int64)] = 1
+    return np.packbits(flags, bitorder='little').view(np.uint32).view(np.int32)
+
+
+def _unpack(words, n):
+    """[Q, W] words -> one ascending array of rows per query"""
+    words = np.ascontiguousarray(words).view(np.uint32)
+    flags = np.unpackbits(words.view(np.uint8).reshape(words.shape[0], -1), axis=1, bitorder='little')[:, :n]
+    return [np.nonzero(f)[0].astype(np.int64) for f in flags]
+
+
+class KGIndex(object):
+    """The graph on the device: per typed relation a CSR over table rows, per mode its row count n (1 + the last row
+    that is an entity, as _EntityRanking._mode_rows has it), the row -> id map and the bitmap of the rows that are
+    entities. Built once. lib: a bound C-ABI library to call instead of the product's -- the tests run a CPU-resident index
+    on the host emulator of the kernels; without one the index must live on the GPU (there is no CPU path)."""
+
+    def __init__(self, mode_ids_of, edges, node_maps, device, lib=None):
+        self.device = torch.device(device)
+        self.lib = lib
+        maps = node_maps.detach().cpu().numpy() if torch.is_tensor(node_maps) else np.asarray(node_maps)
+        self.maps_host = maps = np.ascontiguousarray(maps, dtype=np.int64)
+        self.modes = list(mode_ids_of)
+        if not 1 <= len(self.modes) <= MAX_MODES:
+            raise ValueError('KGIndex: 1 to %d modes, got %d' % (MAX_MODES, len(self.modes)))
+        self.mode_index = {m: i for i, m in enumerate(self.modes)}
+        self.row_ids_host, self.row_ids, self.valid, self.num_entities = {}, {}, {}, {}
+        mode_rows = []
+        for m in self.modes:
+            ids = np.asarray(list(mode_ids_of[m]), dtype=np.int64)
+            if ids.size == 0 or ids.min() < 0 or ids.max() >= maps.shape[0]:
+                raise IndexError('KGIndex: mode %r is empty or holds ids outside node_maps' % (m,))
+            rows = maps[ids]
+            if rows.min() < 0:
+                raise IndexError('KGIndex: mode %r holds ids without a table row' % (m,))
+            n = int(rows.max()) + 1
+            row_ids = np.full(n, -1, dtype=np.int64)
+            row_ids[rows] = ids
+            self.row_ids_host[m] = row_ids
+            self.row_ids[m] = torch.from_numpy(row_ids).to(self.device)
+            self.valid[m] = torch.from_numpy(_bitmap(np.nonzero(row_ids >= 0)[0], n)).to(self.device)
+            self.num_entities[m] = int((row_ids >= 0).sum())
+            mode_rows.append(n)
+        self.mode_rows = np.asarray(mode_rows, dtype=np.int64)
+        self.rels = [tuple(r) for r in edges]
+        self.rel_index = {r: i for i, r in enumerate(self.rels)}
+        self.offsets, self.rows = [], []
+        for rel in self.rels:
+            src, dst = edges[rel]
+            off, rows = self._csr(rel, np.asarray(src, dtype=np.int64).reshape(-1), np.asarray(dst, dtype=np.int64).reshape(-1))
+            self.offsets.append(torch.from_numpy(off).to(self.device))
+            self.rows.append(torch.from_numpy(rows).to(self.device))
+        R = max(len(self.rels), 1)
+        self._off_arr = (ctypes.c_void_p * R)(*[t.data_ptr() for t in self.offsets])
+        self._rows_arr = (ctypes.c_void_p * R)(*[t.data_ptr() if t.numel() else None for t in self.rows])
+        self._edges_arr = (ctypes.c_int64 * R)(*[t.numel() for t in self.rows])
+        self._programmes = {}
+        self.err = ops.new_error_word(self.device)
+
+    @contextlib.contextmanager
+    def _call(self):
+        """-> (library, stream) for one C-ABI call on this index's device"""
+        if self.lib is not None:
+            yield self.lib, None
+        elif self.device.type != 'cuda':
+            raise RuntimeError('mpqe_amd: the KG index must be on a CUDA (ROCm) device -- there is no CPU path')
+        else:
+            with torch.cuda.device(self.device):
+                yield ops.lib(), ops._stream()
+
+    def _rows_of(self, mode, ids):
+        """table rows of ids of `mode`; an id of another mode, of no mode or outside node_maps becomes row n (outside)"""
+        maps, row_ids = self.maps_host, self.row_ids_host[mode]
+        n = row_ids.shape[0]
+        inside = (ids >= 0) & (ids < maps.shape[0])
+        cand = np.where(inside, maps[np.where(inside, ids, 0)], -1)
+        ok = (cand >= 0) & (cand < n)
+        ok &= row_ids[np.where(ok, cand, 0)] == ids
+        return np.where(ok, cand, n)
+
+    def _csr(self, rel, src, dst):
+        if rel[0] not in self.mode_index or rel[2] not in self.mode_index or src.shape != dst.shape:
+            raise ValueError('KGIndex: relation %r names an unknown mode or its arrays differ in length' % (rel,))
+        n_src, n_dst = self.row_ids_host[rel[0]].shape[0], self.row_ids_host[rel[2]].shape[0]
+        s, d = self._rows_of(rel[0], src), self._rows_of(rel[2], dst)
+        if (s >= n_src).any() or (d >= n_dst).any():
+            raise IndexError('KGIndex: an edge of %r has an endpoint that is no entity of its mode' % (rel,))
+        order = np.argsort(s, kind='stable')
+        off = np.zeros(n_src + 1, dtype=np.int64)
+        np.cumsum(np.bincount(s, minlength=n_src), out=off[1:])
+        return off, np.ascontiguousarray(d[order], dtype=np.int64)
+
+    @classmethod
+    def from_graph(cls, graph, node_maps, device, lib=None):
+        """From graph.adj_lists ({relation: {node: neighbours}}) and graph.full_lists ({mode: ids})."""
+        if getattr(graph, 'adj_lists', None) is None:
+            raise ValueError('KGIndex.from_graph: the graph has no adjacency (use from_edges)')
+        edges = {}
+        for rel, adj in graph.adj_lists.items():
+            lens = np.fromiter((len(v) for v in adj.values()), dtype=np.int64, count=len(adj))
+            src = np.repeat(np.fromiter(adj.keys(), dtype=np.int64, count=len(adj)), lens)
+            dst = np.fromiter((x for v in adj.values() for x in v), dtype=np.int64, count=int(lens.sum()))
+            edges[tuple(rel)] = (src, dst)
+        return cls({m: graph.full_lists[m] for m in graph.full_lists}, edges, node_maps, device, lib)
+
+    @classmethod
+    def from_edges(cls, schema_or_modes, edges, node_maps, device, lib=None):
+        """From arrays: schema_or_modes is a synthetic.Schema or {mode: ids}; edges {(m1, name, m2): (src ids, dst ids)}.
+        A relation and its inverse are two entries (the index holds what it is given)."""
+        ids = getattr(schema_or_modes, 'ids', schema_or_modes)
+        return cls(ids, edges, node_maps, device, lib)
+
+    # ------------------------------------------------------------------------------------------ queries
+    def programme(self, formula):
+        hit = self._programmes.get(formula)
+        if hit is None:
+            branches, tail = query_hops(formula)
+
+            def code(rel):
+                if rel not in self.rel_index:
+                    raise KeyError('KGIndex: no adjacency for relation %r' % (rel,))
+                return self.rel_index[rel], self.mode_index[rel[2]]
+            prog = kg_programme([(self.mode_index[steps[0][0]], [code(r) for r in steps]) for _, steps in branches],
+                                [code(r) for r in tail], self.mode_index[formula.target_mode])
+            hit = self._programmes[formula] = (np.ascontiguousarray(prog), [slot for slot, _ in branches])
+        return hit
+
+    def anchor_rows(self, formula, queries_or_anchor_ids):
+        """[branches, B] int64 on the device: the table rows of the anchors"""
+        _, slots = self.programme(formula)
+        a = queries_or_anchor_ids
+        if torch.is_tensor(a):
+            a = a.detach().cpu().numpy()
+        elif len(a) and hasattr(a[0], 'anchor_nodes'):
+            a = [q.anchor_nodes for q in a]
+        ids = np.asarray(a, dtype=np.int64).reshape(-1, len(formula.anchor_modes))
+        rows = np.stack([self._rows_of(formula.anchor_modes[s], ids[:, s]) for s in slots]) if ids.shape[0] else \
+            np.zeros((len(slots), 0), dtype=np.int64)
+        return torch.from_numpy(np.ascontiguousarray(rows)).to(self.device)
+
+    def answers(self, formula, queries_or_anchor_ids, hard=False, global_bits=False):
+        """The exact answer sets of a batch of queries of one formula (Query objects, or anchor ids [B, anchors]) ->
+        KGAnswers. hard: also the hard negatives' sets (union of the branches minus the answers)."""
+        prog, _ = self.programme(formula)
+        rows = self.anchor_rows(formula, queries_or_anchor_ids)
+        return self.answers_of_rows(formula, prog, rows, hard, global_bits)
+
+    def answers_of_rows(self, formula, prog, anchor_rows, hard=False, global_bits=False):
+        """answers() from its two prepared inputs: the programme and the anchors' rows [branches, B] on the device (nothing
+        is translated or uploaded here). global_bits: the working bitmaps in the workspace whatever their size."""
+        mode = formula.target_mode
+        n = int(self.mode_rows[self.mode_index[mode]])
+        Q, W = int(anchor_rows.shape[1]), _words(n)
+        dev = self.device
+        bits = torch.empty((Q, W), dtype=torch.int32, device=dev)
+        hard_bits = torch.empty((Q, W), dtype=torch.int32, device=dev) if hard else None
+        counts = torch.empty((2, Q), dtype=torch.int64, device=dev)
+        if Q:
+            flags = _capi.KG_GLOBAL_BITS if global_bits else 0
+            with self._call() as (lib, stream):
+                need = lib.mpqe_kg_workspace_bytes(prog.ctypes.data, Q, self.mode_rows.ctypes.data, len(self.modes), flags)
+                if need == 0:
+                    raise ValueError('KGIndex.answers: programme outside what the kernel covers')
+                ws = torch.empty(need + 256, dtype=torch.uint8, device=dev)
+                _capi.check(lib, lib.mpqe_kg_answers(prog.ctypes.data, self._off_arr, self._rows_arr, self._edges_arr,
+                                                     len(self.rels), self.mode_rows.ctypes.data, len(self.modes),
+                                                     anchor_rows.data_ptr(), Q, bits.data_ptr(), ops._p(hard_bits),
+                                                     counts.data_ptr(), flags, _capi._align256(ws.data_ptr()), need,
+                                                     self.err.data_ptr(), stream), 'mpqe_kg_answers')
+        return KGAnswers(self, formula, mode, n, bits, hard_bits, counts)
+
+    def check(self):
+        """IndexError if a call since the last check met an anchor that is no entity of its mode (its query got empty
+        sets). One 4-byte read."""
+        ops.raise_on_flags(self.err)
+
+
+class KGAnswers(object):
+    """What KGIndex.answers returns. On the device: bits [Q, W] (the answers), hard_bits [Q, W] or None, counts [2, Q]
+    int64 (|answers|, |hard|); int32 tensors holding the uint32 words. Rows are table rows of `mode` (n of them)."""
+
+    def __init__(self, index, formula, mode, n, bits, hard_bits, counts):
+        self.index, self.formula, self.mode, self.n = index, formula, mode, n
+        self.bits, self.hard_bits, self.counts = bits, hard_bits, counts
+
+    def __len__(self):
+        return int(self.bits.shape[0])
+
+    def _compact(self, bits, select, lengths):
+        """(offsets [Q + 1], rows) int64 on the device: mpqe_kg_rows"""
+        Q = len(self)
+        dev = self.index.device
+        offsets = torch.zeros(Q + 1, dtype=torch.int64, device=dev)
+        if Q == 0:
+            return offsets, torch.zeros(0, dtype=torch.int64, device=dev)
+        torch.cumsum(lengths, 0, out=offsets[1:])
+        total = int(offsets[-1].item())
+        rows = torch.empty(total, dtype=torch.int64, device=dev)
+        with self.index._call() as (lib, stream):
+            _capi.check(lib, lib.mpqe_kg_rows(bits.data_ptr(), Q, self.n, self.index.valid[self.mode].data_ptr(), select,
+                                              offsets.data_ptr(), rows.data_ptr() if total else None, total,
+                                              self.index.err.data_ptr(), stream), 'mpqe_kg_rows')
+        return offsets, rows
+
+    def exclusion_csr(self):
+        """(offsets, rows): per query its answers and the rows below n that are no entity, ascending -- what
+        ops.rank_entities takes as `exclude` for the filtered setting."""
+        holes = self.n - self.index.num_entities[self.mode]
+        return self._compact(self.bits, _capi.KG_ROWS_WITH_HOLES, self.counts[0] + holes)
+
+    def _ids_csr(self, bits, select, lengths):
+        offsets, rows = self._compact(bits, select, lengths)
+        return self.index.row_ids[self.mode][rows], offsets
+
+    def answer_csr(self):
+        """(ids, offsets): the answers as global entity ids, CSR on the device"""
+        return self._ids_csr(self.bits, _capi.KG_ROWS_SET, self.counts[0])
+
+    def negative_csr(self):
+        """(ids, offsets): every entity of the mode that is no answer (full_sets[mode] - answers), the form
+        NegativeSampler.from_csr takes"""
+        return self._ids_csr(self.bits, _capi.KG_ROWS_COMPLEMENT, self.index.num_entities[self.mode] - self.counts[0])
+
+    def hard_csr(self):
+        if self.hard_bits is None:
+            raise ValueError('KGAnswers: computed without hard=True')
+        return self._ids_csr(self.hard_bits, _capi.KG_ROWS_SET, self.counts[1])
+
+    def _lists(self, words):
+        row_ids = self.index.row_ids_host[self.mode]
+        return [row_ids[r] for r in _unpack(words.cpu().numpy(), self.n)]
+
+    def lists(self):
+        """per query the answers as global entity ids (host arrays; for tests and small uses)"""
+        return self._lists(self.bits)
+
+    def hard_lists(self):
+        if self.hard_bits is None:
+            raise ValueError('KGAnswers: computed without hard=True')
+        return self._lists(self.hard_bits)
+
+    def negative_lists(self):
+        valid = self.index.valid[self.mode]
+        return self._lists(valid.unsqueeze(0) & ~self.bits)
+
+    def check(self):
+        self.index.check()

@@ -148,7 +148,14 @@ class _EntityRanking(object):
             if target_rows.shape[0] != B:
                 raise ValueError('one target per query')
         csr = None
-        if exclude is not None:
+        from .kg import KGAnswers
+        if isinstance(exclude, KGAnswers):
+            # exact answers from the device index (mpqe_amd/kg.py): the bitmaps OR the mode's holes, compacted on the device
+            if exclude.mode != mode or exclude.n != n or len(exclude) != B:
+                raise ValueError('exclude: KGAnswers of %d queries over %d rows of %r, ranking %d queries over %d rows of %r'
+                                 % (len(exclude), exclude.n, exclude.mode, B, n, mode))
+            csr = exclude.exclusion_csr()
+        elif exclude is not None:
             if len(exclude) != B:
                 raise ValueError('exclude must hold one id list per query')
             # one translation and one sort for the whole batch: keys (query, row), unique, then the segment bounds

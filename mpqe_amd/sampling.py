@@ -38,6 +38,29 @@ class NegativeSampler(object):
         self.hard = csr([h if h is not None else () for h in hard]) if any(h is not None for h in hard) else None
         self.err = ops.new_error_word(self.device)
 
+    @classmethod
+    def from_csr(cls, neg, hard, device, full_list=None):
+        """From candidate lists that are CSR already: neg / hard = (ids, offsets [n + 1]) int64 tensors or arrays, hard may
+        be None (kg.KGAnswers.negative_csr() / hard_csr() give them on the device: no Query object holds a Python list)."""
+        self = cls.__new__(cls)
+        self.device = torch.device(device)
+
+        def pair(p):
+            ids, off = (torch.as_tensor(a, dtype=torch.long).to(self.device).contiguous() for a in p)
+            if off.dim() != 1 or off.shape[0] < 1 or ids.dim() != 1:
+                raise ValueError('from_csr: (ids, offsets [n + 1])')
+            return ids, off
+        self.neg = pair(neg)
+        self.n = int(self.neg[1].shape[0]) - 1
+        self.hard = None if hard is None else pair(hard)
+        if self.hard is not None and self.hard[1].shape[0] != self.n + 1:
+            raise ValueError('from_csr: neg and hard must list the same queries')
+        self.shared = None
+        if full_list is not None:
+            self.shared = torch.as_tensor(np.asarray(list(full_list), dtype=np.int64)).to(self.device)
+        self.err = ops.new_error_word(self.device)
+        return self
+
     def sample(self, idx, seed, hard_negatives=False, out=None):
         """idx: int64 tensor / array of query positions (the batch). Returns the device tensor of negatives."""
         idx = torch.as_tensor(idx, dtype=torch.long).to(self.device)

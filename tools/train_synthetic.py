@@ -10,6 +10,7 @@ type), loss.backward(), Adam; evaluation by ROC-AUC with one sampled negative pe
     python tools/train_synthetic.py --kg aifb --embed-dim 128 --batch-size 512 --steps 300            # GPU only
     python tools/train_synthetic.py --kg small --embed-dim 64 --batch-size 64 --steps 300 --oracle    # both, compared
     python tools/train_synthetic.py --model gqe --kg small --embed-dim 64 --batch-size 64 --steps 300 # the GQE baseline
+    python tools/train_synthetic.py --model gqe --kg small --steps 300 --kg-index    # its filtered metrics through kg.KGIndex
 
 Prints one JSON line: loss curves, AUC before / after training on held-out queries of the same KG (both sides).
 Only tests/ and this tool's --oracle leg use oracle/ (the checker, never the thing trained or shipped).
@@ -102,6 +103,9 @@ def main(argv=None):
                     help="gqe: the baseline QueryEncoderDecoder (the reference's --model gqe) through the reference's loop body")
     ap.add_argument('--decoder', default='bilinear', help='gqe: metapath decoder (the reference\'s --decoder)')
     ap.add_argument('--inter-decoder', default='mean', help='gqe: mean | min | mean-simple | min-simple (--inter_decoder)')
+    ap.add_argument('--kg-index', action='store_true',
+                    help='gqe: the filtered metrics take their known answers from the device index (mpqe_amd/kg.py) instead of '
+                         'the host walk over the adjacency: same numbers')
     args = ap.parse_args(argv)
     if args.model == 'gqe':
         out = run_gqe(args)
@@ -341,6 +345,19 @@ def known_answers(args, schema, tq):
     return {q: synthetic._answers(adj, f, list(q.anchor_nodes))[0] for f in tq for q in tq[f]}
 
 
+def kg_index(args, schema, node_maps, device):
+    """The same adjacency as a kg.KGIndex on the device: eval_rank_queries(known_answers=index) answers each batch there."""
+    from mpqe_amd import synthetic
+    from mpqe_amd.kg import KGIndex
+    adj = synthetic.make_adjacency(schema, degree=args.degree, seed=args.seed)
+    edges = {}
+    for rel, lists in adj.items():
+        lens = np.fromiter((len(s) for s in lists.values()), dtype=np.int64, count=len(lists))
+        edges[rel] = (np.repeat(np.fromiter(lists.keys(), dtype=np.int64, count=len(lists)), lens),
+                      np.fromiter((d for s in lists.values() for d in s), dtype=np.int64, count=int(lens.sum())))
+    return KGIndex.from_edges(schema, edges, node_maps, device)
+
+
 def run_gqe(args):
     """The GQE baseline (QueryEncoderDecoder, bilinear paths + set intersection) through the reference's loop body
     (_reference_loop): margin_loss per batch on the fused kernels, loss.backward(), Adam; ROC-AUC and the filtered ranking
@@ -350,7 +367,7 @@ def run_gqe(args):
     device = torch.device('cuda:0')
     schema, graph, node_maps, model, train, test = build_gqe(args, device)
     tq = test_dict(test)
-    known = known_answers(args, schema, tq)
+    known = kg_index(args, schema, node_maps, device) if getattr(args, 'kg_index', False) else known_answers(args, schema, tq)
     order = [qt for qt, _ in __import__('mpqe_amd.synthetic', fromlist=['FULL_MIX']).FULL_MIX]
     query_types = list(dict.fromkeys(order))
 
@@ -382,7 +399,8 @@ def run_gqe(args):
                 batch_size=args.batch_size, steps=args.steps, train_seconds=train_s, loss_first=losses[0],
                 loss_last20=float(np.mean(losses[-20:])), auc_before=float(auc0), auc_after=float(auc1),
                 filtered_mrr_before=rank0['mrr'], filtered_mrr_after=rank1['mrr'], filtered_hits10_before=rank0['hits@10'],
-                filtered_hits10_after=rank1['hits@10'], loss_curve=losses)
+                filtered_hits10_after=rank1['hits@10'], known_answers='kg-index' if getattr(args, 'kg_index', False) else 'host',
+                loss_curve=losses)
 
 
 if __name__ == '__main__':
