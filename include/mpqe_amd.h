@@ -399,6 +399,14 @@ typedef struct {
     float readout_weight_decay;
 } mpqe_step_params_t;
 
+/* Alignment of the step's operands (mpqe_step_params_t, mpqe_step_grads_t, the ids, loss and scores). The level form
+ * takes any pointer aligned for its element type (4 bytes for the float operands): where a parameter, a table or a
+ * gradient buffer is not on a 16-byte boundary, or dim % 4 != 0, its kernels run their scalar forms. The chain form (dim
+ * 64 / 128 / 256) takes 16-byte aligned parameters and gradient buffers: a step whose PARAMETERS are not is planned as a
+ * level-form step (the size queries see them); GRADIENT buffers that are not (mode_emb, basis, root, bias, readout_*; and
+ * tables with a touch plan) make the call return MPQE_ERR_INVALID_ARG before anything is queued -- the form was chosen, and
+ * workspace and descriptors sized, before the gradients were known. MPQE_STEP_NO_CHAIN asks for the level form. Entity-table
+ * gradients added by atomics (touch = NULL), the ids, loss and the scores are scalar accesses in both forms.            */
 typedef struct {
     float *tables[MPQE_STEP_MAX_MODES];          /* NULL = not wanted                          */
     float *mode_emb;

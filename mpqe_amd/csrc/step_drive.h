@@ -49,7 +49,8 @@ struct StepCtx : StepCall {     // (upload_desc: possibly raised by the plan loo
     unsigned *notify, notify_value;
     LayerPtrs lp; GradPtrs gp;
     TablePtrs tabs; LossMeta lm;
-    int vec, vec_tab; bool fast;      // 16-byte rows of the weights / the tables; and whole tiles
+    int vec, vec_tab; bool fast;      // 16-byte rows of the weights / the tables and mode vectors; and whole tiles
+    int vec_grad;                     // 16-byte rows of every gradient buffer the reduction launch reads and writes
     const StepDev *sd;
     unsigned *epoch_f, *epoch_b;
     float *H, *GH, *VT, *WT, *slabs, *parts, *terms, *tpos, *tneg, *spos, *sneg;
@@ -103,6 +104,16 @@ static void step_flags(StepCtx &c) {
     c.notify = c.extra ? reinterpret_cast<unsigned *>(c.extra->notify) : nullptr;
     c.notify_value = c.extra ? c.extra->notify_value : 0u;
 }
+// every gradient buffer but the entity tables' on a 16-byte boundary (NULL: not wanted). readout: a learned readout's too
+// (the chain form's virtual layers; off the chain they are the dense layer's, which looks at its own pointers)
+static bool grads_vec_ok(const StepCall &c, bool readout) {
+    const mpqe_step_grads_t &G = *c.G;
+    uintptr_t bits = (uintptr_t)G.mode_emb;
+    for (int l = 0; l < c.P->num_layers; ++l) bits |= (uintptr_t)G.basis[l] | (uintptr_t)G.root[l] | (uintptr_t)G.bias[l];
+    if (readout && c.P->readout >= MPQE_READOUT_MLP)
+        bits |= (uintptr_t)G.readout_w0 | (uintptr_t)G.readout_b0 | (uintptr_t)G.readout_w2 | (uintptr_t)G.readout_b2;
+    return bits % 16 == 0;
+}
 // every argument check of the step, in front of its first queued operation
 static int step_check(const StepCtx &c) {
     const HostPlan &hp = *c.hp;
@@ -121,6 +132,9 @@ static int step_check(const StepCtx &c) {
     if (c.build_touch && (hp.ts_blocks <= 0 || (c.P->flags & MPQE_STEP_EIGHT_WAVES) || hp.nlanes > 1))
         return MPQE_ERR_UNSUPPORTED;        // (a step beyond TSORT_MAX_ENTRIES ids: build the plan at pack time)
     if (c.sparse_tables && c.backward && !c.use_touch) return MPQE_ERR_INVALID_ARG;      // (needs the touch plan and the chain form)
+    // (the chain form's kernels move whole 16-byte pieces of the gradient buffers; the level form takes any float pointer:
+    // step_resolve picks its scalar forms)
+    if (c.chain && c.backward && c.G && !grads_vec_ok(c, true)) return MPQE_ERR_INVALID_ARG;
     if (c.use_touch) {
         if ((uintptr_t)c.touch % 256 != 0) return MPQE_ERR_INVALID_ARG;
         for (int m = 0; m < c.P->num_modes; ++m)
@@ -170,7 +184,9 @@ static void step_resolve(StepCtx &c) {
             c.gp.root[hp.ro_layer + 1] = c.G->readout_w2; c.gp.bias[hp.ro_layer + 1] = c.G->readout_b2;
         }
     }
-    c.vec_tab = D % 4 == 0;
+    // (the assemble kernel reads the table rows and the mode vectors with the same loads)
+    c.vec_tab = D % 4 == 0 && (uintptr_t)c.P->mode_emb % 16 == 0;
+    c.vec_grad = D % 4 == 0 && (!c.backward || grads_vec_ok(c, c.chain));
     for (int m = 0; m < c.P->num_modes; ++m) {
         c.vec_tab = c.vec_tab && (uintptr_t)c.P->tables[m] % 16 == 0;
         c.tabs.table[m] = c.P->tables[m]; c.tabs.rows[m] = c.P->table_rows[m];
@@ -262,7 +278,7 @@ static void step_launch_args(StepCtx &c) {
         c.r_trows = (unsigned)((tblk + c.r_gx - 1) / c.r_gx);
     }
     ra.groups = at<const RGroup>(db, hp.o_groups); ra.ngroups = (int)hp.groups.size();
-    ra.D = D; ra.vec = (int)(D % 4 == 0); ra.zeroed = (c.P->flags & MPQE_STEP_ZERO_GRADS) ? 1 : 0;
+    ra.D = D; ra.vec = c.vec_grad; ra.zeroed = (c.P->flags & MPQE_STEP_ZERO_GRADS) ? 1 : 0;
     ra.gp = c.gp; ra.tabs = c.tabs; ra.lm = c.lm; ra.sd = c.sd;
     ra.slabs = c.slabs; ra.partial = c.parts; ra.VT = c.VT; ra.rank1 = at<const Rank1>(db, hp.o_rank1);
     ra.terms = c.terms; ra.bterms = c.bterms; ra.loss = c.loss;

@@ -86,8 +86,12 @@ def oracle_step(params, cfg, node_map, batches, margin):
 
 def run_step(be, schema, mode_ids, params, node_map, cfg, batches, margin, backward=1, lanes=None, flags=0, touch='step', repeat=1,
              plan_out=None, between=None, recover=False, before_recovery=None, dev_weights=False, query_out=None,
-             then_plain=False, xcd_shift=0, readout_norms=False):
-    """between: the step in three calls around the CALLER's readout (MPQE_READOUT_CALLER, MPQE_STEP_PHASE_*): a generator
+             then_plain=False, xcd_shift=0, readout_norms=False, place=None):
+    """place: where every operand lives -- place(be, name, array) returns the backend array (or a view of one, such as
+    tests/fenced.py: fenced()) that holds `array` and is used for be.ptr / be.get from then on. Names: 'P.<parameter key>' and
+    'P.node_map', 'G.<parameter key>' (array: the gradient buffer's initial content), 'anchor_ids', 'targets', 'negs', and the
+    outputs 'loss', 'scores_pos', 'scores_neg' (array: their initial NaN). Default: a private array from be.put.
+    between: the step in three calls around the CALLER's readout (MPQE_READOUT_CALLER, MPQE_STEP_PHASE_*): a generator
     function -- between(final_states) yields the query embeddings [graphs, D], is sent their gradients and yields d loss /
     d final states per batch; final_states[i]: batch i's [B N, D]. touch: 'step' = the step builds the touch plan of its ids itself (MPQE_STEP_BUILD_TOUCH, the product's default),
     'pack' = mpqe_step_touch_build in front of it, False = fp32 atomics. plan_out: a list that receives the plan's bytes."""
@@ -100,11 +104,17 @@ def run_step(be, schema, mode_ids, params, node_map, cfg, batches, margin, backw
     R = params['layers.0.basis'].shape[0]
     modes = list(schema.modes)
     dev = {}
+    if place is None:
+        place = lambda be_, name, array: be_.put(array)
 
     def put(key):
         if key not in dev:
-            dev[key] = be.put(params[key].detach().numpy())
+            dev[key] = place(be, 'P.' + key, params[key].detach().numpy())
         return dev[key]
+
+    def grad_buffer(key):      # (MPQE_STEP_ZERO_GRADS: the library must clear whatever is in the gradient buffers)
+        shape = tuple(params[key].shape)
+        return place(be, 'G.' + key, np.full(shape, 7.5 if flags & _capi.STEP_ZERO_GRADS else 0.0, np.float32))
     tables = [put('enc.feat-%s.weight' % m) for m in modes]
     # shared layers must alias ONE buffer, exactly like the reference's ModuleList of one module
     uniq = {}
@@ -114,7 +124,7 @@ def run_step(be, schema, mode_ids, params, node_map, cfg, batches, margin, backw
         if key not in uniq:
             uniq[key] = tuple(put('layers.%d.%s' % (l, k)) for k in ('basis', 'root', 'bias'))
         lay.append(uniq[key])
-    dnm = be.put(node_map.numpy())
+    dnm = place(be, 'P.node_map', node_map.numpy())
     dmode = put('mode_embeddings.weight')
     learned = between is None and cfg['readout'] in _capi.LEARNED_READOUT_IDS
     if between is not None or (learned and not (D in (64, 128, 256) and (cfg['readout'] != 'concat' or not cfg['adaptive']))):
@@ -124,16 +134,14 @@ def run_step(be, schema, mode_ids, params, node_map, cfg, batches, margin, backw
                                [params['enc.feat-%s.weight' % m].shape[0] for m in modes], be.ptr(dnm),
                                node_map.shape[0], be.ptr(dmode), [be.ptr(x[0]) for x in lay],
                                [be.ptr(x[1]) for x in lay], [be.ptr(x[2]) for x in lay], flags=flags)
-    gtabs = [be.zeros(tuple(params['enc.feat-%s.weight' % m].shape)) for m in modes]
-    gmode = be.zeros(tuple(params['mode_embeddings.weight'].shape))
-    glay_u = {k: (be.zeros((R, D, D)), be.zeros((D, D)), be.zeros((D,))) for k in uniq}
+    gtabs = [grad_buffer('enc.feat-%s.weight' % m) for m in modes]
+    gmode = grad_buffer('mode_embeddings.weight')
+    glay_u = {}
+    for l in range(L):
+        key = id(params['layers.%d.basis' % l])
+        if key not in glay_u:
+            glay_u[key] = tuple(grad_buffer('layers.%d.%s' % (l, k)) for k in ('basis', 'root', 'bias'))
     glay = [glay_u[id(params['layers.%d.basis' % l])] for l in range(L)]
-    if flags & _capi.STEP_ZERO_GRADS:     # the library must clear whatever is in the gradient buffers
-        for t in gtabs + [gmode] + [x for u in glay_u.values() for x in u]:
-            if be.name == 'emu':
-                t.fill(7.5)
-            else:
-                t.fill_(7.5)
     G = _capi.make_step_grads([be.ptr(t) for t in gtabs], be.ptr(gmode), [be.ptr(x[0]) for x in glay],
                               [be.ptr(x[1]) for x in glay], [be.ptr(x[2]) for x in glay])
     gro = {}
@@ -141,9 +149,7 @@ def run_step(be, schema, mode_ids, params, node_map, cfg, batches, margin, backw
         for field, key in (('readout_w0', 'readout.layers.0.weight'), ('readout_b0', 'readout.layers.0.bias'),
                            ('readout_w2', 'readout.layers.2.weight'), ('readout_b2', 'readout.layers.2.bias')):
             setattr(P, field, be.ptr(put(key)))
-            gro[key] = be.zeros(tuple(params[key].shape))
-            if flags & _capi.STEP_ZERO_GRADS:
-                gro[key].fill(7.5) if be.name == 'emu' else gro[key].fill_(7.5)
+            gro[key] = grad_buffer(key)
             setattr(G, field, be.ptr(gro[key]))
         P.readout_scatter = _capi.SCATTER_IDS[cfg['scatter_op']]
         P.readout_weight_decay = float(cfg.get('weight_decay', 0))
@@ -158,9 +164,9 @@ def run_step(be, schema, mode_ids, params, node_map, cfg, batches, margin, backw
                                       [modes.index(m) for m in f.anchor_modes], modes.index(f.target_mode),
                                       2.0 if dev_weights else b['weight'])
         anchors.append(np.ascontiguousarray(col['anchor_ids'].T).reshape(-1))
-    d_anchor = be.put(np.concatenate(anchors))
-    d_tg = be.put(np.concatenate([b['targets'] for b in batches]))
-    d_ng = be.put(np.concatenate([b['negs'] for b in batches]))
+    d_anchor = place(be, 'anchor_ids', np.concatenate(anchors))
+    d_tg = place(be, 'targets', np.concatenate([b['targets'] for b in batches]))
+    d_ng = place(be, 'negs', np.concatenate([b['negs'] for b in batches]))
     Gtot = sum(b['B'] for b in batches)
     keep = []
     if lanes is not None:
@@ -196,8 +202,9 @@ def run_step(be, schema, mode_ids, params, node_map, cfg, batches, margin, backw
     dsb = be.lib.mpqe_step_desc_bytes(ctypes.byref(P), SB, nb, lanes)
     dbuf = be.nbytes(dsb + 256)
     dptr = (be.ptr(dbuf) + 255) // 256 * 256
-    loss = be.empty((1 + nb,))
-    sp, sn = be.empty((Gtot,)), be.empty((Gtot,))
+    loss = place(be, 'loss', np.full((1 + nb,), np.nan, np.float32))
+    sp = place(be, 'scores_pos', np.full((Gtot,), np.nan, np.float32))
+    sn = place(be, 'scores_neg', np.full((Gtot,), np.nan, np.float32))
     err = be.zeros((1,), np.int32)
     tptr = None
     if touch:
