@@ -817,6 +817,62 @@ int mpqe_kg_answers(const int32_t *prog_host, const int64_t *const *rel_offsets_
 int mpqe_kg_rows(const uint32_t *bits, int64_t num_queries, int64_t n, const uint32_t *valid /*[W] or NULL*/, int select,
                  const int64_t *offsets /*[Q + 1]*/, int64_t *rows_out, int64_t rows_cap, int32_t *err, void *stream);
 
+/* ---- sampling on the KG index (csrc/kg_sample.hip) -- added under ABI 7: entries only --------------------------------
+ * Conventions of mpqe_kg_answers: every set, id and offset is in table ROWS; the *_host arrays are host arrays (of device
+ * pointers); a CSR offset or row outside its range ORs MPQE_FLAG_BAD_INDEX and is not followed; arguments are checked
+ * before any launch. Integer work only.
+ *
+ * The random stream. M = the splitmix64 finaliser of mpqe_sample_negatives (x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) *
+ * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) * 0x94D049BB133111EB; x ^ x >> 31; all mod 2^64). With base = M[seed ^ M[slot]]:
+ *   the walk          draw number d = 0, 1, ... of try t of a slot is  M[ M[base ^ t] ^ d ] % length
+ *   the row sampler   round r = 0 .. 7 of query q's Feistel network uses  M[ base ^ ((r + 1) << 32 | R) ] & (2^h - 1)
+ * Stateless: an output is a pure function of (seed, slot, the graph or set). tests/kg_sample_oracle.py restates both.
+ *
+ * mpqe_kg_sample_queries: grounded queries by the reference's random walk (Graph.sample_query_subgraph_bytype
+ * graph.py:321-389). The CSR arrays are mpqe_kg_answers'; rel_src_mode_host / rel_dst_mode_host [num_rels] the modes of
+ * every typed relation; rel_start_rows_host[i] -> int64 [rel_start_count_host[i]] on the device: relation i's source rows
+ * with a non-empty list, ascending. num_rels <= 4 096, num_modes <= 16, 1 <= max_tries <= 1 024.
+ * out [num_slots, MPQE_KG_QUERY_INTS] int64: [0] 1 = a query, 0 = none after max_tries; then the query's edges (source row,
+ * relation index, destination row) in the order of the reference's query tuple with nested tuples flattened (3-inter_chain:
+ * edge_1, edge_2, the edge from edge_2's neighbour; 3-chain_inter: the first edge, the two intersection edges). Unused
+ * ints, and everything behind a status of 0, are -1. The target is edge 0's source row.
+ * One try (draws in this order, each uniform by the stream above):
+ *   start   a relation among those with rel_start_count > 0 (in index order; a relation without edges is skipped, where
+ *           the reference's random.choice([]) would raise), then one of its start rows.
+ *   flat    the "flat adjacency" of row x of mode m is the concatenation, in relation-index order, of x's lists in every
+ *           relation whose source mode is m; a draw from it is uniform over its ENTRIES (graph.py:147-151).
+ *   edges   1-chain: 1 entry at the start; 2-chain / 3-chain: 1 at the start, then 1 at each neighbour in turn; 2-inter /
+ *           3-inter: 2 / 3 at the start; 3-inter_chain: 2 at the start, then 1 at the second's neighbour; 3-chain_inter:
+ *           1 at the start, 2 at its neighbour. Fewer entries than needed at a node rejects the try. The edges out of one
+ *           node are redrawn until their (relation, neighbour) pairs differ; since the index allows repeated entries an
+ *           edge gives up after 64 redraws and the try is rejected (a walk never spins).
+ * A corrupt offset / row rejects that try only. workspace: mpqe_kg_sample_workspace_bytes (0: arguments out of range),
+ * 8-byte aligned; the host writes the per-relation table into it on `stream` with every call. */
+#define MPQE_KG_QUERY_INTS 10
+size_t mpqe_kg_sample_workspace_bytes(int num_rels, int num_modes);
+int mpqe_kg_sample_queries(const int64_t *const *rel_offsets_host, const int64_t *const *rel_rows_host,
+                           const int64_t *rel_edges_host, const int32_t *rel_src_mode_host, const int32_t *rel_dst_mode_host,
+                           const int64_t *const *rel_start_rows_host, const int64_t *rel_start_count_host, int num_rels,
+                           const int64_t *mode_rows_host, int num_modes, int query_type, int64_t num_slots, int max_tries,
+                           uint64_t seed, int64_t *out /*[num_slots, 10] device*/, void *workspace, size_t workspace_bytes,
+                           int32_t *err, void *stream);
+
+/* mpqe_kg_rows with a bound: at most k members of every query's selected set (the reference's Query(neg_sample_max):
+ * random.sample of the negatives, graph.py:83-87). select: MPQE_KG_ROWS_SET or MPQE_KG_ROWS_COMPLEMENT
+ * (MPQE_KG_ROWS_WITH_HOLES: MPQE_ERR_INVALID_ARG). For query q with c selected members, m = min(k, c) rows are written to
+ * rows_out[offsets[q] .. offsets[q] + m); offsets[q + 1] - offsets[q] must be m (otherwise MPQE_FLAG_BAD_INDEX, and
+ * nothing is written outside the segment). c <= k: all members ascending, the bits of mpqe_kg_rows. c > k: k DISTINCT
+ * members, a uniform k-subset in the order j = 0 .. k - 1 of their draw: the member of rank P[j] for the bijection P of
+ * [0, c) keyed by (seed, q): with h the least integer >= 1 with 4^h >= c, x = j is split into L = x >> h, R = x & (2^h - 1),
+ * eight rounds (L, R) <- (R, L ^ F_r[R]) with F_r from the stream above, x = L << h | R, repeated while x >= c.
+ * 1 <= k <= MPQE_KG_SAMPLE_MAX_K, n <= MPQE_KG_SAMPLE_MAX_ROWS: MPQE_ERR_UNSUPPORTED above either; k < 1:
+ * MPQE_ERR_INVALID_ARG. */
+#define MPQE_KG_SAMPLE_MAX_K 1024
+#define MPQE_KG_SAMPLE_MAX_ROWS (1 << 22)
+int mpqe_kg_sample_rows(const uint32_t *bits, int64_t num_queries, int64_t n, const uint32_t *valid /*[W] or NULL*/,
+                        int select, const int64_t *offsets /*[Q + 1]*/, int64_t *rows_out, int64_t rows_cap, int k,
+                        uint64_t seed, int32_t *err, void *stream);
+
 /* The aggregate of the intersection on its own (decoders.py:293-298, 313-318: torch.stack + agg_func(dim = 0)): out[i] =
  * mean (agg 0) / min (agg 1) of x0[i], x1[i] and, unless NULL, x2[i]; count elements. Backward: the mean's gradient in equal
  * parts, the minimum's to the first branch that holds it; NULL gradient pointers are not written. */

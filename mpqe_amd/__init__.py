@@ -5,7 +5,7 @@ from .graph import Formula, Graph, Query  # noqa: F401
 __all__ = ['Formula', 'Graph', 'Query', 'RGCNConv', 'RGCNEncoderDecoder', 'DirectEncoder',
            'RGCNQueryDataset', 'MLPReadout', 'TargetMLPReadout', 'QueryEncoderDecoder', 'BilinearMetapathDecoder',
            'SetIntersection', 'SimpleSetIntersection', 'get_metapath_decoder', 'get_intersection_decoder',
-           'KGIndex', 'KGAnswers']
+           'KGIndex', 'KGAnswers', 'QuerySet']
 
 
 def __getattr__(name):
@@ -20,7 +20,7 @@ def __getattr__(name):
     if name in ('get_metapath_decoder', 'get_intersection_decoder'):
         from . import utils
         return getattr(utils, name)
-    if name in ('KGIndex', 'KGAnswers'):
+    if name in ('KGIndex', 'KGAnswers', 'QuerySet'):
         from . import kg
         return getattr(kg, name)
     if name == 'DirectEncoder':

@@ -113,6 +113,9 @@ PROTOTYPES = {
     'mpqe_kg_workspace_bytes': (Z, [P, L, P, I, I]),
     'mpqe_kg_answers': (I, [P, P, P, P, I, P, I, P, L, P, P, P, I, P, Z, P, P]),
     'mpqe_kg_rows': (I, [P, L, L, P, I, P, P, L, P, P]),
+    'mpqe_kg_sample_workspace_bytes': (Z, [I, I]),
+    'mpqe_kg_sample_queries': (I, [P, P, P, P, P, P, P, I, P, I, I, L, I, ctypes.c_uint64, P, P, Z, P, P]),
+    'mpqe_kg_sample_rows': (I, [P, L, L, P, I, P, P, L, I, ctypes.c_uint64, P, P]),
     'mpqe_branch_agg_fwd': (I, [P, P, P, L, I, P, P]),
     'mpqe_branch_agg_bwd': (I, [P, P, P, L, I, P, P, P, P, P]),
     'mpqe_debug_chain_stamps': (None, [P, Z]),
@@ -176,6 +179,8 @@ FLAG_BAD_NODE_ID, FLAG_BAD_EDGE, FLAG_BAD_RELATION, FLAG_BAD_INDEX = 1, 2, 4, 8
 FLAG_INTERNAL, FLAG_TOUCH_RETRY = 16, 32
 KG_GLOBAL_BITS = 1                                   # mpqe_kg_answers flags
 KG_ROWS_SET, KG_ROWS_COMPLEMENT, KG_ROWS_WITH_HOLES = 0, 1, 2       # mpqe_kg_rows select
+KG_QUERY_INTS = 10                                   # mpqe_kg_sample_queries: ints of one record
+KG_SAMPLE_MAX_K, KG_SAMPLE_MAX_ROWS = 1024, 1 << 22  # mpqe_kg_sample_rows
 
 
 def bind(cdll):

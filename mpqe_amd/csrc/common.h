@@ -45,6 +45,15 @@ __device__ __forceinline__ void flag_error(int32_t *err, int32_t bit) {
     if (err) atomicOr(err, bit);
 }
 
+// The library's counter-based random stream: splitmix64's finaliser over a counter (mpqe_sample_negatives in optim.hip, the
+// KG samplers in kg_sample.hip). Stateless, restated with Python ints by oracle/ref_cpu.py and tests/kg_sample_oracle.py.
+__host__ __device__ __forceinline__ unsigned long long mpqe_mix64(unsigned long long x) {
+    x += 0x9E3779B97F4A7C15ull;            // splitmix64
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+
 // A word handed between workgroups of ONE launch (they may sit on different XCDs, each with an L2 of its own): written
 // through / read at agent scope, no L2 write-back. (The host emulator runs a launch's workgroups one after the other.)
 template <typename T>

@@ -132,12 +132,7 @@ extern "C" int mpqe_sgd_step_guarded(float *param, const float *grad, int64_t n,
 // the draw is a counter-based hash of (seed, position in the batch): no state, reproducible on the CPU
 // (oracle/ref_cpu.py: sample_negatives). It is NOT python's Mersenne-Twister stream: same distribution
 // (uniform over the candidates), different numbers.
-__host__ __device__ __forceinline__ unsigned long long mpqe_mix64(unsigned long long x) {
-    x += 0x9E3779B97F4A7C15ull;            // splitmix64
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
+// (mpqe_mix64: common.h)
 
 __global__ __launch_bounds__(256) void sample_negatives_kernel(const long long *__restrict__ cand,
                                                                const long long *__restrict__ offsets,

@@ -9,6 +9,14 @@ is one launch.
     model.rank_targets(formula, queries, targets, exclude=ans)         # filtered ranking without host lists
     eval_rank_queries(test_queries, model, known_answers=index)
     NegativeSampler.from_csr(ans.negative_csr(), ans.hard_csr(), device)
+
+Sampling on the index (csrc/kg_sample.hip: mpqe_kg_sample_queries, mpqe_kg_sample_rows; reference Graph.sample_queries /
+sample_test_queries graph.py:227-260, sample_query_subgraph_bytype graph.py:321-389, Query(neg_sample_max) graph.py:83-87):
+
+    records = index.sample_queries('3-inter', 100000, seed)            # [count, 10] int64 on the device: the walk
+    ans.sample_negative_csr(100, seed), ans.sample_hard_csr(100, seed) # at most 100 negatives a query, on the device
+    sets = index.sample_query_sets(['2-chain', '3-inter'], 10000, seed, train_index=None)      # {Formula: QuerySet}
+    sets[f].negative_sampler(); sets[f].queries()
 """
 import contextlib
 import ctypes
@@ -17,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _capi, ops
-from .graph import reverse_relation
+from .graph import Formula, Query, reverse_relation
 
 PROG_INTS = ops.GQE_PROG_INTS
 MAX_MODES = 16
@@ -107,16 +115,22 @@ class KGIndex(object):
         self.mode_rows = np.asarray(mode_rows, dtype=np.int64)
         self.rels = [tuple(r) for r in edges]
         self.rel_index = {r: i for i, r in enumerate(self.rels)}
-        self.offsets, self.rows = [], []
+        self.offsets, self.rows, self.start_rows = [], [], []
         for rel in self.rels:
             src, dst = edges[rel]
             off, rows = self._csr(rel, np.asarray(src, dtype=np.int64).reshape(-1), np.asarray(dst, dtype=np.int64).reshape(-1))
             self.offsets.append(torch.from_numpy(off).to(self.device))
             self.rows.append(torch.from_numpy(rows).to(self.device))
+            self.start_rows.append(torch.from_numpy(np.nonzero(np.diff(off))[0].astype(np.int64)).to(self.device))
         R = max(len(self.rels), 1)
         self._off_arr = (ctypes.c_void_p * R)(*[t.data_ptr() for t in self.offsets])
         self._rows_arr = (ctypes.c_void_p * R)(*[t.data_ptr() if t.numel() else None for t in self.rows])
         self._edges_arr = (ctypes.c_int64 * R)(*[t.numel() for t in self.rows])
+        # what the walk takes besides the CSRs: every relation's modes and its source rows that have an edge
+        self.rel_src = np.asarray([self.mode_index[r[0]] for r in self.rels] or [0], dtype=np.int32)
+        self.rel_dst = np.asarray([self.mode_index[r[2]] for r in self.rels] or [0], dtype=np.int32)
+        self._start_arr = (ctypes.c_void_p * R)(*[t.data_ptr() if t.numel() else None for t in self.start_rows])
+        self._start_count = (ctypes.c_int64 * R)(*[t.numel() for t in self.start_rows])
         self._programmes = {}
         self.err = ops.new_error_word(self.device)
 
@@ -237,6 +251,107 @@ class KGIndex(object):
         sets). One 4-byte read."""
         ops.raise_on_flags(self.err)
 
+    # ------------------------------------------------------------------------------------------ sampling
+    def sample_queries(self, query_type, count, seed, max_tries=8):
+        """The reference's random walk (Graph.sample_query_subgraph_bytype) for `count` slots -> [count, 10] int64 on the
+        device: status (1 a query, 0 none after max_tries), then up to three edges (source row, relation index, destination
+        row) in the order of the reference's query tuple, -1 padded. A pure function of (seed, slot, the index)."""
+        qt = _capi.QUERY_TYPE_IDS[query_type] if isinstance(query_type, str) else int(query_type)
+        count = int(count)
+        out = torch.empty((count, _capi.KG_QUERY_INTS), dtype=torch.int64, device=self.device)
+        if count:
+            if not self.rels:
+                raise ValueError('KGIndex.sample_queries: the index has no relation')
+            with self._call() as (lib, stream):
+                need = lib.mpqe_kg_sample_workspace_bytes(len(self.rels), len(self.modes))
+                if need == 0:
+                    raise ValueError('KGIndex.sample_queries: more relations than the walk covers')
+                ws = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+                _capi.check(lib, lib.mpqe_kg_sample_queries(
+                    self._off_arr, self._rows_arr, self._edges_arr, self.rel_src.ctypes.data, self.rel_dst.ctypes.data,
+                    self._start_arr, self._start_count, len(self.rels), self.mode_rows.ctypes.data, len(self.modes), qt,
+                    count, int(max_tries), int(seed) & (2 ** 64 - 1), out.data_ptr(), _capi._align256(ws.data_ptr()), need,
+                    self.err.data_ptr(), stream), 'mpqe_kg_sample_queries')
+        return out
+
+    def _records_by_formula(self, qt_name, records):
+        """The accepted slots of a host [Q, 10] array grouped by formula -> {Formula: (slots, target rows [B], anchor rows
+        [B, A], variable rows [B, V])}; the same reading of the query tuple as graph.Query's."""
+        slots = np.nonzero(records[:, 0] == 1)[0]
+        n_edges = {'1-chain': 1, '2-chain': 2, '3-chain': 3, '2-inter': 2, '3-inter': 3, '3-inter_chain': 3,
+                   '3-chain_inter': 3}[qt_name]
+        e = records[slots, 1:1 + 3 * n_edges].reshape(-1, n_edges, 3)
+        out = {}
+        if slots.size == 0:
+            return out
+        keys, inverse = np.unique(e[:, :, 1], axis=0, return_inverse=True)
+        inverse = inverse.reshape(-1)
+        for g, rel_ids in enumerate(keys):
+            pick = np.nonzero(inverse == g)[0]
+            rels = [self.rels[int(r)] for r in rel_ids]
+            x, y = e[pick, :, 0], e[pick, :, 2]
+            if qt_name.endswith('-chain'):
+                formula, anchors, variables = Formula(qt_name, tuple(rels)), y[:, -1:], y[:, :-1]
+            elif qt_name.endswith('-inter'):
+                formula, anchors, variables = Formula(qt_name, tuple(rels)), y, y[:, :0]
+            elif qt_name == '3-inter_chain':
+                formula, anchors, variables = Formula(qt_name, (rels[0], (rels[1], rels[2]))), y[:, [0, 2]], y[:, 1:2]
+            else:
+                formula, anchors, variables = Formula(qt_name, (rels[0], (rels[1], rels[2]))), y[:, [1, 2]], y[:, 0:1]
+            out[formula] = (slots[pick], x[:, 0].copy(), np.ascontiguousarray(anchors), np.ascontiguousarray(variables))
+        return out
+
+    def sample_query_sets(self, query_types, per_type, seed, neg_sample_max=100, train_index=None, max_rounds=8,
+                          max_tries=8):
+        """The reference's Graph.sample_queries (train_index None) / sample_test_queries pipeline on the device: walk,
+        group the accepted slots by formula, one answers(hard=True) call per formula, keep a query only if it has a
+        negative (and, for the intersection types, a hard negative) and -- with train_index, an index of the same modes and
+        node map over the training edges -- only if its target does NOT answer it on the training graph; then at most
+        neg_sample_max negatives / hard negatives per kept query. Rounds repeat until `per_type` queries per type or
+        max_rounds. -> {Formula: QuerySet}. A pure function of (seed, the index)."""
+        sets = {}
+        for qt_name in query_types:
+            have, parts = 0, {}
+            type_seed = (int(seed) * 1000003 + 7919 * _capi.QUERY_TYPE_IDS[qt_name]) & (2 ** 63 - 1)
+            for rnd in range(int(max_rounds)):
+                want = int(per_type) - have
+                if want <= 0:
+                    break
+                slots = 2 * want + 64
+                records = self.sample_queries(qt_name, slots, type_seed + 104729 * rnd, max_tries).cpu().numpy()
+                groups = self._records_by_formula(qt_name, records)
+                kept = {}
+                for formula, (where, target, anchors, variables) in groups.items():
+                    prog, order = self.programme(formula)
+                    rows = torch.from_numpy(np.ascontiguousarray(anchors[:, order].T)).to(self.device)
+                    ans = self.answers_of_rows(formula, prog, rows, hard=True)
+                    ok = ans.counts[0] < self.num_entities[formula.target_mode]
+                    if 'inter' in qt_name:
+                        ok &= ans.counts[1] > 0
+                    t = torch.from_numpy(target).to(self.device)
+                    if train_index is not None:
+                        t_prog, _ = train_index.programme(formula)
+                        seen = train_index.answers_of_rows(formula, t_prog, rows).bits
+                        ok &= ((seen.gather(1, (t >> 5).unsqueeze(1)).squeeze(1) >> (t & 31)) & 1) == 0
+                    kept[formula] = (ans, ok.cpu().numpy())
+                accepted = np.sort(np.concatenate([groups[f][0][kept[f][1]] for f in groups] or [np.zeros(0, np.int64)]))
+                last = accepted[want - 1] if accepted.size >= want else slots
+                for k, formula in enumerate(groups):
+                    where, target, anchors, variables = groups[formula]
+                    ans, ok = kept[formula]
+                    pick = np.nonzero(ok & (where <= last))[0]
+                    if pick.size == 0:
+                        continue
+                    sub = ans.subset(torch.from_numpy(pick).to(self.device))
+                    draw = type_seed + 104729 * rnd + 15485863 * (k + 1)
+                    neg = sub.sample_negative_csr(neg_sample_max, draw)
+                    hard = sub.sample_hard_csr(neg_sample_max, draw + 1) if 'inter' in qt_name else None
+                    parts.setdefault(formula, []).append((target[pick], anchors[pick], variables[pick], neg, hard))
+                    have += pick.size
+            for formula, chunks in parts.items():
+                sets[formula] = QuerySet._from_parts(self, formula, chunks)
+        return sets
+
 
 class KGAnswers(object):
     """What KGIndex.answers returns. On the device: bits [Q, W] (the answers), hard_bits [Q, W] or None, counts [2, Q]
@@ -264,6 +379,42 @@ class KGAnswers(object):
                                               offsets.data_ptr(), rows.data_ptr() if total else None, total,
                                               self.index.err.data_ptr(), stream), 'mpqe_kg_rows')
         return offsets, rows
+
+    def subset(self, pick):
+        """the answers of the queries `pick` (a device index tensor) alone"""
+        return KGAnswers(self.index, self.formula, self.mode, self.n, self.bits[pick].contiguous(),
+                         None if self.hard_bits is None else self.hard_bits[pick].contiguous(),
+                         self.counts[:, pick].contiguous())
+
+    def _sample_ids_csr(self, bits, select, lengths, k, seed):
+        """(ids, offsets) on the device: mpqe_kg_sample_rows -- at most k members of every query's set"""
+        Q = len(self)
+        dev = self.index.device
+        k = int(k)
+        offsets = torch.zeros(Q + 1, dtype=torch.int64, device=dev)
+        if Q == 0:
+            return torch.zeros(0, dtype=torch.int64, device=dev), offsets
+        torch.cumsum(torch.clamp(lengths, max=k), 0, out=offsets[1:])
+        total = int(offsets[-1].item())
+        rows = torch.empty(total, dtype=torch.int64, device=dev)
+        with self.index._call() as (lib, stream):
+            _capi.check(lib, lib.mpqe_kg_sample_rows(bits.data_ptr(), Q, self.n, self.index.valid[self.mode].data_ptr(),
+                                                     select, offsets.data_ptr(), rows.data_ptr() if total else None, total,
+                                                     k, int(seed) & (2 ** 64 - 1), self.index.err.data_ptr(), stream),
+                        'mpqe_kg_sample_rows')
+        return self.index.row_ids[self.mode][rows], offsets
+
+    def sample_negative_csr(self, k, seed):
+        """negative_csr() with at most k ids a query (the reference's Query(neg_sample_max), graph.py:83-87): all of them
+        ascending where there are at most k, otherwise k distinct ones, a uniform subset, a pure function of (seed, the
+        query's position, its set). Q x k ids at most, where negative_csr() is Q x (entities of the mode)."""
+        return self._sample_ids_csr(self.bits, _capi.KG_ROWS_COMPLEMENT,
+                                    self.index.num_entities[self.mode] - self.counts[0], k, seed)
+
+    def sample_hard_csr(self, k, seed):
+        if self.hard_bits is None:
+            raise ValueError('KGAnswers: computed without hard=True')
+        return self._sample_ids_csr(self.hard_bits, _capi.KG_ROWS_SET, self.counts[1], k, seed)
 
     def exclusion_csr(self):
         """(offsets, rows): per query its answers and the rows below n that are no entity, ascending -- what
@@ -308,3 +459,65 @@ class KGAnswers(object):
 
     def check(self):
         self.index.check()
+
+
+class QuerySet(object):
+    """Grounded queries of one formula with their sampled negatives, on the device (KGIndex.sample_query_sets): targets [B],
+    anchors [B, A] and variables [B, V] as global entity ids, neg / hard = (ids, offsets [B + 1]) in the form
+    NegativeSampler.from_csr takes (hard None for the chain types)."""
+
+    def __init__(self, index, formula, targets, anchors, variables, neg, hard):
+        self.index, self.formula = index, formula
+        self.targets, self.anchors, self.variables, self.neg, self.hard = targets, anchors, variables, neg, hard
+
+    @classmethod
+    def _from_parts(cls, index, formula, chunks):
+        dev = index.device
+
+        def ids(mode_of_column, rows):
+            cols = [index.row_ids[m][torch.from_numpy(np.ascontiguousarray(rows[:, c])).to(dev)]
+                    for c, m in enumerate(mode_of_column)]
+            return torch.stack(cols, dim=1) if cols else torch.zeros((rows.shape[0], 0), dtype=torch.int64, device=dev)
+
+        def csr(pairs):
+            offsets, base = [torch.zeros(1, dtype=torch.int64, device=dev)], 0
+            for _, off in pairs:
+                offsets.append(off[1:] + base)
+                base += int(off[-1].item())
+            return torch.cat([p[0] for p in pairs]), torch.cat(offsets)
+        qt, rels = formula.query_type, formula.rels
+        if qt.endswith('-chain'):
+            var_modes = [r[2] for r in rels[:-1]]
+        elif qt == '3-inter_chain':
+            var_modes = [rels[1][0][2]]
+        elif qt == '3-chain_inter':
+            var_modes = [rels[0][2]]
+        else:
+            var_modes = []
+        target = np.concatenate([c[0] for c in chunks])
+        anchors = np.concatenate([c[1] for c in chunks])
+        variables = np.concatenate([c[2] for c in chunks])
+        return cls(index, formula, ids([formula.target_mode], target[:, None])[:, 0], ids(formula.anchor_modes, anchors),
+                   ids(var_modes, variables), csr([c[3] for c in chunks]),
+                   None if chunks[0][4] is None else csr([c[4] for c in chunks]))
+
+    def __len__(self):
+        return int(self.targets.shape[0])
+
+    def negative_sampler(self):
+        """NegativeSampler over the sampled lists; a 1-chain draws from the whole mode as the reference does (model.py:473)"""
+        from .sampling import NegativeSampler
+        full = None
+        if self.formula.query_type == '1-chain':
+            ids = self.index.row_ids_host[self.formula.target_mode]
+            full = ids[ids >= 0]
+        return NegativeSampler.from_csr(self.neg, self.hard, self.index.device, full_list=full)
+
+    def queries(self):
+        """graph.Query objects (host lists; for small sets: the drop-in loop and evaluation.eval_* take these)"""
+        from .synthetic import query_graph_tuple
+        t, a, v = self.targets.cpu().tolist(), self.anchors.cpu().tolist(), self.variables.cpu().tolist()
+        neg, neg_off = self.neg[0].cpu().tolist(), self.neg[1].cpu().tolist()
+        hard, hard_off = (None, None) if self.hard is None else (self.hard[0].cpu().tolist(), self.hard[1].cpu().tolist())
+        return [Query(query_graph_tuple(self.formula, t[i], a[i], v[i]), neg[neg_off[i]:neg_off[i + 1]],
+                      None if hard is None else hard[hard_off[i]:hard_off[i + 1]], keep_graph=True) for i in range(len(t))]

@@ -204,8 +204,9 @@ FULL_MIX = [('1-chain', False), ('2-chain', False), ('3-chain', False),
 
 # ----------------------------------------------------------------------------- grounded queries on a real adjacency
 # For end-task runs (tools/train_synthetic.py): queries whose target really answers them on `adj`, negatives that do
-# not. A minimal stand-in for the reference's KG sampler (mpqe/graph.py:227-473, out of scope): one random
-# walk per query, the answer set by following the inverse relations back from the anchors.
+# not. A minimal host stand-in for the reference's KG sampler (mpqe/graph.py:227-473), for graphs small enough for a
+# Python adjacency: one random walk per query, the answer set by following the inverse relations back from the anchors.
+# The sampler itself is kg.KGIndex.sample_query_sets, on the device index.
 def _answers(adj, formula, anchors):
     """All entities that answer the query (formula, anchors) on adj."""
     def back(rel, nodes):          # {x : some y in nodes with y in adj[rel][x]} = union of the inverse lists

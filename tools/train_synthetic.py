@@ -11,6 +11,7 @@ type), loss.backward(), Adam; evaluation by ROC-AUC with one sampled negative pe
     python tools/train_synthetic.py --kg small --embed-dim 64 --batch-size 64 --steps 300 --oracle    # both, compared
     python tools/train_synthetic.py --model gqe --kg small --embed-dim 64 --batch-size 64 --steps 300 # the GQE baseline
     python tools/train_synthetic.py --model gqe --kg small --steps 300 --kg-index    # its filtered metrics through kg.KGIndex
+    python tools/train_synthetic.py --model gqe --kg small --steps 300 --device-queries   # queries sampled on the device index
 
 Prints one JSON line: loss curves, AUC before / after training on held-out queries of the same KG (both sides).
 Only tests/ and this tool's --oracle leg use oracle/ (the checker, never the thing trained or shipped).
@@ -46,6 +47,9 @@ def build(args, device):
                                shared_layers=False, adaptive=args.readout == 'mp', weight_decay=0)
     rng = np.random.RandomState(args.seed + 1)
     train, test = {}, {}
+    if getattr(args, 'device_queries', False):
+        train, test = device_queries(args, schema, adj, node_maps, device)
+        return schema, graph, node_maps, model, train, test
     for qt in sorted(set(q for q, _ in synthetic.FULL_MIX)):
         train[qt], test[qt] = [], []
         for _ in range(args.formulas):
@@ -53,6 +57,51 @@ def build(args, device):
             train[qt].append((f, synthetic.sample_grounded_queries(schema, adj, f, args.train_queries, rng)))
             test[qt].append((f, synthetic.sample_grounded_queries(schema, adj, f, args.test_queries, rng)))
     return schema, graph, node_maps, model, train, test
+
+
+def device_queries(args, schema, adj, node_maps, device):
+    """--device-queries: the train / test sets through kg.KGIndex.sample_query_sets (the reference's Graph.sample_queries /
+    sample_test_queries on the device) instead of synthetic.sample_grounded_queries. A tenth of the edges is held out: the
+    training queries are walked on the rest, the test queries on the whole graph and kept only where the target does not
+    answer them on the training graph. The formulas are the ones the walk meets, --formulas x --train-queries /
+    --test-queries queries per type in all. args.query_sets keeps the training QuerySets (their device samplers)."""
+    from mpqe_amd import synthetic
+    from mpqe_amd.graph import reverse_relation
+    from mpqe_amd.kg import KGIndex
+    rng = np.random.RandomState(args.seed + 3)
+    full, kept = {}, {}
+    for rel in adj:
+        if rel in full:
+            continue
+        inv = reverse_relation(rel)
+        pairs = np.array([(n, d) for n in sorted(adj[rel]) for d in sorted(adj[rel][n])], dtype=np.int64).reshape(-1, 2)
+        keep = rng.rand(pairs.shape[0]) >= 0.1
+        full[rel], full[inv] = (pairs[:, 0], pairs[:, 1]), (pairs[:, 1], pairs[:, 0])
+        kept[rel], kept[inv] = (pairs[keep, 0], pairs[keep, 1]), (pairs[keep, 1], pairs[keep, 0])
+    index = KGIndex.from_edges(schema, full, node_maps, device)
+    train_index = KGIndex.from_edges(schema, kept, node_maps, device)
+    types = sorted(set(q for q, _ in synthetic.FULL_MIX))
+    t0 = time.perf_counter()
+    train_sets = train_index.sample_query_sets(types, args.formulas * args.train_queries, args.seed + 1)
+    test_sets = index.sample_query_sets(types, args.formulas * args.test_queries, args.seed + 2, train_index=train_index,
+                                        max_rounds=32)
+    index.check()
+    train_index.check()
+    torch.cuda.synchronize()
+    args.query_sets, args.sampling_seconds = {}, time.perf_counter() - t0
+    train, test = {qt: [] for qt in types}, {qt: [] for qt in types}
+    for f, qs in train_sets.items():
+        args.query_sets[(f.query_type, len(train[f.query_type]))] = qs
+        train[f.query_type].append((f, qs.queries()))
+    for f, qs in test_sets.items():
+        test[f.query_type].append((f, qs.queries()))
+    args.sampled = {'train_queries': sum(len(q) for v in train.values() for _, q in v),
+                    'test_queries': sum(len(q) for v in test.values() for _, q in v),
+                    'train_formulas': len(train_sets), 'test_formulas': len(test_sets), 'seconds': args.sampling_seconds}
+    missing = [qt for qt in types if not train[qt] or not test[qt]]
+    if missing:
+        raise RuntimeError('--device-queries: no query of %s found on this graph' % missing)
+    return train, test
 
 
 def schedule(args, train):
@@ -106,11 +155,16 @@ def main(argv=None):
     ap.add_argument('--kg-index', action='store_true',
                     help='gqe: the filtered metrics take their known answers from the device index (mpqe_amd/kg.py) instead of '
                          'the host walk over the adjacency: same numbers')
+    ap.add_argument('--device-queries', action='store_true',
+                    help='sample the train / test queries and their negatives on the device index (kg.KGIndex.sample_query_sets: '
+                         'the reference\'s KG sampler) instead of the host stand-in synthetic.sample_grounded_queries')
     args = ap.parse_args(argv)
     if args.model == 'gqe':
         out = run_gqe(args)
     else:
         out = run_dropin(args) if args.dropin else run(args)
+    if getattr(args, 'device_queries', False):
+        out['device_queries'] = args.sampled
     print(json.dumps(out))
     return out
 
@@ -129,6 +183,9 @@ def run(args):
     samplers = {}
     for qt in train:
         for fi, (f, qs) in enumerate(train[qt]):
+            if getattr(args, 'device_queries', False):
+                samplers[(qt, fi)] = args.query_sets[(qt, fi)].negative_sampler()         # the sampled CSRs, on the device
+                continue
             samplers[(qt, fi)] = NegativeSampler(qs, device, full_list=graph.full_lists[f.target_mode] if qt == '1-chain' else None)
     anchors = {(qt, fi): np.array([q.anchor_nodes for q in qs], dtype=np.int64) for qt in train for fi, (f, qs) in enumerate(train[qt])}
     targets = {(qt, fi): np.array([q.target_node for q in qs], dtype=np.int64) for qt in train for fi, (f, qs) in enumerate(train[qt])}
