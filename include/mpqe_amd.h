@@ -296,6 +296,16 @@ int mpqe_rank_entities(const float *q /*[Q, dim]*/, int64_t num_queries, const f
                        const int64_t *excl_offsets, const int64_t *excl_rows, int64_t num_excluded, int k /*0: no top-k*/,
                        int64_t *topk_rows, float *topk_scores, int64_t *rank, float *target_scores, void *workspace,
                        size_t workspace_bytes, int32_t *err, void *stream);
+/* The same call with the score chosen (added under ABI 7: an entry only). score_kind 0: the cosine above --
+ * mpqe_rank_entities is this call with 0. score_kind 1: score(i, r) = q[i] . table[r], the plain dot product the diagonal
+ * path decoder gives a chain query (mpqe_gqe_fwd, programme int [27]): the pre-pass writes 1.0f for both factors, so the
+ * score is the MFMA dot's own bits and eps is not read. Scores are then finite but unbounded and often negative; order,
+ * ties, exclusions, rank and top-k are as above. Another score_kind: MPQE_ERR_INVALID_ARG. */
+int mpqe_rank_entities_scored(const float *q, int64_t num_queries, const float *table, int64_t table_rows, int64_t dim,
+                              float eps, int score_kind, const int64_t *target_rows, const int64_t *excl_offsets,
+                              const int64_t *excl_rows, int64_t num_excluded, int k, int64_t *topk_rows, float *topk_scores,
+                              int64_t *rank, float *target_scores, void *workspace, size_t workspace_bytes, int32_t *err,
+                              void *stream);
 
 /* ---- fused training step -------------------------------------------------------------------
  * Forward + backward of RGCNEncoderDecoder.margin_loss (reference model.py:464-494) for ALL the
@@ -724,6 +734,15 @@ int mpqe_sample_negatives(const int64_t *cand, int64_t n_cand, const int64_t *of
  *   [6] table (mode) of the rows scored against   [8 + 5 b] table of branch b's ids, [9 + 5 b] its products (0..3),
  *       [10 + 5 b ..] their codes; [24 ..] the codes of the products after the intersection.
  *   A code is 2 * matrix index + T: T = 0 multiplies the row by M (decoders.py:145), T = 1 by M^T (project, decoders.py:150).
+ *   [7] path operator of every branch site and every site after the intersection: 0 matrix (above), 1 translate
+ *       (TransEMetapathDecoder decoders.py:181-208: row + v), 2 scale (BilinearDiagMetapathDecoder decoders.py:211-236:
+ *       row * v). With 1 or 2 such a site's code still carries the parameter index in code >> 1 (the low bit is ignored),
+ *       mats_host[index] is a [dim] vector (16-byte aligned) and grad_mats_host[index] its [dim] gradient; sites run in
+ *       programme order, ((x + v1) + v2) + v3. The pre / post matrices [3] / [4] stay [dim, dim] in the same arrays.
+ *   [27] scoring: 0 the cosine, 1 the plain dot product of the two rows (decoders.py:232: no norms, eps not read); -1, which
+ *       programmes written before this int existed carry, is the cosine.
+ *   Other values of [7] / [27]: MPQE_ERR_INVALID_ARG. Vector gradients: per-workgroup partial column sums over the p_rows
+ *   real rows (dY for translate, X * dY for scale), then one ordered pass, site after site in programme order.
  * tables_host / mats_host: host arrays of device pointers ([rows, dim] tables by mode; [dim, dim] matrices), 16-byte
  * aligned. p_ids [branches, p_rows]: the ids that pass through the matrices (chain form: p_rows = n; intersection form:
  * p_rows = B, n >= B); e_ids [e_rows] the other side (chain form: the B anchors; intersection form: e_rows = n). scores [n].

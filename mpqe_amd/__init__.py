@@ -4,7 +4,7 @@ from .graph import Formula, Graph, Query  # noqa: F401
 
 __all__ = ['Formula', 'Graph', 'Query', 'RGCNConv', 'RGCNEncoderDecoder', 'DirectEncoder',
            'RGCNQueryDataset', 'MLPReadout', 'TargetMLPReadout', 'QueryEncoderDecoder', 'BilinearMetapathDecoder',
-           'SetIntersection', 'SimpleSetIntersection', 'get_metapath_decoder', 'get_intersection_decoder',
+           'TransEMetapathDecoder', 'BilinearDiagMetapathDecoder', 'SetIntersection', 'SimpleSetIntersection', 'get_metapath_decoder', 'get_intersection_decoder',
            'KGIndex', 'KGAnswers', 'QuerySet']
 
 
@@ -14,7 +14,8 @@ def __getattr__(name):
     if name in ('RGCNConv', 'RGCNEncoderDecoder', 'MLPReadout', 'TargetMLPReadout', 'QueryEncoderDecoder'):
         from . import model
         return getattr(model, name)
-    if name in ('BilinearMetapathDecoder', 'SetIntersection', 'SimpleSetIntersection'):
+    if name in ('BilinearMetapathDecoder', 'TransEMetapathDecoder', 'BilinearDiagMetapathDecoder', 'SetIntersection',
+                'SimpleSetIntersection'):
         from . import decoders
         return getattr(decoders, name)
     if name in ('get_metapath_decoder', 'get_intersection_decoder'):

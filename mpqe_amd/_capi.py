@@ -106,6 +106,7 @@ PROTOTYPES = {
     'mpqe_hinge_bwd': (I, [P, P, L, F, P, P, P, P]),
     'mpqe_rank_workspace_bytes': (Z, [L, L, L, I]),
     'mpqe_rank_entities': (I, [P, L, P, L, L, F, P, P, P, L, I, P, P, P, P, P, Z, P, P]),
+    'mpqe_rank_entities_scored': (I, [P, L, P, L, L, F, I, P, P, P, L, I, P, P, P, P, P, Z, P, P]),
     'mpqe_gqe_workspace_bytes': (Z, [P, L, L, L]),
     'mpqe_gqe_fwd': (I, [P, P, P, I, P, L, P, I, L, P, L, P, L, P, P, L, F, I, P, P, Z, P, P]),
     'mpqe_gqe_bwd': (I, [P, P, P, I, P, L, P, I, L, P, L, P, L, P, P, L, F, P, P, P, P, Z, P, P]),

@@ -27,6 +27,18 @@
 // a matrix used at two sites gets both terms in that order). Entity-table rows: every looked-up row has one key; the
 // first entry of a key sums the entries of that key in entry order and adds the sum to the table gradient (one writer
 // per row, no float atomics: the same bits every run).
+//
+// Vector path operators (programme int [7]; reference decoders.py:181-236): with 1 (translate, TransE) or 2 (scale, the
+// diagonal bilinear form) every branch and tail site owns a [D] vector, not a matrix, and is one elementwise pass over the
+// tile in LDS, in place: x + v / x * v, site after site in programme order (three translations are ((x + v1) + v2) + v3).
+// The pre / post products of the intersection stay matrices. Programme int [27] = 1 scores by the plain dot product
+// (the diagonal decoder's chain form, decoders.py:228-233). Backward: translate passes dY on, scale gives dX = dY * v; a
+// vector's gradient is the column sum over the p_rows real rows of dY (translate) / X * dY (scale): every workgroup of
+// gqe_bwd_kernel adds its 16 rows in row order into one partial row per site, gqe_vec_final_kernel then adds the partial
+// rows in a fixed order (four row groups per column, then the four sums in group order) and the sites in programme order
+// into the caller's buffer: no float atomics, the same bits every run. Scale sites keep X; translate sites keep nothing,
+// neither keeps a dY. (The padded rows of the last tile carry a gradient of exactly zero -- nothing is scored against
+// them --, so leaving them out of the sum is a rule, not a correction.)
 #include <string.h>
 
 #include "gemm_core.h"
@@ -38,9 +50,11 @@
 #define GQ_SITE_PRE 9
 #define GQ_SITE_POST 12
 #define GQ_SITE_TAIL 13
+#define GQ_VEC_SITES 12       // branch and tail sites: the ones a vector operator can own
 
 struct GqeDev {
     int form, nb, agg, ntail, has_pre, has_post, D, save;
+    int op, dot;                   // path operator of the branch / tail sites (0 matrix, 1 translate, 2 scale); 1: dot scoring
     int bn[3], bT[3][3], tT[3];
     const float *tab[4];           // tables of the branch sources, then of the E side
     float *gtab[4];                // their gradients (backward; NULL = not wanted)
@@ -49,6 +63,7 @@ struct GqeDev {
     const float *w[GQ_SITES];
     long long x_off[GQ_SITES], dy_off[GQ_SITES];
     long long t_off[3], pfin_off, ge_off, key_off;
+    long long part_off[GQ_SITES];  // vector sites: [Rp16 / 16, D] partial column sums of the site's vector gradient
     const long long *node_map;
     long long map_len;
     const long long *p_ids, *e_ids, *qrow, *neg_off;
@@ -134,6 +149,51 @@ __device__ __forceinline__ void gq_mm(const float *src, float *dst, const float 
     }
 }
 
+// one vector site, in place: x + v (op 1) / x * v (op 2). Lane l holds v[4 l .. 4 l + 3] (one 16-byte global read per
+// wave), wave w walks rows w, w + 4, ... xsave != NULL: the input rows go to rows [i0, i0 + 16) of that [Rp16, D] state
+// first, from the thread that then changes them (the pass is in place: a separate gq_store would race with it).
+__device__ __forceinline__ void gq_vec(float *tile, int LDX, const float *v, int D, int op, float *xsave, long long i0) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane * 4;
+    if (c >= D) return;
+    const f32x4 w = gload4(v + c);
+    for (int i = wave; i < GQ_ROWS; i += 4) {
+        f32x4 x = *reinterpret_cast<const f32x4 *>(tile + i * LDX + c);
+        if (xsave) *reinterpret_cast<f32x4 *>(xsave + (i0 + i) * D + c) = x;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) x[u] = op == 1 ? x[u] + w[u] : x[u] * w[u];
+        *reinterpret_cast<f32x4 *>(tile + i * LDX + c) = x;
+    }
+}
+
+// the backward of one vector site on the tile of dY, in place: the workgroup's partial row of the vector's gradient (the
+// rows below Rp, in row order: padded rows hold no query) -> part; scale: dX = dY * v. Thread t < D / 4 owns 4 columns.
+__device__ __forceinline__ void gq_vec_bwd(float *tile, int LDX, const float *v, const float *X, float *part, long long i0,
+                                           long long Rp, int D, int op) {
+    const int c = threadIdx.x * 4;
+    if (c >= D) return;
+    f32x4 w = {1.f, 1.f, 1.f, 1.f}, s = {0.f, 0.f, 0.f, 0.f};
+    if (op == 2) w = gload4(v + c);
+    for (int i = 0; i < GQ_ROWS; ++i) {
+        f32x4 g = *reinterpret_cast<const f32x4 *>(tile + i * LDX + c);
+        if (i0 + i < Rp) {
+            if (op == 2) {
+                const f32x4 x = gload4(X + (i0 + i) * D + c);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) s[u] += x[u] * g[u];
+            } else {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) s[u] += g[u];
+            }
+        }
+        if (op == 2) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) g[u] *= w[u];
+            *reinterpret_cast<f32x4 *>(tile + i * LDX + c) = g;
+        }
+    }
+    *reinterpret_cast<f32x4 *>(part + (i0 / GQ_ROWS) * D + c) = s;
+}
+
 // tile -> rows [i0, i0 + 16) of a [Rp16, D] state
 __device__ __forceinline__ void gq_store(const float *tile, int LDX, float *g, long long i0, int D) {
     const int per = D / 4;
@@ -202,9 +262,31 @@ __device__ __forceinline__ float gq_cos(const f32x4 p, const f32x4 e, float eps,
     return s;
 }
 
+// the plain dot product (decoders.py:232); with g != NULL also the two gradients
+__device__ __forceinline__ float gq_dot(const f32x4 p, const f32x4 e, const float *g, f32x4 *gp, f32x4 *ge) {
+    const float dot = wave_sum(p[0] * e[0] + p[1] * e[1] + p[2] * e[2] + p[3] * e[3]);
+    if (g) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            (*gp)[u] = *g * e[u];
+            (*ge)[u] = *g * p[u];
+        }
+    }
+    return dot;
+}
+// (the score is a template parameter of the kernels, not a branch: the cosine instantiation's scoring code is the one it
+// was before the dot score existed, and gives the same bits)
+template <int DOT>
+__device__ __forceinline__ float gq_score(const GqeDev &G, const f32x4 p, const f32x4 e, const float *g, f32x4 *gp,
+                                          f32x4 *ge) {
+    if (DOT) return gq_dot(p, e, g, gp, ge);
+    return gq_cos(p, e, G.eps, g, gp, ge);
+}
+
 // EMBED = 0: the forward. EMBED = 1 (mpqe_gqe_embed): the same P side, then the rows the forward would score go to
 // `scores` as [Rp, D] -- no E side, no states; G.p_ids == NULL (one branch): P row r is row r of the branch's table.
-template <int EMBED>
+// DOT = 1: the pairs are scored by the plain dot product.
+template <int EMBED, int DOT>
 __global__ __launch_bounds__(256) void gqe_fwd_kernel(GqeDev G, float *__restrict__ scores) {
     __shared__ __attribute__((aligned(16))) float lds[3 * GQ_ROWS * GQ_LDXMAX];
     const int D = G.D, LDX = D + 4, per = D / 4;
@@ -218,6 +300,11 @@ __global__ __launch_bounds__(256) void gqe_fwd_kernel(GqeDev G, float *__restric
         __syncthreads();
         for (int s = 0; s < G.bn[b]; ++s) {
             const int site = 3 * b + s;
+            if (G.op) {
+                gq_vec(cur, LDX, G.w[site], D, G.op, save && G.op == 2 ? G.ws + G.x_off[site] : nullptr, i0);
+                __syncthreads();
+                continue;
+            }
             if (save) gq_store(cur, LDX, G.ws + G.x_off[site], i0, D);
             gq_mm(cur, nxt, G.w[site], D, LDX, G.bT[b][s], 0);
             __syncthreads();
@@ -259,6 +346,11 @@ __global__ __launch_bounds__(256) void gqe_fwd_kernel(GqeDev G, float *__restric
     }
     for (int s = 0; s < G.ntail; ++s) {
         const int site = GQ_SITE_TAIL + s;
+        if (G.op) {
+            gq_vec(cur, LDX, G.w[site], D, G.op, save && G.op == 2 ? G.ws + G.x_off[site] : nullptr, i0);
+            __syncthreads();
+            continue;
+        }
         if (save) gq_store(cur, LDX, G.ws + G.x_off[site], i0, D);
         gq_mm(cur, nxt, G.w[site], D, LDX, G.tT[s], 0);
         __syncthreads();
@@ -281,14 +373,14 @@ __global__ __launch_bounds__(256) void gqe_fwd_kernel(GqeDev G, float *__restric
         if (lane * 4 < D) p = *reinterpret_cast<const f32x4 *>(cur + i * LDX + lane * 4);
         if (G.form == 0) {
             if (q < G.n) {
-                const float s = gq_cos(p, gq_e_row(G, q, lane), G.eps, nullptr, nullptr, nullptr);
+                const float s = gq_score<DOT>(G, p, gq_e_row(G, q, lane), nullptr, nullptr, nullptr);
                 if (lane == 0) scores[q] = s;
             }
         } else if (q < G.Rp) {
             long long lo, hi;
             gq_neg_range(G, q, lane, lo, hi);
             for (long long r = q;;) {
-                const float s = gq_cos(p, gq_e_row(G, r, lane), G.eps, nullptr, nullptr, nullptr);
+                const float s = gq_score<DOT>(G, p, gq_e_row(G, r, lane), nullptr, nullptr, nullptr);
                 if (lane == 0) scores[r] = s;
                 r = r == q ? lo : r + 1;
                 if (r >= hi) break;
@@ -297,6 +389,7 @@ __global__ __launch_bounds__(256) void gqe_fwd_kernel(GqeDev G, float *__restric
     }
 }
 
+template <int DOT>
 __global__ __launch_bounds__(256) void gqe_bwd_kernel(GqeDev G, const float *__restrict__ gs) {
     __shared__ __attribute__((aligned(16))) float lds[3 * GQ_ROWS * GQ_LDXMAX];
     const int D = G.D, LDX = D + 4, per = D / 4;
@@ -315,7 +408,7 @@ __global__ __launch_bounds__(256) void gqe_bwd_kernel(GqeDev G, const float *__r
             if (q < G.n) {
                 f32x4 ge;
                 const float g = gs[q];
-                gq_cos(p, gq_e_row(G, q, lane), G.eps, &g, &gp, &ge);
+                gq_score<DOT>(G, p, gq_e_row(G, q, lane), &g, &gp, &ge);
                 if (lane * 4 < D) *reinterpret_cast<f32x4 *>(GE + (ge_e0 + q) * D + lane * 4) = ge;
             }
         } else if (q < G.Rp) {
@@ -324,7 +417,7 @@ __global__ __launch_bounds__(256) void gqe_bwd_kernel(GqeDev G, const float *__r
             for (long long r = q;;) {
                 f32x4 g1, ge;
                 const float g = gs[r];
-                gq_cos(p, gq_e_row(G, r, lane), G.eps, &g, &g1, &ge);
+                gq_score<DOT>(G, p, gq_e_row(G, r, lane), &g, &g1, &ge);
 #pragma unroll
                 for (int u = 0; u < 4; ++u) gp[u] += g1[u];
                 if (lane * 4 < D) *reinterpret_cast<f32x4 *>(GE + (ge_e0 + r) * D + lane * 4) = ge;
@@ -338,6 +431,11 @@ __global__ __launch_bounds__(256) void gqe_bwd_kernel(GqeDev G, const float *__r
 
     for (int s = G.ntail - 1; s >= 0; --s) {
         const int site = GQ_SITE_TAIL + s;
+        if (G.op) {
+            gq_vec_bwd(cur, LDX, G.w[site], G.ws + G.x_off[site], G.ws + G.part_off[site], i0, G.Rp, D, G.op);
+            __syncthreads();
+            continue;
+        }
         gq_store(cur, LDX, G.ws + G.dy_off[site], i0, D);
         gq_mm(cur, nxt, G.w[site], D, LDX, !G.tT[s], 0);
         __syncthreads();
@@ -391,6 +489,11 @@ __global__ __launch_bounds__(256) void gqe_bwd_kernel(GqeDev G, const float *__r
         }
         for (int s = G.bn[b] - 1; s >= 0; --s) {
             const int site = 3 * b + s;
+            if (G.op) {
+                gq_vec_bwd(cur, LDX, G.w[site], G.ws + G.x_off[site], G.ws + G.part_off[site], i0, G.Rp, D, G.op);
+                __syncthreads();
+                continue;
+            }
             gq_store(cur, LDX, G.ws + G.dy_off[site], i0, D);
             gq_mm(cur, nxt, G.w[site], D, LDX, !G.bT[b][s], 0);
             __syncthreads();
@@ -489,6 +592,40 @@ __global__ __launch_bounds__(256) void gqe_rows_kernel(GqeDev G, long long n_ent
     }
 }
 
+// The vector gradients from the workgroups' partial rows (gq_vec_bwd), the house form of bias_grad.h: one workgroup,
+// thread = (row group rg of 4, column); a row group adds every 4th partial row in order (eight loads in flight), the four
+// sums are added in group order, and the sites follow each other in programme order in the same thread -- a vector used at
+// two sites gets both terms in that order. A fixed order: the same bits every run.
+struct GqeVecFin {
+    const float *part[GQ_VEC_SITES];
+    float *grad[GQ_VEC_SITES];
+    int n;
+};
+
+__global__ __launch_bounds__(4 * GQ_MAXD) void gqe_vec_final_kernel(GqeVecFin F, long long nblk, int D) {
+    __shared__ float sums[4][GQ_MAXD];
+    const int col = threadIdx.x % GQ_MAXD, rg = threadIdx.x / GQ_MAXD;
+    for (int k = 0; k < F.n; ++k) {
+        float s = 0.f;
+        if (col < D)
+            for (long long b0 = rg; b0 < nblk; b0 += 4 * 8) {
+                float v[8];
+#pragma unroll
+                for (int q = 0; q < 8; ++q) {
+                    const long long b = b0 + 4 * q;
+                    v[q] = F.part[k][(b < nblk ? b : b0) * D + col];
+                }
+#pragma unroll
+                for (int q = 0; q < 8; ++q)
+                    if (b0 + 4 * q < nblk) s += v[q];
+            }
+        sums[rg][col] = s;
+        __syncthreads();
+        if (rg == 0 && col < D) F.grad[k][col] += ((sums[0][col] + sums[1][col]) + sums[2][col]) + sums[3][col];
+        __syncthreads();
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 struct GqeHost {
     GqeDev G;
@@ -496,6 +633,11 @@ struct GqeHost {
     int site_T[GQ_SITES];
     size_t lin_off, lin_bytes, total;
 };
+
+// whether site s holds a [D] vector under path operator op: the branch and tail sites do, the pre / post products never
+static bool gqe_vec_site(int op, int s) {
+    return op != 0 && (s < GQ_SITE_PRE || s >= GQ_SITE_TAIL);
+}
 
 static int gqe_step(int code, int num_mats, int *mat, int *T) {
     if (code < 0) return 1;
@@ -519,6 +661,10 @@ static int gqe_plan(const int32_t *prog, int num_tables, int num_mats, int64_t d
     G.D = (int)dim;
     if (G.form < 0 || G.form > 1 || G.nb < 1 || G.nb > 3 || G.agg < 0 || G.agg > 1 || G.ntail < 0 || G.ntail > 3)
         return MPQE_ERR_INVALID_ARG;
+    // ([27] = -1 is what programmes written before the dot score existed carry there: the cosine)
+    if (prog[7] < 0 || prog[7] > 2 || prog[27] < -1 || prog[27] > 1) return MPQE_ERR_INVALID_ARG;
+    G.op = prog[7];
+    G.dot = prog[27] == 1;
     if (G.form == 0 ? (p_rows != n || e_rows < 1) : (e_rows != n || n < p_rows)) return MPQE_ERR_INVALID_ARG;
     if (G.nb == 1 && (prog[3] >= 0 || prog[4] >= 0)) return MPQE_ERR_INVALID_ARG;
     for (int s = 0; s < GQ_SITES; ++s) H->site_mat[s] = -1;
@@ -563,8 +709,18 @@ static int gqe_plan(const int32_t *prog, int num_tables, int num_mats, int64_t d
     const long long blk = G.Rp16 * dim;
     long long off = 0;
     for (int s = 0; s < GQ_SITES; ++s) {
-        G.x_off[s] = G.dy_off[s] = -1;
+        G.x_off[s] = G.dy_off[s] = G.part_off[s] = -1;
         if (H->site_mat[s] < 0) continue;
+        if (gqe_vec_site(G.op, s)) {
+            // (a vector site: X only where the gradient reads it, and one partial row per workgroup)
+            if (G.op == 2) {
+                G.x_off[s] = off;
+                off += blk;
+            }
+            G.part_off[s] = off;
+            off += (long long)align_up((size_t)(G.Rp16 / GQ_ROWS) * (size_t)dim, 64);
+            continue;
+        }
         G.x_off[s] = off;
         G.dy_off[s] = off + blk;
         off += 2 * blk;
@@ -647,7 +803,12 @@ extern "C" int mpqe_gqe_fwd(const int32_t *prog_host, const float *const *tables
         if (!workspace || (uintptr_t)workspace % 256 != 0) return MPQE_ERR_INVALID_ARG;
         if (workspace_bytes < H.total) return MPQE_ERR_WORKSPACE;
     }
-    hipLaunchKernelGGL((gqe_fwd_kernel<0>), dim3((unsigned)(H.G.Rp16 / GQ_ROWS)), dim3(256), 0, as_stream(stream), H.G, scores);
+    if (H.G.dot)
+        hipLaunchKernelGGL((gqe_fwd_kernel<0, 1>), dim3((unsigned)(H.G.Rp16 / GQ_ROWS)), dim3(256), 0, as_stream(stream), H.G,
+                           scores);
+    else
+        hipLaunchKernelGGL((gqe_fwd_kernel<0, 0>), dim3((unsigned)(H.G.Rp16 / GQ_ROWS)), dim3(256), 0, as_stream(stream), H.G,
+                           scores);
     return mpqe_launch_status();
 }
 
@@ -668,7 +829,7 @@ extern "C" int mpqe_gqe_embed(const int32_t *prog_host, const float *const *tabl
     if (st != MPQE_OK) return st;
     if ((uintptr_t)out % 16 != 0) return MPQE_ERR_INVALID_ARG;
     if (!p_ids && (H.G.nb != 1 || p_rows > H.G.tab_rows[0])) return MPQE_ERR_INVALID_ARG;
-    hipLaunchKernelGGL((gqe_fwd_kernel<1>), dim3((unsigned)(H.G.Rp16 / GQ_ROWS)), dim3(256), 0, as_stream(stream), H.G, out);
+    hipLaunchKernelGGL((gqe_fwd_kernel<1, 0>), dim3((unsigned)(H.G.Rp16 / GQ_ROWS)), dim3(256), 0, as_stream(stream), H.G, out);
     return mpqe_launch_status();
 }
 
@@ -700,7 +861,10 @@ extern "C" int mpqe_gqe_bwd(const int32_t *prog_host, const float *const *tables
         if (g && (uintptr_t)g % 16 != 0) return MPQE_ERR_INVALID_ARG;
     }
     hipStream_t s = as_stream(stream);
-    hipLaunchKernelGGL(gqe_bwd_kernel, dim3((unsigned)(G.Rp16 / GQ_ROWS)), dim3(256), 0, s, G, grad_scores);
+    if (G.dot)
+        hipLaunchKernelGGL(gqe_bwd_kernel<1>, dim3((unsigned)(G.Rp16 / GQ_ROWS)), dim3(256), 0, s, G, grad_scores);
+    else
+        hipLaunchKernelGGL(gqe_bwd_kernel<0>, dim3((unsigned)(G.Rp16 / GQ_ROWS)), dim3(256), 0, s, G, grad_scores);
     if (any_table) {
         const long long n_ent = (long long)G.nb * G.Rp + G.n;
         hipLaunchKernelGGL(gqe_keys_kernel, dim3((unsigned)((n_ent + 255) / 256)), dim3(256), 0, s, G, n_ent);
@@ -710,8 +874,26 @@ extern "C" int mpqe_gqe_bwd(const int32_t *prog_host, const float *const *tables
     if (st != MPQE_OK) return st;
     // matrix gradients, site after site (stream order = programme order): Y = X . M^T: gM = dY^T . X; Y = X . M: gM = X^T . dY
     char *lin = reinterpret_cast<char *>(workspace) + H.lin_off;
+    if (G.op) {
+        // vector gradients: one launch, the sites in programme order inside it
+        GqeVecFin F;
+        F.n = 0;
+        for (int site = 0; site < GQ_SITES; ++site) {
+            if (H.site_mat[site] < 0 || !gqe_vec_site(G.op, site)) continue;
+            float *gv = grad_mats_host[H.site_mat[site]];
+            if (!gv) continue;
+            F.part[F.n] = G.ws + G.part_off[site];
+            F.grad[F.n] = gv;
+            ++F.n;
+        }
+        if (F.n > 0) {
+            hipLaunchKernelGGL(gqe_vec_final_kernel, dim3(1), dim3(4 * GQ_MAXD), 0, s, F, (long long)(G.Rp16 / GQ_ROWS), G.D);
+            st = mpqe_launch_status();
+            if (st != MPQE_OK) return st;
+        }
+    }
     for (int site = 0; site < GQ_SITES; ++site) {
-        if (H.site_mat[site] < 0) continue;
+        if (H.site_mat[site] < 0 || gqe_vec_site(G.op, site)) continue;
         float *gm = grad_mats_host[H.site_mat[site]];
         if (!gm) continue;
         const float *X = G.ws + G.x_off[site], *dY = G.ws + G.dy_off[site];

@@ -34,7 +34,8 @@ __device__ __forceinline__ float rank_score(float dot, float rinv, float qinv) {
 // ---------------------------------------------------------------------------------------------- pre-pass
 __global__ __launch_bounds__(256) void rank_prep_kernel(const float *__restrict__ q, long long Q,
                                                         const float *__restrict__ table, long long N, int D, float eps,
-                                                        float *__restrict__ rinv, float *__restrict__ qinv,
+                                                        int score_kind, float *__restrict__ rinv,
+                                                        float *__restrict__ qinv,
                                                         float *__restrict__ tsc, int *__restrict__ trow,
                                                         int *__restrict__ cnt, int *__restrict__ cntx) {
     const long long i = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -43,19 +44,20 @@ __global__ __launch_bounds__(256) void rank_prep_kernel(const float *__restrict_
     const bool is_q = i >= N;
     const float *v = is_q ? q + (i - N) * D : table + i * D;
     float ss = 0.f;
-    for (int c = lane; c < D; c += 64) ss += v[c] * v[c];
+    if (score_kind == 0)
+        for (int c = lane; c < D; c += 64) ss += v[c] * v[c];
     ss = wave_sum(ss);
     if (lane != 0) return;
     const float nrm = sqrtf(ss);
     if (is_q) {
         const long long j = i - N;
-        qinv[j] = 1.f / fmaxf(nrm, eps);
+        qinv[j] = score_kind ? 1.f : 1.f / fmaxf(nrm, eps);      // (dot: (dot * 1) * 1 is the dot's own bits; eps is not read)
         tsc[j] = -INFINITY;
         trow[j] = -1;
         cnt[j] = 0;
         cntx[j] = 0;
     } else {
-        rinv[i] = nrm > 0.f ? 1.f / nrm : 0.f;      // (a zero row has no direction: it scores 0)
+        rinv[i] = score_kind ? 1.f : (nrm > 0.f ? 1.f / nrm : 0.f);      // (a zero row has no direction: it scores 0)
     }
 }
 
@@ -463,13 +465,16 @@ static void rank_launch(const RankPlan &pl, const float *q, int64_t Q, const flo
                            pl.tiles_per_strip, cnt, cs, cr);
 }
 
-extern "C" int mpqe_rank_entities(const float *q, int64_t num_queries, const float *table, int64_t table_rows,
-                                  int64_t dim, float eps, const int64_t *target_rows, const int64_t *excl_offsets,
-                                  const int64_t *excl_rows, int64_t num_excluded, int k, int64_t *topk_rows,
-                                  float *topk_scores, int64_t *rank, float *target_scores, void *workspace,
-                                  size_t workspace_bytes, int32_t *err, void *stream) {
+// score_kind 1: score(i, r) = q[i] . table[r], the pre-pass writing 1.0f for both factors. Nothing after the pre-pass
+// knows a score's range: "no target" is trow < 0 and "no candidate" a row of -1 (the -inf beside them is never compared
+// as a score of a live entry), lists are ordered by float compares, so finite scores of any size and sign rank alike.
+extern "C" int mpqe_rank_entities_scored(const float *q, int64_t num_queries, const float *table, int64_t table_rows,
+                                         int64_t dim, float eps, int score_kind, const int64_t *target_rows,
+                                         const int64_t *excl_offsets, const int64_t *excl_rows, int64_t num_excluded, int k,
+                                         int64_t *topk_rows, float *topk_scores, int64_t *rank, float *target_scores,
+                                         void *workspace, size_t workspace_bytes, int32_t *err, void *stream) {
     const int64_t Q = num_queries, N = table_rows, E = num_excluded;
-    if (Q < 0 || N < 1 || dim <= 0 || k < 0 || E < 0) return MPQE_ERR_INVALID_ARG;
+    if (Q < 0 || N < 1 || dim <= 0 || k < 0 || E < 0 || score_kind < 0 || score_kind > 1) return MPQE_ERR_INVALID_ARG;
     if (Q == 0) return MPQE_OK;
     if (!q || !table) return MPQE_ERR_INVALID_ARG;
     if (k > 0 && (!topk_rows || !topk_scores)) return MPQE_ERR_INVALID_ARG;
@@ -488,7 +493,7 @@ extern "C" int mpqe_rank_entities(const float *q, int64_t num_queries, const flo
     const int64_t *off = E > 0 ? excl_offsets : nullptr;        // (no entries: nothing is excluded)
 
     hipLaunchKernelGGL(rank_prep_kernel, dim3((unsigned)((N + Q + 3) / 4)), dim3(256), 0, s, q, (long long)Q, table,
-                       (long long)N, D, eps, rinv, qinv, tsc, trow, cnt, cntx);
+                       (long long)N, D, eps, score_kind, rinv, qinv, tsc, trow, cnt, cntx);
     const bool vec = ptr_vec_ok(q, dim) && ptr_vec_ok(table, dim);
     if (vec && dim % GT_BK == 0)
         rank_launch<LD_FAST>(pl, q, Q, table, N, D, target_rows, off, excl_rows, E, k, rinv, qinv, tsc, trow, cnt, cntx,
@@ -504,4 +509,14 @@ extern "C" int mpqe_rank_entities(const float *q, int64_t num_queries, const flo
                            (const float *)cs, (const int *)cr, (const float *)tsc, (const int *)trow, (const int *)cnt,
                            (const int *)cntx, (long long *)topk_rows, topk_scores, (long long *)rank, target_scores);
     return mpqe_launch_status();
+}
+
+extern "C" int mpqe_rank_entities(const float *q, int64_t num_queries, const float *table, int64_t table_rows,
+                                  int64_t dim, float eps, const int64_t *target_rows, const int64_t *excl_offsets,
+                                  const int64_t *excl_rows, int64_t num_excluded, int k, int64_t *topk_rows,
+                                  float *topk_scores, int64_t *rank, float *target_scores, void *workspace,
+                                  size_t workspace_bytes, int32_t *err, void *stream) {
+    return mpqe_rank_entities_scored(q, num_queries, table, table_rows, dim, eps, 0, target_rows, excl_offsets, excl_rows,
+                                     num_excluded, k, topk_rows, topk_scores, rank, target_scores, workspace, workspace_bytes,
+                                     err, stream);
 }

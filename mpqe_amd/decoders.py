@@ -1,8 +1,9 @@
-"""The GQE baseline's decoders with the reference's interface (mpqe/decoders.py): the bilinear metapath decoder and the
-two set-intersection operators. Embeddings are columns ([D, B]) at this interface, as in the reference; each forward /
+"""The GQE baseline's decoders with the reference's interface (mpqe/decoders.py): the three metapath decoders (bilinear,
+TransE, diagonal bilinear) and the two set-intersection operators. Embeddings are columns ([D, B]) at this interface, as in the reference; each forward /
 project runs on the library's kernels through ops.linear / ops.cosine / ops.branch_agg. `QueryEncoderDecoder`
 (mpqe_amd/model.py) calls them only on its composed path: its fused path reads their parameters and runs one launch.
 """
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.init as init
@@ -34,6 +35,56 @@ class BilinearMetapathDecoder(nn.Module):
     def project(self, embeds, rel):
         """M[rel] . embeds (decoders.py:149-150)."""
         return ops.linear(embeds.t(), self.mats[tuple(rel)]).t()
+
+
+class _VectorMetapathDecoder(nn.Module):
+    """One [D] vector per relation triple (reference decoders.py:188-197, 217-226: the bilinear decoder's creation order
+    and parameter names, uniform(-6 / sqrt(D), 6 / sqrt(D))). forward / project are plain differentiable tensor ops: the
+    composed path of `QueryEncoderDecoder`; its fused path reads `vecs`, `op` and `score` and runs one launch."""
+    op = None           # ops.gqe_programme's path operator
+    score = None        # how forward() scores a chain: 'cosine' | 'dot'
+
+    def __init__(self, relations, dims):
+        super(_VectorMetapathDecoder, self).__init__()
+        self.relations = relations
+        self.vecs = {}
+        for r1 in relations:
+            for r2 in relations[r1]:
+                rel = (r1, r2[1], r2[0])
+                self.vecs[rel] = nn.Parameter(torch.FloatTensor(dims[rel[0]]))
+                bound = 6.0 / np.sqrt(dims[rel[0]])
+                init.uniform_(self.vecs[rel], a=-bound, b=bound)
+                self.register_parameter('_'.join(rel), self.vecs[rel])
+
+
+class TransEMetapathDecoder(_VectorMetapathDecoder):
+    """reference decoders.py:181-208: a relation translates, a metapath adds its vectors one after another."""
+    op, score = 'translate', 'cosine'
+
+    def forward(self, embeds1, embeds2, rels):
+        """cos(embeds2, ((embeds1 + v[rels[0]]) + v[rels[1]]) ...) per column pair (decoders.py:200-205; the reference adds
+        in place into embeds1, which changes no value)."""
+        act = embeds1
+        for i_rel in rels:
+            act = act + self.vecs[tuple(i_rel)].unsqueeze(1)
+        return nn.functional.cosine_similarity(embeds2, act, dim=0)
+
+    def project(self, embeds, rel):
+        return embeds + self.vecs[tuple(rel)].unsqueeze(1)
+
+
+class BilinearDiagMetapathDecoder(_VectorMetapathDecoder):
+    """reference decoders.py:211-236: a relation scales, and a chain is scored by the plain dot product (no cosine)."""
+    op, score = 'scale', 'dot'
+
+    def forward(self, embeds1, embeds2, rels):
+        act = embeds1
+        for i_rel in rels:
+            act = act * self.vecs[tuple(i_rel)].unsqueeze(1)
+        return (act * embeds2).sum(0)
+
+    def project(self, embeds, rel):
+        return embeds * self.vecs[tuple(rel)].unsqueeze(1)
 
 
 def _agg_kind(agg_func):

@@ -119,7 +119,8 @@ class _EntityRanking(object):
 
     def _rank_rows(self, formula, queries, target_nodes, exclude, k, operands):
         """Every entity of formula.target_mode ranked for each query: (ids [B, k] or None, scores, ranks [B] or None).
-        operands(n) -> (q [B, D], candidates [n, D]): the two sides of ops.rank_entities over the mode's first n rows."""
+        operands(n) -> (q [B, D], candidates [n, D]) or (q, candidates, score): the two sides of ops.rank_entities over the
+        mode's first n rows, and its score kind ('cosine' when left out)."""
         enc = self.enc
         if not (hasattr(enc, 'table') and getattr(enc, 'node_maps', None) is not None):
             raise NotImplementedError('answering a query needs the entity tables (DirectEncoder with node_maps)')
@@ -176,8 +177,8 @@ class _EntityRanking(object):
                 off = torch.arange(B + 1, dtype=torch.int64) * holes.size
                 hit = cache[('holes', mode)] = (B, (off.to(device), torch.from_numpy(np.tile(holes, B)).to(device)))
             csr = hit[1]
-        q, table = operands(n)
-        topr, tops, rank, _ = ops.rank_entities(q, table, target_rows, csr, k, err=err)
+        q, table, score = (tuple(operands(n)) + ('cosine',))[:3]
+        topr, tops, rank, _ = ops.rank_entities(q, table, target_rows, csr, k, err=err, score=score)
         self._check()
         ids = None
         if topr is not None:
@@ -583,8 +584,9 @@ class QueryEncoderDecoder(nn.Module, _EntityRanking):
     inter_dec.*).
 
     fused = True: forward() is ONE ops.gqe_scores call (mpqe_gqe_fwd / mpqe_gqe_bwd, csrc/gqe.hip) and margin_loss() one
-    for targets and negatives together. Taken with a DirectEncoder that has node_maps, a BilinearMetapathDecoder, a
-    SetIntersection / SimpleSetIntersection, parameters on the GPU and a shape the kernel covers (one D for every mode,
+    for targets and negatives together. Taken with a DirectEncoder that has node_maps, a BilinearMetapathDecoder,
+    TransEMetapathDecoder or BilinearDiagMetapathDecoder (the path operator and the parameters come from the decoder's
+    type: matrices `mats`, or vectors `vecs` that translate / scale), a SetIntersection / SimpleSetIntersection, parameters on the GPU and a shape the kernel covers (one D for every mode,
     a multiple of 16 up to 256). Everything else -- and fused = False -- takes the composed path: the decoders' own
     forward / project, one library call per product.
 
@@ -592,9 +594,11 @@ class QueryEncoderDecoder(nn.Module, _EntityRanking):
     ops.rank_entities call, as on RGCNEncoderDecoder. An intersection formula's B query embeddings come from
     ops.gqe_embed (mpqe_gqe_embed: the forward's P side alone) and are ranked against the mode's table. In a chain formula
     the rows that pass through the matrices are the candidates, and they depend on the formula alone: the mode's table is
-    projected ONCE ([n, D], not once per query) and the B normalised anchors are ranked against it. In eval() mode that
+    projected ONCE ([n, D], not once per query) and the B normalised anchors are ranked against it -- by the cosine, or by
+    the dot product under the diagonal decoder, whose chains forward() scores that way. In eval() mode that
     projection is kept for the next call (one entry, self.__dict__['_cand']: copies and pickles drop it), keyed on the
-    chain's relations, the target mode, the device and data_ptr() / _version of the table and of every matrix used; in
+    chain's relations, the target mode, the device and data_ptr() / _version of the table and of every matrix or vector
+    used; in
     train() mode it is always recomputed. Code that writes parameters through raw pointers (no version bump) must switch
     to train() or set model.__dict__['_cand'] = None."""
 
@@ -643,30 +647,51 @@ class QueryEncoderDecoder(nn.Module, _EntityRanking):
     def _plan(self, formula):
         return gqe_plan(formula)
 
+    def _path_kind(self):
+        """(path operator, the decoder's parameters by relation, chain score) from the type of path_dec, or None for a
+        decoder the fused kernel does not know."""
+        from .decoders import BilinearDiagMetapathDecoder, BilinearMetapathDecoder, TransEMetapathDecoder
+        kind = type(self.path_dec)
+        if kind is BilinearMetapathDecoder:
+            return 'matrix', self.path_dec.mats, 'cosine'
+        if kind in (TransEMetapathDecoder, BilinearDiagMetapathDecoder):
+            return self.path_dec.op, self.path_dec.vecs, self.path_dec.score
+        return None
+
+    def _plan_score(self, plan):
+        """How forward() scores this plan's pairs: the decoder's own score on a chain (model.py:80-83 hands a chain to
+        path_dec.forward), the model's cosine on every intersection form (model.py:104, 115)."""
+        return getattr(self.path_dec, 'score', 'cosine') if plan[0] == 0 else 'cosine'
+
     def _fused_ok(self, plan):
-        from .decoders import BilinearMetapathDecoder, SetIntersection, SimpleSetIntersection
+        from .decoders import SetIntersection, SimpleSetIntersection
         enc = self.enc
         if not self.fused or not (hasattr(enc, 'table') and getattr(enc, 'node_maps', None) is not None):
             return False
-        if type(self.path_dec) is not BilinearMetapathDecoder or type(self.inter_dec) not in (SetIntersection,
-                                                                                            SimpleSetIntersection):
+        kind = self._path_kind()
+        if kind is None or type(self.inter_dec) not in (SetIntersection, SimpleSetIntersection):
             return False
         if self._device().type != 'cuda':
             return False
+        op, path, _ = kind
         form, branches, imode, tail, emode = plan
         dims = {enc.table(m).shape[1] for _, m, _ in branches} | {enc.table(emode).shape[1]}
-        mats = [self.path_dec.mats[r] for _, _, steps in branches for r, _ in steps] + [self.path_dec.mats[r] for r, _ in tail]
+        used = [path[r] for _, _, steps in branches for r, _ in steps] + [path[r] for r, _ in tail]
+        mats = []
         if imode is not None and isinstance(self.inter_dec, SetIntersection):
             mats += [self.inter_dec.pre_mats[imode], self.inter_dec.post_mats[imode]]
         if len(dims) != 1:
             return False
         D = next(iter(dims))
-        return ops.gqe_supported(D) and all(tuple(m.shape) == (D, D) for m in mats)
+        want = (D, D) if op == 'matrix' else (D,)
+        return (ops.gqe_supported(D) and all(tuple(p.shape) == want for p in used)
+                and all(tuple(m.shape) == (D, D) for m in mats))
 
     def _programme(self, plan):
-        """(programme of mpqe_gqe_fwd / mpqe_gqe_embed, the modes of its tables, its matrices) of one plan."""
+        """(programme of mpqe_gqe_fwd / mpqe_gqe_embed, the modes of its tables, its matrices / vectors) of one plan."""
         from .decoders import SetIntersection
         form, branches, imode, tail, emode = plan
+        op, path, _ = self._path_kind()
         modes, mats, mat_ids = [], [], {}
 
         def table_of(mode):
@@ -680,13 +705,15 @@ class QueryEncoderDecoder(nn.Module, _EntityRanking):
                 mats.append(param)
             return mat_ids[id(param)]
 
-        prog_branches = [(table_of(m), [(mat_of(self.path_dec.mats[r]), t) for r, t in steps]) for _, m, steps in branches]
-        prog_tail = [(mat_of(self.path_dec.mats[r]), t) for r, t in tail]
+        prog_branches = [(table_of(m), [(mat_of(path[r]), t) for r, t in steps]) for _, m, steps in branches]
+        prog_tail = [(mat_of(path[r]), t) for r, t in tail]
         pre = post = -1
         if imode is not None and isinstance(self.inter_dec, SetIntersection):
             pre, post = mat_of(self.inter_dec.pre_mats[imode]), mat_of(self.inter_dec.post_mats[imode])
         agg = self.inter_dec.agg_kind if imode is not None else 'mean'
-        return ops.gqe_programme(form, prog_branches, table_of(emode), agg, pre, post, prog_tail), modes, mats
+        prog = ops.gqe_programme(form, prog_branches, table_of(emode), agg, pre, post, prog_tail, op=op,
+                                 score=self._plan_score(plan))
+        return prog, modes, mats
 
     def _fused_scores(self, formula, queries, target_nodes, neg_nodes, neg_lengths, plan):
         form, branches, imode, tail, emode = plan
@@ -732,11 +759,15 @@ class QueryEncoderDecoder(nn.Module, _EntityRanking):
             q_row = torch.cat([torch.arange(B), torch.repeat_interleave(torch.arange(B), lengths)]).to(self._device())
         target_embeds = self.enc(target_nodes, formula.target_mode)
         if form == 0:
+            anchors = self.enc(_anchor_ids(queries, 0), formula.anchor_modes[0])
+            if hasattr(self.path_dec, 'vecs'):
+                # (the vector decoders' own forward: plain tensor ops, one anchor column per scored pair)
+                return self.path_dec(target_embeds, anchors if q_row is None else anchors[:, q_row],
+                                     [rel for rel, _ in branches[0][2]])
             act = target_embeds.t()
             for rel, _ in branches[0][2]:
                 act = ops.linear(act, self.path_dec.mats[rel].t())
-            anchors = self.enc(_anchor_ids(queries, 0), formula.anchor_modes[0]).t()
-            return ops.cosine(anchors, act, q_row=q_row)
+            return ops.cosine(anchors.t(), act, q_row=q_row)
         return ops.cosine(self._composed_query(queries, plan).t(), target_embeds.t(), q_row=q_row)
 
     def _composed_query(self, queries, plan):
@@ -772,7 +803,8 @@ class QueryEncoderDecoder(nn.Module, _EntityRanking):
             return project()
         steps = plan[1][0][2]
         table = self.enc.table(plan[1][0][1])
-        used = [table] + [self.path_dec.mats[r] for r, _ in steps]
+        path = self.path_dec.vecs if hasattr(self.path_dec, 'vecs') else self.path_dec.mats
+        used = [table] + [path[r] for r, _ in steps]
         key = (tuple(r for r, _ in steps), plan[1][0][1], str(table.device), n, bool(self._fused_ok(plan)),
                tuple((t.data_ptr(), t._version) for t in used))
         hit = self.__dict__.get('_cand')
@@ -781,7 +813,8 @@ class QueryEncoderDecoder(nn.Module, _EntityRanking):
         return hit[1]
 
     def _rank_operands(self, formula, queries, n):
-        """(q [B, D], candidates [n, D]) for ops.rank_entities: cos(q, candidate) is the score forward() gives the pair."""
+        """(q [B, D], candidates [n, D], score kind) for ops.rank_entities: that score of (q, candidate) is the one
+        forward() gives the pair."""
         plan = self._plan(formula)
         form, branches, imode, tail, emode = plan
         enc, device = self.enc, self._device()
@@ -796,7 +829,7 @@ class QueryEncoderDecoder(nn.Module, _EntityRanking):
                                   torch.from_numpy(p_ids).to(device), B, err)
             else:
                 q = self._composed_query(queries, plan).t()
-            return q, enc.table(formula.target_mode).detach()[:n]
+            return q, enc.table(formula.target_mode).detach()[:n], 'cosine'
         steps = branches[0][2]
         table = enc.table(formula.target_mode).detach()
 
@@ -806,10 +839,13 @@ class QueryEncoderDecoder(nn.Module, _EntityRanking):
                 return ops.gqe_embed(prog, [enc.table(m) for m in modes], mats, None, None, n, err)
             act = ops.embed_l2norm(table, None, torch.arange(n, device=device), err)
             for rel, _ in steps:
-                act = ops.linear(act, self.path_dec.mats[rel].detach().t())
-            return act
+                if hasattr(self.path_dec, 'vecs'):
+                    act = self.path_dec.project(act.t(), rel).t().detach()
+                else:
+                    act = ops.linear(act, self.path_dec.mats[rel].detach().t())
+            return act.contiguous()
         cand = self._chain_candidates(plan, n, project)
-        return enc(_anchor_ids(queries, 0), formula.anchor_modes[0]).t(), cand
+        return enc(_anchor_ids(queries, 0), formula.anchor_modes[0]).t(), cand, self._plan_score(plan)
 
     def _rank_all(self, formula, queries, target_nodes, exclude, k):
         return self._rank_rows(formula, queries, target_nodes, exclude, k, lambda n: self._rank_operands(formula, queries, n))

@@ -579,10 +579,13 @@ def exclusion_csr(exclude, n_queries):
     return off, rows.astype(np.int64, copy=False)
 
 
-def rank_entities(q, table, target_rows=None, exclude=None, k=0, eps=1e-8, err=None):
+RANK_SCORES = {'cosine': 0, 'dot': 1}
+
+
+def rank_entities(q, table, target_rows=None, exclude=None, k=0, eps=1e-8, err=None, score='cosine'):
     """Every row of `table` ([N, D], raw rows) ranked against the query embeddings q [Q, D] by the model's score
-    cos(q[i], table[r] / |table[r]|): mpqe_rank_entities (include/mpqe_amd.h). Inference only: nothing here is
-    differentiated. Everything is in table rows.
+    cos(q[i], table[r] / |table[r]|), or with score='dot' by q[i] . table[r]: mpqe_rank_entities_scored
+    (include/mpqe_amd.h). Inference only: nothing here is differentiated. Everything is in table rows.
       target_rows  [Q] int64 or None
       exclude      None, one list of rows per query, or (offsets [Q+1], rows) int64 tensors (lists sorted ascending)
     -> (topk_rows [Q, k] int64, topk_scores [Q, k], rank [Q] int64 or None, target_scores [Q] or None); the first two
@@ -590,6 +593,8 @@ def rank_entities(q, table, target_rows=None, exclude=None, k=0, eps=1e-8, err=N
     k = int(k)
     if k < 0 or k > RANK_MAX_K:
         raise ValueError('rank_entities: k must be in [0, %d], got %d' % (RANK_MAX_K, k))
+    if score not in RANK_SCORES:
+        raise ValueError('rank_entities: score must be one of %s, got %r' % (sorted(RANK_SCORES), score))
     if not torch.is_tensor(q) or not torch.is_tensor(table) or q.dim() != 2 or table.dim() != 2:
         raise ValueError('rank_entities: q and table must be 2-d tensors')
     if q.shape[1] != table.shape[1] or table.shape[0] < 1:
@@ -629,9 +634,9 @@ def rank_entities(q, table, target_rows=None, exclude=None, k=0, eps=1e-8, err=N
         if need == 0:
             raise ValueError('rank_entities: shape outside what the kernel covers')
         ws = _ws(need, dev)
-        _ck(lib().mpqe_rank_entities(_p(q), Q, _p(table), N, D, float(eps), _p(target_rows), _p(off), _p(rows), E, k,
-                                     _p(topr), _p(tops), _p(rank), _p(tsc), _p(ws), need, _p(err), _stream()),
-            'mpqe_rank_entities')
+        _ck(lib().mpqe_rank_entities_scored(_p(q), Q, _p(table), N, D, float(eps), RANK_SCORES[score], _p(target_rows),
+                                            _p(off), _p(rows), E, k, _p(topr), _p(tops), _p(rank), _p(tsc), _p(ws), need,
+                                            _p(err), _stream()), 'mpqe_rank_entities_scored')
     return topr, tops, rank, tsc
 
 
@@ -743,12 +748,21 @@ GQE_PROG_INTS = 32
 GQE_MAX_DIM = 256
 
 
-def gqe_programme(form, branches, e_table, agg='mean', pre=-1, post=-1, tail=()):
+GQE_OPS = {'matrix': 0, 'translate': 1, 'scale': 2}
+GQE_SCORES = {'cosine': 0, 'dot': 1}
+
+
+def gqe_programme(form, branches, e_table, agg='mean', pre=-1, post=-1, tail=(), op='matrix', score='cosine'):
     """The int32 programme of mpqe_gqe_fwd / bwd (include/mpqe_amd.h). branches: [(table index, [(matrix index, transposed)])],
-    tail: [(matrix index, transposed)] after the intersection; form 0 = chain, 1 = intersection."""
+    tail: [(matrix index, transposed)] after the intersection; form 0 = chain, 1 = intersection. op: what a branch / tail
+    site does with its parameter -- 'matrix' [D, D], 'translate' / 'scale' a [D] vector (`transposed` then means nothing);
+    score: 'cosine' | 'dot'."""
+    if op not in GQE_OPS or score not in GQE_SCORES:
+        raise ValueError('gqe_programme: op %r / score %r' % (op, score))
     prog = np.full(GQE_PROG_INTS, -1, dtype=np.int32)
     prog[0], prog[1], prog[2], prog[3], prog[4], prog[5], prog[6], prog[7] = (form, len(branches), int(agg == 'min'), pre, post,
-                                                                             len(tail), e_table, 0)
+                                                                             len(tail), e_table, GQE_OPS[op])
+    prog[27] = GQE_SCORES[score]
     for b, (table, steps) in enumerate(branches):
         prog[8 + 5 * b], prog[9 + 5 * b] = table, len(steps)
         for s, (m, t) in enumerate(steps):
@@ -762,6 +776,19 @@ def gqe_supported(dim):
     return dim % 16 == 0 and 16 <= dim <= GQE_MAX_DIM
 
 
+def _gqe_check_params(prog, params, D, what):
+    """Every parameter a programme names has the shape its site reads: [D] at a branch / tail site under a vector operator,
+    [D, D] everywhere else (the kernel cannot see a shape: a [D] vector read as a matrix would be read past its end)."""
+    vec = int(prog[7]) != 0
+    sites = [(int(prog[10 + 5 * b + s]) >> 1, vec) for b in range(int(prog[1])) for s in range(int(prog[9 + 5 * b]))]
+    sites += [(int(prog[24 + s]) >> 1, vec) for s in range(int(prog[5]))]
+    sites += [(int(prog[k]), False) for k in (3, 4) if int(prog[k]) >= 0]
+    for m, is_vec in sites:
+        # (an index outside `params` is the entry point's to refuse)
+        if 0 <= m < len(params) and tuple(params[m].shape) != ((D,) if is_vec else (D, D)):
+            raise ValueError('%s: parameter %d of the programme must be %s' % (what, m, '[D]' if is_vec else '[D, D]'))
+
+
 class _GqeScores(torch.autograd.Function):
     """One mpqe_gqe_fwd per forward, one mpqe_gqe_bwd per backward; the differentiable inputs are the entity tables and the
     matrices the programme names (`params` = tables, then matrices)."""
@@ -772,9 +799,10 @@ class _GqeScores(torch.autograd.Function):
         tables = [_f(t, 'embedding table') for t in params[:num_tables]]
         mats = [_f(m, 'matrix') for m in params[num_tables:]]
         D = tables[0].shape[1]
-        if any(t.dim() != 2 or t.shape[1] != D for t in tables) or any(tuple(m.shape) != (D, D) for m in mats):
-            raise ValueError('gqe_scores: every table [rows, D] and every matrix [D, D] with one D')
+        if any(t.dim() != 2 or t.shape[1] != D for t in tables) or any(tuple(m.shape) not in ((D, D), (D,)) for m in mats):
+            raise ValueError('gqe_scores: every table [rows, D] and every parameter [D, D] or [D] with one D')
         prog, node_map, p_ids, e_ids, qrow, neg_off, n, err, eps = spec
+        _gqe_check_params(prog, mats, D, 'gqe_scores')
         p_ids, e_ids = _i(p_ids, 'p_ids'), _i(e_ids, 'e_ids')
         node_map = None if node_map is None else _i(node_map, 'node_map')
         qrow = None if qrow is None else _i(qrow, 'qrow')
@@ -834,8 +862,9 @@ def gqe_embed(prog, tables, mats, node_map, p_ids, p_rows, err=None):
     tables = [_f(t.detach(), 'embedding table') for t in tables]
     mats = [_f(m.detach(), 'matrix') for m in mats]
     D = tables[0].shape[1]
-    if any(t.dim() != 2 or t.shape[1] != D for t in tables) or any(tuple(m.shape) != (D, D) for m in mats):
-        raise ValueError('gqe_embed: every table [rows, D] and every matrix [D, D] with one D')
+    if any(t.dim() != 2 or t.shape[1] != D for t in tables) or any(tuple(m.shape) not in ((D, D), (D,)) for m in mats):
+        raise ValueError('gqe_embed: every table [rows, D] and every parameter [D, D] or [D] with one D')
+    _gqe_check_params(prog, mats, D, 'gqe_embed')
     p_rows = int(p_rows)
     if p_ids is not None:
         p_ids = _i(p_ids, 'p_ids')

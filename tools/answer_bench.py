@@ -64,7 +64,7 @@ def build(kg, dim, seed=0):
     return schema, model
 
 
-def build_gqe(kg, dim, inter, seed=0):
+def build_gqe(kg, dim, inter, seed=0, decoder='bilinear'):
     from mpqe_amd import synthetic
     from mpqe_amd.data_utils import make_feature_modules
     from mpqe_amd.encoders import DirectEncoder
@@ -76,7 +76,7 @@ def build_gqe(kg, dim, inter, seed=0):
     graph.full_lists = {m: [int(v) for v in ids] for m, ids in graph.full_lists.items()}
     fm, node_maps = make_feature_modules(schema.ids, dim, schema.num_entities)
     dims = {m: dim for m in schema.modes}
-    model = QueryEncoderDecoder(graph, DirectEncoder(None, fm, node_maps), get_metapath_decoder(graph, dims, 'bilinear'),
+    model = QueryEncoderDecoder(graph, DirectEncoder(None, fm, node_maps), get_metapath_decoder(graph, dims, decoder, vector_decoders=True),
                                 get_intersection_decoder(graph, dims, inter))
     return schema, model
 
@@ -92,7 +92,10 @@ def gqe_torch_operands(model, formula, queries, n):
         return F.normalize(enc.table(mode)[maps[ids]], dim=1)
 
     def step(x, rel, transposed):
-        m = model.path_dec.mats[rel]
+        dec = model.path_dec
+        if hasattr(dec, 'vecs'):
+            return x + dec.vecs[rel] if dec.op == 'translate' else x * dec.vecs[rel]
+        m = dec.mats[rel]
         return x @ (m.t() if transposed else m)
     if form == 0:
         cand = F.normalize(enc.table(formula.target_mode)[:n], dim=1)
@@ -120,11 +123,11 @@ def gqe_torch_operands(model, formula, queries, n):
 def main_gqe(a):
     from mpqe_amd import synthetic
     torch.cuda.set_device(0)
-    out = {'tool': 'answer_bench', 'model': 'gqe', 'inter_decoder': a.inter_decoder, 'batch': a.batch, 'dim': a.dim, 'k': a.k,
+    out = {'tool': 'answer_bench', 'model': 'gqe', 'decoder': a.decoder, 'inter_decoder': a.inter_decoder, 'batch': a.batch, 'dim': a.dim, 'k': a.k,
            'timing': 'device events, median of %d blocks of %d calls after %d warm-up calls' % (a.blocks, a.iters, a.warmup),
            'shapes': {}}
     for kg in a.kgs:
-        schema, model = build_gqe(kg, a.dim, a.inter_decoder)
+        schema, model = build_gqe(kg, a.dim, a.inter_decoder, decoder=a.decoder)
         model = model.to('cuda:0').eval()
         per_type = {}
         for qt in a.query_types:
@@ -137,8 +140,12 @@ def main_gqe(a):
             target_rows = model.enc.node_maps[torch.as_tensor(targets, device='cuda:0')]
             negs, lens = np.tile(ids_all, a.batch).tolist(), [len(ids_all)] * a.batch
 
+            dot = 'inter' not in qt and getattr(model.path_dec, 'score', 'cosine') == 'dot'
+
             def cosines():
                 q, cand = gqe_torch_operands(model, f, qs, n)
+                if dot:             # (the diagonal decoder scores a chain by the plain dot product)
+                    return q @ cand.t()
                 return F.normalize(q, dim=1) @ F.normalize(cand, dim=1).t()
 
             def torch_rank():
@@ -186,6 +193,8 @@ def main():
     ap.add_argument('--blocks', type=int, default=9)
     ap.add_argument('--iters', type=int, default=10)
     ap.add_argument('--model', default='rgcn', choices=['rgcn', 'gqe'])
+    ap.add_argument('--decoder', default='bilinear', choices=['bilinear', 'transe', 'bilinear-diag'],
+                    help='gqe: the metapath decoder')
     ap.add_argument('--inter-decoder', default='mean', help='gqe: mean | min | mean-simple | min-simple')
     ap.add_argument('--query-types', nargs='+', default=['1-chain', '2-chain', '3-chain', '2-inter', '3-inter', '3-inter_chain',
                                                          '3-chain_inter'], help='gqe: the query types timed')

@@ -2,7 +2,8 @@
 plain torch ops on the GPU (F.normalize, mm, relu, min / mean, cosine_similarity), per query type and for the 11-batch
 AIFB post-burn-in mix, at B = 512, D = 128 on the AIFB-shaped synthetic KG.
 
-    python tools/gqe_bench.py [--batch-size 512] [--embed-dim 128] [--iters 20] [--rounds 5] [--inter min] [--composed]
+    python tools/gqe_bench.py [--batch-size 512] [--embed-dim 128] [--iters 20] [--rounds 5] [--inter min] [--decoder bilinear]
+                                [--composed]
 
 Two things are timed, each from the python call to the end of its device work (device events around a window of
 `iters` calls, every call with ids of its own; the windows of the variants alternate, the median over `rounds` is
@@ -40,7 +41,7 @@ def build(args, device):
     graph.full_lists = {m: [int(v) for v in ids] for m, ids in graph.full_lists.items()}
     fm, node_maps = make_feature_modules(schema.ids, args.embed_dim, schema.num_entities)
     dims = {m: args.embed_dim for m in schema.modes}
-    model = QueryEncoderDecoder(graph, DirectEncoder(None, fm, node_maps), get_metapath_decoder(graph, dims, 'bilinear'),
+    model = QueryEncoderDecoder(graph, DirectEncoder(None, fm, node_maps), get_metapath_decoder(graph, dims, args.decoder, vector_decoders=True),
                                 get_intersection_decoder(graph, dims, args.inter))
     return schema, model.to(device)
 
@@ -56,6 +57,13 @@ class TorchGQE(object):
         rows = self.maps[torch.as_tensor(ids, dtype=torch.long).to(self.maps.device)]
         return F.normalize(self.m.enc.table(mode)[rows], dim=1)
 
+    def step(self, x, rel, transposed):
+        """One path site on rows: a matrix product, or the vector decoders' x + v / x * v."""
+        dec = self.m.path_dec
+        if hasattr(dec, 'vecs'):
+            return x + dec.vecs[rel] if dec.op == 'translate' else x * dec.vecs[rel]
+        return x.mm(dec.mats[rel].t() if transposed else dec.mats[rel])
+
     def forward(self, formula, queries, targets):
         from mpqe_amd.model import gqe_plan
         m = self.m
@@ -64,13 +72,16 @@ class TorchGQE(object):
         if form == 0:
             act = t
             for rel, _ in branches[0][2]:
-                act = act.mm(m.path_dec.mats[rel])
-            return F.cosine_similarity(act, self.embed([q.anchor_nodes[0] for q in queries], emode), dim=1)
+                act = self.step(act, rel, False)
+            anchors = self.embed([q.anchor_nodes[0] for q in queries], emode)
+            if getattr(m.path_dec, 'score', 'cosine') == 'dot':
+                return (act * anchors).sum(dim=1)
+            return F.cosine_similarity(act, anchors, dim=1)
         xs = []
         for slot, mode, steps in branches:
             e = self.embed([q.anchor_nodes[slot] for q in queries], mode)
             for rel, _ in steps:
-                e = e.mm(m.path_dec.mats[rel].t())
+                e = self.step(e, rel, True)
             xs.append(e)
         if hasattr(m.inter_dec, 'pre_mats'):
             xs = [F.relu(x.mm(m.inter_dec.pre_mats[imode].t())) for x in xs]
@@ -79,7 +90,7 @@ class TorchGQE(object):
         if hasattr(m.inter_dec, 'post_mats'):
             c = c.mm(m.inter_dec.post_mats[imode].t())
         for rel, _ in tail:
-            c = c.mm(m.path_dec.mats[rel].t())
+            c = self.step(c, rel, True)
         return F.cosine_similarity(t, c, dim=1)
 
     def margin_loss(self, formula, queries, hard_negatives=False, margin=1):
@@ -110,6 +121,7 @@ def main(argv=None):
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--inter', default='min')
+    ap.add_argument('--decoder', default='bilinear', choices=['bilinear', 'transe', 'bilinear-diag'])
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--composed', action='store_true')
     ap.add_argument('--validate', action='store_true',
@@ -166,7 +178,7 @@ def main(argv=None):
                     else:
                         times[v].append(window(make(m), sets[args.warmup:]))
             model.fused = True
-            rec = dict(what=what, batch=name, B=args.batch_size, D=args.embed_dim, inter=args.inter, iters=args.iters,
+            rec = dict(what=what, batch=name, B=args.batch_size, D=args.embed_dim, inter=args.inter, decoder=args.decoder, iters=args.iters,
                        rounds=args.rounds)
             for v in times:
                 rec[v + '_us'] = 1000.0 * float(np.median(times[v]))

@@ -150,7 +150,8 @@ def main(argv=None):
                          'mpqe_amd/dropin.py) instead of FusedTrainStep.pack / run')
     ap.add_argument('--model', default='rgcn', choices=['rgcn', 'gqe'],
                     help="gqe: the baseline QueryEncoderDecoder (the reference's --model gqe) through the reference's loop body")
-    ap.add_argument('--decoder', default='bilinear', help='gqe: metapath decoder (the reference\'s --decoder)')
+    ap.add_argument('--decoder', default='bilinear', choices=['bilinear', 'transe', 'bilinear-diag'],
+                    help='gqe: metapath decoder (the reference\'s --decoder)')
     ap.add_argument('--inter-decoder', default='mean', help='gqe: mean | min | mean-simple | min-simple (--inter_decoder)')
     ap.add_argument('--kg-index', action='store_true',
                     help='gqe: the filtered metrics take their known answers from the device index (mpqe_amd/kg.py) instead of '
@@ -390,7 +391,7 @@ def build_gqe(args, device):
     graph.full_lists = {m: [int(v) for v in ids] for m, ids in graph.full_lists.items()}
     dims = {m: args.embed_dim for m in schema.modes}
     torch.manual_seed(args.seed)
-    model = QueryEncoderDecoder(graph, rgcn.enc, get_metapath_decoder(graph, dims, args.decoder),
+    model = QueryEncoderDecoder(graph, rgcn.enc, get_metapath_decoder(graph, dims, args.decoder, vector_decoders=True),
                                 get_intersection_decoder(graph, dims, args.inter_decoder)).to(device)
     return schema, graph, node_maps, model, train, test
 
