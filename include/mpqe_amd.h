@@ -159,6 +159,8 @@ int mpqe_rgcn_template_fwd(int query_type, int64_t batch_size,
                            float *out /*[B*N, dim_out]*/, void *stream);
 size_t mpqe_rgcn_template_bwd_workspace_bytes(int query_type, int64_t batch_size,
                                               int64_t dim_in, int64_t dim_out);
+/* workspace (needed unless grad_basis, grad_root and grad_bias are all NULL): 16-byte aligned, any contents; too small
+ * (MPQE_ERR_WORKSPACE) or misaligned (MPQE_ERR_INVALID_ARG) is refused before anything is queued, grad_x included. */
 /* grad_out is d loss / d out (post-ReLU when relu != 0; `out` is then needed for the mask).
  * grad_x is overwritten; grad_basis / grad_root / grad_bias are ACCUMULATED into (dense, like
  * the reference's autograd). Any of the three may be NULL to skip it. Deterministic.        */
@@ -178,6 +180,8 @@ int mpqe_rgcn_plan_build(const int64_t *edge_index /*[2, E]*/, const int64_t *ed
                          int64_t num_nodes, int64_t num_edges, int64_t num_relations,
                          void *plan, size_t plan_bytes, void *workspace, size_t workspace_bytes,
                          int32_t *err, void *stream);
+/* workspace (forward and backward): 16-byte aligned, MPQE_ERR_INVALID_ARG otherwise, before anything is queued (which
+ * kernels run, and so the last bits of the results, never depend on where it lies); nothing is assumed of what it holds. */
 size_t mpqe_rgcn_general_workspace_bytes(int64_t num_nodes, int64_t num_edges, int64_t num_relations,
                                          int64_t dim_in, int64_t dim_out, int backward);
 /* relu_mask (may be NULL; needs relu, dim_out % 64 == 0): mpqe_rgcn_general_mask_bytes(num_nodes, dim_out) bytes, 8-byte
@@ -216,6 +220,8 @@ int mpqe_rgcn_general_bwd(const void *plan, int64_t num_nodes, int64_t num_edges
  * (overwrite = 1). Fixed-order reductions (no float atomics).                                              */
 int mpqe_linear_fwd(const float *x, int64_t rows, const float *W, int64_t ldw, const float *bias, int64_t dim_in,
                     int64_t dim_out, int relu, int accumulate, float *y, void *stream);
+/* workspace (needed unless grad_W and grad_bias are both NULL): 16-byte aligned, any contents; too small
+ * (MPQE_ERR_WORKSPACE) or misaligned (MPQE_ERR_INVALID_ARG) is refused before anything is queued, grad_x included. */
 size_t mpqe_linear_bwd_workspace_bytes(int64_t rows, int64_t dim_in, int64_t dim_out);
 int mpqe_linear_bwd(const float *x, int64_t rows, const float *W, int64_t ldw, const float *y, const float *grad_y,
                     int64_t dim_in, int64_t dim_out, int relu, int overwrite, float *grad_x, float *grad_W, int64_t ldgw,

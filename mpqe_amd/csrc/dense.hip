@@ -166,6 +166,11 @@ extern "C" int mpqe_linear_bwd(const float *x, int64_t rows, const float *W, int
         }
         return MPQE_OK;
     }
+    // (refused before anything is queued: a short workspace must not leave grad_x written behind an error)
+    if ((grad_W || grad_bias) && (!workspace || workspace_bytes < mpqe_linear_bwd_workspace_bytes(rows, din, dout)))
+        return MPQE_ERR_WORKSPACE;
+    // (the bias sums pick their 16-byte form by the workspace's address too: the result's bits must not hang on it)
+    if ((grad_W || grad_bias) && (uintptr_t)workspace % 16 != 0) return MPQE_ERR_INVALID_ARG;
     const float *mask = relu ? y : nullptr;
     const bool vec = ptr_vec_ok(x, din) && ptr_vec_ok(W, ldw) && ptr_vec_ok(grad_y, dout) && (!relu || ptr_vec_ok(y, dout));
     if (grad_x) {
@@ -181,7 +186,6 @@ extern "C" int mpqe_linear_bwd(const float *x, int64_t rows, const float *W, int
                                (int)ldw, (int)din, (int)dout, grad_x);
     }
     if (grad_W || grad_bias) {
-        if (!workspace || workspace_bytes < mpqe_linear_bwd_workspace_bytes(rows, din, dout)) return MPQE_ERR_WORKSPACE;
         int nch, ch;
         dense_chunks(rows, &nch, &ch);
         float *slabs = reinterpret_cast<float *>(workspace);

@@ -376,6 +376,10 @@ extern "C" int mpqe_kg_answers(const int32_t *prog_host, const int64_t *const *r
     if (st != MPQE_OK) return st;
     if (Q == 0) return MPQE_OK;
     if (!anchor_rows || !answers) return MPQE_ERR_INVALID_ARG;
+    // (short of what the size query returns for these flags -- in LDS too, where the 256 bytes are not touched)
+    const size_t need = kg_in_lds(P, flags) ? 256 : align_up((size_t)Q * 4 * (size_t)P.W * 4, 256) + 256;
+    if (!kg_in_lds(P, flags) && (!workspace || ((uintptr_t)workspace & 3))) return MPQE_ERR_INVALID_ARG;
+    if (workspace_bytes < need) return MPQE_ERR_WORKSPACE;
     hipStream_t s = as_stream(stream);
     const long long *anc = reinterpret_cast<const long long *>(anchor_rows);
     long long *cnt = reinterpret_cast<long long *>(counts);
@@ -384,9 +388,6 @@ extern "C" int mpqe_kg_answers(const int32_t *prog_host, const int64_t *const *r
                            answers, hard, cnt, (uint32_t *)nullptr, err);
         return mpqe_launch_status();
     }
-    const size_t need = align_up((size_t)Q * 4 * (size_t)P.W * 4, 256);
-    if (!workspace || ((uintptr_t)workspace & 3)) return MPQE_ERR_INVALID_ARG;
-    if (workspace_bytes < need) return MPQE_ERR_WORKSPACE;
     hipLaunchKernelGGL(kg_answers_kernel<true>, dim3((unsigned)Q), dim3(KG_THREADS), 0, s, P, anc, (long long)Q, answers,
                        hard, cnt, reinterpret_cast<uint32_t *>(workspace), err);
     return mpqe_launch_status();

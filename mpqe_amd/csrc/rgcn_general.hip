@@ -935,6 +935,9 @@ extern "C" int mpqe_rgcn_general_fwd(const void *plan, int64_t Nn, int64_t E, in
     if (relu_mask && (!relu || Dout % 64 != 0 || (uintptr_t)relu_mask % 8 != 0)) return MPQE_ERR_INVALID_ARG;
     if (!workspace || workspace_bytes < mpqe_rgcn_general_workspace_bytes(Nn, E, R, Din, Dout, 0))
         return MPQE_ERR_WORKSPACE;
+    // (the message rows are stored and summed 16 bytes at a time where the other operands allow it: which form runs, and so
+    // the bits of the result, must not hang on where the workspace lies. Refused before anything is queued)
+    if ((uintptr_t)workspace % 16 != 0) return MPQE_ERR_INVALID_ARG;
     PlanView P = plan_view(plan, Nn, E, R);
     hipStream_t s = as_stream(stream);
     float *msg = reinterpret_cast<float *>(workspace);
@@ -942,6 +945,8 @@ extern "C" int mpqe_rgcn_general_fwd(const void *plan, int64_t Nn, int64_t E, in
                       ptr_vec_ok(x, Din);
     dim3 grid((unsigned)(((tile_bound(Nn, E, R) + 7) / 8 * 8) * ((Dout + GT_BN - 1) / GT_BN)));      // (1-D: see the kernel)
     const bool rows64 = gvec && Din % 64 == 0 && Dout % 64 == 0 && !dbg_on("GEN_LDS_GEMM");
+    const int vec = Dout % 4 == 0 && ptr_vec_ok(out, Dout) && (!bias || (uintptr_t)bias % 16 == 0);
+    if (relu_mask && !vec) return MPQE_ERR_INVALID_ARG;       // (the mask words come from the 16-byte form)
     if (rows64) {
         // persistent: one workgroup per CU (the kernel claims the LDS for that), whole groups of 8 x column groups
         const long long cb1 = Dout / 64, rt1 = (cb1 >= 3 || cb1 == 0) ? 1 : 4 / cb1, cg1 = cb1 >= 4 ? (cb1 + 3) / 4 : 1;
@@ -958,10 +963,7 @@ extern "C" int mpqe_rgcn_general_fwd(const void *plan, int64_t Nn, int64_t E, in
     else
         hipLaunchKernelGGL((rgcn_gen_gemm_kernel<false, LD_SCALAR>), grid, dim3(256), 0, s, P.rows_fwd, P.rel_ptr,
                            P.tile_ptr, (int)R, x, (const float *)nullptr, basis, root, (int)Din, (int)Dout, msg);
-    const int vec = Dout % 4 == 0 && ptr_vec_ok(out, Dout) && (!bias || (uintptr_t)bias % 16 == 0) &&
-                    (uintptr_t)workspace % 16 == 0;
     const long long threads = Nn * (vec ? Dout / 4 : Dout);
-    if (relu_mask && !vec) return MPQE_ERR_INVALID_ARG;       // (the mask words come from the 16-byte form)
     hipLaunchKernelGGL(segment_sum_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, P.dst_ptr,
                        P.dst_list, (long long)Nn, (long long)E, (int)Dout, (const float *)msg, bias, relu, out, vec,
                        reinterpret_cast<unsigned long long *>(relu_mask));
@@ -1009,6 +1011,7 @@ extern "C" int mpqe_rgcn_general_bwd(const void *plan, int64_t Nn, int64_t E, in
     if (relu_mask && (!relu || Dout % 64 != 0 || (uintptr_t)relu_mask % 8 != 0)) return MPQE_ERR_INVALID_ARG;
     if (!workspace || workspace_bytes < mpqe_rgcn_general_workspace_bytes(Nn, E, R, Din, Dout, 1))
         return MPQE_ERR_WORKSPACE;
+    if ((uintptr_t)workspace % 16 != 0) return MPQE_ERR_INVALID_ARG;      // (as in the forward)
     PlanView P = plan_view(plan, Nn, E, R);
     hipStream_t s = as_stream(stream);
     char *wb = reinterpret_cast<char *>(workspace);
@@ -1054,7 +1057,7 @@ extern "C" int mpqe_rgcn_general_bwd(const void *plan, int64_t Nn, int64_t E, in
         else
             hipLaunchKernelGGL((rgcn_gen_gemm_kernel<true, LD_SCALAR>), grid, dim3(256), 0, s, P.rows_bwd, P.rel_ptr,
                                P.tile_ptr, (int)R, grad_out, mask, basis, root, (int)Din, (int)Dout, gmsg);
-        const int vec = Din % 4 == 0 && ptr_vec_ok(grad_x, Din) && (uintptr_t)workspace % 16 == 0;
+        const int vec = Din % 4 == 0 && ptr_vec_ok(grad_x, Din);
         const long long threads = Nn * (vec ? Din / 4 : Din);
         hipLaunchKernelGGL(segment_sum_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, P.src_ptr,
                            P.src_list, (long long)Nn, (long long)E, (int)Din, (const float *)gmsg,

@@ -202,6 +202,12 @@ extern "C" int mpqe_rgcn_template_bwd(int query_type, int64_t B, const int64_t *
     if (!x || !grad_out || !basis || !root || B < 0 || Din <= 0 || Dout <= 0) return MPQE_ERR_INVALID_ARG;
     if (relu && !out) return MPQE_ERR_INVALID_ARG;
     if (B == 0) return MPQE_OK;
+    // (refused before anything is queued: a short workspace must not leave grad_x written behind an error)
+    if ((grad_basis || grad_root || grad_bias) &&
+        (workspace_bytes < mpqe_rgcn_template_bwd_workspace_bytes(query_type, B, Din, Dout) || !workspace))
+        return MPQE_ERR_WORKSPACE;
+    // (the bias sums pick their 16-byte form by the workspace's address too: the result's bits must not hang on it)
+    if ((grad_basis || grad_root || grad_bias) && (uintptr_t)workspace % 16 != 0) return MPQE_ERR_INVALID_ARG;
     hipStream_t s = as_stream(stream);
     const bool vec = ptr_vec_ok(basis, Dout) && ptr_vec_ok(root, Dout) && (Din * Dout) % 4 == 0 &&
                      ptr_vec_ok(grad_out, Dout) && (!relu || ptr_vec_ok(out, Dout)) && ptr_vec_ok(x, Din);
@@ -218,8 +224,6 @@ extern "C" int mpqe_rgcn_template_bwd(int query_type, int64_t B, const int64_t *
                                out, basis, root, (int)Din, (int)Dout, relu, grad_x);
     }
     if (grad_basis || grad_root || grad_bias) {
-        if (workspace_bytes < mpqe_rgcn_template_bwd_workspace_bytes(query_type, B, Din, Dout) || !workspace)
-            return MPQE_ERR_WORKSPACE;
         WChunks w = plan_chunks(B, tp.N);
         float *slabs = reinterpret_cast<float *>(workspace);
         float *bias_part = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) +

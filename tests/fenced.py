@@ -12,6 +12,11 @@ A kernel that reads outside its operand meets a NaN (0 * NaN is NaN: a zero-fill
 writes outside it is caught by assert_fence_intact, which compares every fence element bit for bit. On the GPU the
 fences also keep such a stray access inside memory the test owns: at least max(64, one row stride) elements on both
 sides.
+
+fenced_bytes(be, nbytes, fill) does the same for the buffers whose size the library dictates (workspaces, plans,
+descriptor blocks): a uint8 view of exactly `nbytes` bytes, `misalign` bytes past an `align`-byte boundary, between two
+fences of the float fence pattern that are each at least as large as the buffer and never under 4 KiB, so that an overrun
+by a whole tile row still lands in memory the test owns. `fill` is what the buffer holds before the call (FILLS).
 """
 import numpy as np
 
@@ -72,6 +77,46 @@ def fenced(be, array, misalign=0, ld=None, off=0):
     return view
 
 
+BYTE_FENCE = np.array([FLOAT_FENCE_BITS[4]], dtype='<u4').view(np.uint8)      # the float fence, byte by byte
+# what a library-sized buffer may hold when the call starts: zeros; the fence NaN; every bit set (-1 as an integer, an
+# all-ones counter, a negative NaN as a float); 1.0f (a large positive integer; an accumulator that is never cleared stays
+# finite and gives a visibly wrong sum); and bytes that differ from word to word, 4099 of them repeated (a prime: no two of
+# a layout's planes start alike -- two counters that are subtracted from each other cancel any uniform fill)
+FILLS = {'zeros': np.zeros(4, dtype=np.uint8), 'nan': BYTE_FENCE, 'ones': np.full(4, 0xFF, dtype=np.uint8),
+         'one_f32': np.array([0x3F800000], dtype='<u4').view(np.uint8),
+         'noise': np.random.RandomState(4099).randint(0, 256, size=4099).astype(np.uint8)}
+MIN_BYTE_FENCE = 4096
+
+
+def _pattern(word, n):
+    return np.resize(word, n) if n else np.zeros(0, dtype=np.uint8)
+
+
+def fenced_bytes(be, nbytes, fill, align=256, misalign=0):
+    nbytes = int(nbytes)
+    assert nbytes >= 0 and align >= 4 and align % 4 == 0 and 0 <= misalign < align
+    fence = max(nbytes, MIN_BYTE_FENCE)
+    fence += -fence % 4
+    total = fence + align + misalign + nbytes + fence
+    buf = be.put(_pattern(BYTE_FENCE, total))
+    base = be.ptr(buf)
+    assert base % 4 == 0
+    start = fence
+    while (base + start) % align != misalign:
+        start += 1
+    assert start + nbytes + fence <= total
+    view = buf[start:start + nbytes]
+    if be.name == 'emu' and nbytes == 0:                # (an empty slice forgets where it starts)
+        view = np.ndarray((0,), np.uint8, buffer=buf, offset=start)
+    image = _pattern(FILLS[fill], nbytes)               # (the fill's words start at the view's first byte)
+    if be.name == 'emu':
+        view[...] = image
+    else:
+        view.copy_(be.torch.from_numpy(image))
+    assert (nbytes == 0 or be.ptr(view) == base + start) and int(view.shape[0]) == nbytes
+    return view
+
+
 def _base_and_start(be, view):
     if be.name == 'emu':
         base = view.base
@@ -94,7 +139,10 @@ def assert_fence_intact(be, view, what=''):
         sh[axis] = n
         idx = idx + (np.arange(n, dtype=np.int64) * s).reshape(sh)
     inside[idx.reshape(-1)] = True
-    bits = whole.view(_bits_dtype(whole.dtype))
-    bad = np.nonzero(~inside & (bits != fence_bits(whole.dtype)))[0]
+    if whole.dtype == np.uint8:                         # fenced_bytes(): the float fence byte by byte, from the base on
+        bad = np.nonzero(~inside & (whole != _pattern(BYTE_FENCE, whole.shape[0])))[0]
+    else:
+        bits = whole.view(_bits_dtype(whole.dtype))
+        bad = np.nonzero(~inside & (bits != fence_bits(whole.dtype)))[0]
     assert bad.size == 0, '%s: %d fence elements overwritten, the first at %+d from the operand' % (
         what, bad.size, int(bad[0]) - start)

@@ -261,7 +261,10 @@ def test_embed_then_rank_gives_the_oracle_ranks(qt, inter):
     once (identity mode) and the normalised anchors ranked against it; intersection form -- the query rows ranked against
     the raw table. The ranks lie in the bracket of the oracle's scores of every entity."""
     from tests.kernel_backend import EmuBackend
-    be = EmuBackend()
+    embed_then_rank(EmuBackend(), qt, inter)
+
+
+def embed_then_rank(be, qt, inter):
     prob, _ = settled(qt, 48, 17, inter)
     f, B, D, n = prob.formula, prob.B, prob.D, 23
     ids_all = prob.ids[f.target_mode]
@@ -280,6 +283,7 @@ def test_embed_then_rank_gives_the_oracle_ranks(qt, inter):
         q = be.empty((B, D), np.float32)
         assert be.lib.mpqe_embed_l2norm_fwd(be.ptr(tab), tab.shape[0], D, be.ptr(nm), nm.shape[0], be.ptr(anchors), B,
                                             be.ptr(q), D, None, be.ptr(err), be.stream) == OK
+        q = be.get(q)
     assert st == OK and e == 0
     target_rows = be.put(prob.node_map[prob.targets])
     dq, dc = be.put(q), be.put(cand)

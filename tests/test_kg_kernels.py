@@ -45,6 +45,12 @@ def _garbage(rng, words):
     return rng.randint(-2 ** 31, 2 ** 31 - 1, size=int(words)).astype(np.int32)
 
 
+def _workspace(be, rng, need, misalign):
+    """The workspace of one call: random bits, `misalign` bytes past a 256-byte boundary, a word more than asked. (One place,
+    so that tests/test_workspace_bounds.py can put an exact, fenced buffer there instead.)"""
+    return _at(be, _garbage(rng, need // 4 + 1), misalign)
+
+
 def _fenced(be, rng, words, item=4):
     """-> (the whole buffer, the view of `words` elements behind GUARD guard elements, the buffer's bits on the host): random
     bits everywhere; the view's first byte is 4 (int32) / 8 (int64) bytes past a 16-byte boundary"""
@@ -126,7 +132,7 @@ def _call(world, prog, anchors, n_out, rng, flags, hard=True, counts=True):
     d_anchors = _at(be, anchors.astype(np.int64), 8)
     need = be.lib.mpqe_kg_workspace_bytes(prog.ctypes.data, Q, world.mode_rows.ctypes.data, len(world.mode_rows), flags)
     assert need >= 256
-    ws = _at(be, _garbage(rng, need // 4 + 1), 4)
+    ws = _workspace(be, rng, need, 4)
     err = be.zeros((1,), np.int32)
     a_buf, a_view, a_before = _fenced(be, rng, Q * W)
     h_buf, h_view, h_before = _fenced(be, rng, Q * W)

@@ -50,13 +50,18 @@ class SampleWorld(K.World):
         return self.keep[2 * rel + 1]
 
 
+def _workspace(be, rng, need, misalign):
+    """as tests/test_kg_kernels.py's: int64 words here, two int32 more than asked"""
+    return K._at(be, K._garbage(rng, need // 4 + 2).view(np.int64), misalign)
+
+
 def _walk(world, qt, Q, max_tries, seed, rng):
     """one mpqe_kg_sample_queries call -> (records [Q, 10], the error word)"""
     be = world.be
     R, M = len(world.relations), len(world.mode_rows)
     need = be.lib.mpqe_kg_sample_workspace_bytes(R, M)
     assert need >= 256
-    ws = K._at(be, K._garbage(rng, need // 4 + 2).view(np.int64), 8)
+    ws = _workspace(be, rng, need, 8)
     err = be.zeros((1,), np.int32)
     buf, view, before = K._fenced(be, rng, Q * 10, item=8)
     be.check(be.lib.mpqe_kg_sample_queries(world.offs, world.rows, world.edges, world.src.ctypes.data, world.dst.ctypes.data,

@@ -86,8 +86,12 @@ def oracle_step(params, cfg, node_map, batches, margin):
 
 def run_step(be, schema, mode_ids, params, node_map, cfg, batches, margin, backward=1, lanes=None, flags=0, touch='step', repeat=1,
              plan_out=None, between=None, recover=False, before_recovery=None, dev_weights=False, query_out=None,
-             then_plain=False, xcd_shift=0, readout_norms=False, place=None):
-    """place: where every operand lives -- place(be, name, array) returns the backend array (or a view of one, such as
+             then_plain=False, xcd_shift=0, readout_norms=False, place=None, alloc=None):
+    """alloc: where the buffers live whose size the library dictates -- alloc(be, name, nbytes) returns a backend buffer of
+    exactly `nbytes` bytes whose be.ptr() is its 256-byte aligned address (such as tests/fenced.py: fenced_bytes()), and
+    decides what it holds; names 'workspace', 'desc', 'touch', 'touch_workspace'. Default: be.nbytes with 256 bytes to round
+    the pointer up in, the workspace filled with NaN. (Not with `between`, which reads the workspace as floats.)
+    place: where every operand lives -- place(be, name, array) returns the backend array (or a view of one, such as
     tests/fenced.py: fenced()) that holds `array` and is used for be.ptr / be.get from then on. Names: 'P.<parameter key>' and
     'P.node_map', 'G.<parameter key>' (array: the gradient buffer's initial content), 'anchor_ids', 'targets', 'negs', and the
     outputs 'loss', 'scores_pos', 'scores_neg' (array: their initial NaN). Default: a private array from be.put.
@@ -193,14 +197,13 @@ def run_step(be, schema, mode_ids, params, node_map, cfg, batches, margin, backw
     wsb = be.lib.mpqe_step_workspace_bytes(ctypes.byref(P), SB, nb, lanes)
     if wsb == 0:
         raise _capi.MpqeError('mpqe_step_workspace_bytes rejected the step descriptors')
-    ws = be.nbytes(wsb + 256)
-    if be.name == 'emu':          # node states the step skips must never be read: poison the arena
-        ws.fill(np.nan)
-    else:
-        ws.fill_(float('nan'))
+    assert alloc is None or between is None
+    ws = be.nbytes(wsb + 256) if alloc is None else alloc(be, 'workspace', wsb)
+    if alloc is None:             # node states the step skips must never be read: poison the arena
+        ws.fill(np.nan) if be.name == 'emu' else ws.fill_(float('nan'))
     wptr = (be.ptr(ws) + 255) // 256 * 256
     dsb = be.lib.mpqe_step_desc_bytes(ctypes.byref(P), SB, nb, lanes)
-    dbuf = be.nbytes(dsb + 256)
+    dbuf = be.nbytes(dsb + 256) if alloc is None else alloc(be, 'desc', dsb)
     dptr = (be.ptr(dbuf) + 255) // 256 * 256
     loss = place(be, 'loss', np.full((1 + nb,), np.nan, np.float32))
     sp = place(be, 'scores_pos', np.full((Gtot,), np.nan, np.float32))
@@ -211,7 +214,10 @@ def run_step(be, schema, mode_ids, params, node_map, cfg, batches, margin, backw
         tb = be.lib.mpqe_step_touch_bytes(ctypes.byref(P), SB, nb)
         twb = be.lib.mpqe_step_touch_workspace_bytes(ctypes.byref(P), SB, nb)
         assert tb > 0 and twb > 0
-        tbuf, twbuf = be.nbytes(tb + 256), be.nbytes(twb + 256)
+        if alloc is None:
+            tbuf, twbuf = be.nbytes(tb + 256), be.nbytes(twb + 256)
+        else:
+            tbuf, twbuf = alloc(be, 'touch', tb), alloc(be, 'touch_workspace', twb)
         tptr = (be.ptr(tbuf) + 255) // 256 * 256
         if touch == 'pack':
             be.check(be.lib.mpqe_step_touch_build(ctypes.byref(P), SB, nb, be.ptr(d_anchor), be.ptr(d_tg), be.ptr(d_ng), tptr, tb,
