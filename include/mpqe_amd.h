@@ -898,6 +898,88 @@ int mpqe_kg_sample_rows(const uint32_t *bits, int64_t num_queries, int64_t n, co
                         int select, const int64_t *offsets /*[Q + 1]*/, int64_t *rows_out, int64_t rows_cap, int k,
                         uint64_t seed, int32_t *err, void *stream);
 
+/* ---- the neighbourhood-aggregating entity encoder on the KG index (csrc/sage.hip) -- added under ABI 7: entries only ------
+ * reference: utils.get_encoder utils.py:97-130, Encoder encoders.py:47-129, MeanAggregator aggregators.py:17-68 (`--depth
+ * 1..3`). Conventions of the KG and GQE entries above: *_host arrays are host arrays (of device pointers); everything is in
+ * table ROWS; arguments are checked before any launch (MPQE_ERR_INVALID_ARG / MPQE_ERR_UNSUPPORTED / MPQE_ERR_WORKSPACE; the
+ * size query returns 0); a bad offset or row ORs MPQE_FLAG_BAD_INDEX into err and is not followed; every word of every output
+ * is written; the workspace is not assumed zeroed; no float atomics: a call gives the same bits every run.
+ *
+ * mpqe_kg_sample_neighbours: the draws of MeanAggregator.forward (aggregators.py:51-53) for the R relations
+ * use_rels_host[0 .. R) (indices into the index's relations, 1 <= R <= 64, all with one source mode: the outgoing relations
+ * of the batch's mode, in relations[mode] order) and B source rows, in ONE launch. The CSR arrays, rel_src_mode_host,
+ * rel_dst_mode_host and mode_rows_host are mpqe_kg_sample_queries'. rows [B] int64 (device): the source rows; a negative row
+ * is the null node. Outputs neigh [R, B, max_keep] int64 and counts [R, B] int32. Per (i, b), with len the length of row
+ * rows[b]'s list in relation use_rels_host[i]:
+ *   len == 0 or the null node: counts 0, every slot -1.
+ *   otherwise k = min((int)ceil((double)len * keep_prob), max_keep) -- the reference's expression in the same IEEE double
+ *     arithmetic -- and counts = k. k == len: the list in CSR order, no draw. k < len: the list's entries at positions
+ *     P[0], .., P[k - 1] in that order, P the bijection of [0, len) that mpqe_kg_sample_rows defines, keyed by
+ *     base = M[seed ^ M[slot]], slot = use_rels_host[i] << 32 | b (the relation's index in the INDEX, so a draw does not depend
+ *     on which other relations the call names). Slots from k on are -1.
+ * The draw is per batch POSITION: a row listed twice draws twice, like the reference. The stream is the library's, not
+ * Python's (as with mpqe_sample_negatives), and the sample is over list POSITIONS: an index built with repeated edges can
+ * return one neighbour twice where the reference's set would merge them.
+ * A source row at or above its mode's rows, or a corrupt offset: MPQE_FLAG_BAD_INDEX, counts 0, slots -1. A neighbour outside
+ * its mode: MPQE_FLAG_BAD_INDEX, that slot is -1 (counts stays k). 0 < keep_prob <= 1, 1 <= max_keep <= MPQE_SAGE_MAX_KEEP, B <=
+ * 2^30 (MPQE_ERR_INVALID_ARG otherwise). B == 0: nothing is launched. No alignment beyond the element types'. */
+#define MPQE_SAGE_MAX_KEEP 32
+#define MPQE_SAGE_MAX_RELS 64
+int mpqe_kg_sample_neighbours(const int64_t *const *rel_offsets_host, const int64_t *const *rel_rows_host,
+                              const int64_t *rel_edges_host, const int32_t *rel_src_mode_host, const int32_t *rel_dst_mode_host,
+                              int num_rels, const int64_t *mode_rows_host, int num_modes, const int32_t *use_rels_host /*[R]*/,
+                              int R, const int64_t *rows /*[B] device*/, int64_t B, double keep_prob, int max_keep,
+                              uint64_t seed, int64_t *neigh /*[R, B, max_keep]*/, int32_t *counts /*[R, B]*/, int32_t *err,
+                              void *stream);
+
+/* mpqe_sage_fwd: Encoder.forward (encoders.py:100-129) for a batch of B nodes of one mode, GIVEN the sampled neighbours, in
+ * ONE launch. The mode's compress matrix W [dim_out, (R + 1) dim_in] has R + 1 column blocks, one per outgoing relation and
+ * one for the node itself (R = num_rels, 0 .. MPQE_SAGE_MAX_RELS):
+ *   feat_r[b] = (1 / count) * sum over s < count = counts[r, b], in slot order, of src_r[neigh[r, b, s]]          (r < R)
+ *               count == 0: src_r[pad row of block r] -- the reference's single null neighbour, encoders.py:115-118
+ *   feat_R[b] = src_R[self_rows[b]]                          (a negative self row: the pad row of block R)
+ *   z[b]      = W . concat(feat_0 .. feat_R)                 (fp32 MFMA; the sum over k in a fixed order)
+ *   out[b]    = ReLU(z)   or, with gamma and beta,   ReLU(gamma * (z - mean) / (unbiased std + eps) + beta)
+ * (encoders.py:126-128, 143-146; the arithmetic of mpqe_layernorm_relu_fwd). gamma == beta == NULL: no normalisation; one
+ * of them NULL: MPQE_ERR_INVALID_ARG. The rows are NOT L2-normalised: the reference's Encoder does not, only DirectEncoder.
+ * Sources are named like mpqe_gqe_fwd's tables: tables_host [num_tables <= 65] with table_rows_host, any [rows, dim_in] float
+ * matrix (an embedding table at depth 1, an inner encoder's output with positions as rows at depth >= 2); block r reads
+ * table block_table_host[r] and its null row is block_pad_host[r] (inside the table: MPQE_ERR_INVALID_ARG otherwise). Two
+ * blocks may name one table: they then share ONE gradient. The means are formed while the A operand is staged in LDS; the
+ * concatenation is never written, except that with save_states != 0 the [B, (R + 1) dim_in] feature rows, z and the
+ * normalisation's {mean, 1 / (std + eps)} go to `workspace` for mpqe_sage_bwd (save_states == 0: the workspace is not
+ * touched and may be NULL).
+ * A neighbour or self row at or above its table's rows, a negative neighbour row in a used slot, or a count outside
+ * [0, max_keep] (taken as 0) ORs MPQE_FLAG_BAD_INDEX; such a row reads as zeros.
+ * dim_in, dim_out: multiples of 16 up to 256 (MPQE_ERR_UNSUPPORTED otherwise, as is R * B * max_keep + B >= 2^31). Tables, W,
+ * out, grad_out, grad_W and the table gradients are 16-byte aligned and the workspace 256-byte aligned, as in mpqe_gqe_fwd
+ * (MPQE_ERR_INVALID_ARG otherwise); neigh, counts, self_rows, gamma, beta, grad_gamma and grad_beta take their element type's
+ * alignment. B == 0: nothing is launched.
+ * workspace: mpqe_sage_workspace_bytes (forward states and the backward's scratch: one size for both calls).
+ *
+ * mpqe_sage_bwd (the forward's arguments and workspace, its `out`, and grad_out [B, dim_out]):
+ *   grad_W [dim_out, (R + 1) dim_in] += grad_z^T . feat on mpqe_linear_bwd's fixed-order tiles;
+ *   grad_gamma / grad_beta [dim_out] += the ordered column sums of mpqe_layernorm_relu_bwd;
+ *   grad_tables_host[t] [rows, dim_in] += per touched row the sum of its entries in entry order, one writer per row. The
+ *     entries, in order: for r < R, b, s: g_feat_r[b] / count for every used slot (count == 0: g_feat_r[b] for the pad row, at
+ *     s = 0); then g_feat_R[b] for the self rows. The pad row receives its gradient like any row. A stable radix sort of the
+ *     (table, row) keys groups them (csrc/radix_sort.h); rows that the forward flagged get nothing.
+ * NULL gradient pointers (and NULL entries of grad_tables_host) are not computed. The number of launches depends on the
+ * tables' sizes (the sort's passes), not on R or B. */
+size_t mpqe_sage_workspace_bytes(int64_t batch, int num_rels, int64_t dim_in, int64_t dim_out, int max_keep);
+int mpqe_sage_fwd(const float *const *tables_host, const int64_t *table_rows_host, int num_tables,
+                  const int32_t *block_table_host /*[R + 1]*/, const int64_t *block_pad_host /*[R + 1]*/, int num_rels,
+                  const int64_t *neigh /*[R, B, max_keep]*/, const int32_t *counts /*[R, B]*/, int max_keep,
+                  const int64_t *self_rows /*[B]*/, int64_t batch, const float *W, int64_t dim_in, int64_t dim_out,
+                  const float *gamma, const float *beta, float eps, int save_states, float *out /*[B, dim_out]*/,
+                  void *workspace, size_t workspace_bytes, int32_t *err, void *stream);
+int mpqe_sage_bwd(const float *const *tables_host, const int64_t *table_rows_host, int num_tables,
+                  const int32_t *block_table_host, const int64_t *block_pad_host, int num_rels, const int64_t *neigh,
+                  const int32_t *counts, int max_keep, const int64_t *self_rows, int64_t batch, const float *W, int64_t dim_in,
+                  int64_t dim_out, const float *gamma, const float *beta, float eps, const float *out, const float *grad_out,
+                  float *const *grad_tables_host, float *grad_W, float *grad_gamma, float *grad_beta, void *workspace,
+                  size_t workspace_bytes, int32_t *err, void *stream);
+
 /* The aggregate of the intersection on its own (decoders.py:293-298, 313-318: torch.stack + agg_func(dim = 0)): out[i] =
  * mean (agg 0) / min (agg 1) of x0[i], x1[i] and, unless NULL, x2[i]; count elements. Backward: the mean's gradient in equal
  * parts, the minimum's to the first branch that holds it; NULL gradient pointers are not written. */

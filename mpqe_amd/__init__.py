@@ -5,7 +5,7 @@ from .graph import Formula, Graph, Query  # noqa: F401
 __all__ = ['Formula', 'Graph', 'Query', 'RGCNConv', 'RGCNEncoderDecoder', 'DirectEncoder',
            'RGCNQueryDataset', 'MLPReadout', 'TargetMLPReadout', 'QueryEncoderDecoder', 'BilinearMetapathDecoder',
            'TransEMetapathDecoder', 'BilinearDiagMetapathDecoder', 'SetIntersection', 'SimpleSetIntersection', 'get_metapath_decoder', 'get_intersection_decoder',
-           'KGIndex', 'KGAnswers', 'QuerySet']
+           'get_encoder', 'Encoder', 'KGIndex', 'KGAnswers', 'QuerySet']
 
 
 def __getattr__(name):
@@ -18,15 +18,15 @@ def __getattr__(name):
                 'SimpleSetIntersection'):
         from . import decoders
         return getattr(decoders, name)
-    if name in ('get_metapath_decoder', 'get_intersection_decoder'):
+    if name in ('get_metapath_decoder', 'get_intersection_decoder', 'get_encoder'):
         from . import utils
         return getattr(utils, name)
     if name in ('KGIndex', 'KGAnswers', 'QuerySet'):
         from . import kg
         return getattr(kg, name)
-    if name == 'DirectEncoder':
-        from .encoders import DirectEncoder
-        return DirectEncoder
+    if name in ('DirectEncoder', 'Encoder'):
+        from . import encoders
+        return getattr(encoders, name)
     if name == 'RGCNQueryDataset':
         from .data_utils import RGCNQueryDataset
         return RGCNQueryDataset

@@ -117,6 +117,10 @@ PROTOTYPES = {
     'mpqe_kg_sample_workspace_bytes': (Z, [I, I]),
     'mpqe_kg_sample_queries': (I, [P, P, P, P, P, P, P, I, P, I, I, L, I, ctypes.c_uint64, P, P, Z, P, P]),
     'mpqe_kg_sample_rows': (I, [P, L, L, P, I, P, P, L, I, ctypes.c_uint64, P, P]),
+    'mpqe_kg_sample_neighbours': (I, [P, P, P, P, P, I, P, I, P, I, P, L, DBL, I, ctypes.c_uint64, P, P, P, P]),
+    'mpqe_sage_workspace_bytes': (Z, [L, I, L, L, I]),
+    'mpqe_sage_fwd': (I, [P, P, I, P, P, I, P, P, I, P, L, P, L, L, P, P, F, I, P, P, Z, P, P]),
+    'mpqe_sage_bwd': (I, [P, P, I, P, P, I, P, P, I, P, L, P, L, L, P, P, F, P, P, P, P, P, P, P, Z, P, P]),
     'mpqe_branch_agg_fwd': (I, [P, P, P, L, I, P, P]),
     'mpqe_branch_agg_bwd': (I, [P, P, P, L, I, P, P, P, P, P]),
     'mpqe_debug_chain_stamps': (None, [P, Z]),
@@ -182,6 +186,7 @@ KG_GLOBAL_BITS = 1                                   # mpqe_kg_answers flags
 KG_ROWS_SET, KG_ROWS_COMPLEMENT, KG_ROWS_WITH_HOLES = 0, 1, 2       # mpqe_kg_rows select
 KG_QUERY_INTS = 10                                   # mpqe_kg_sample_queries: ints of one record
 KG_SAMPLE_MAX_K, KG_SAMPLE_MAX_ROWS = 1024, 1 << 22  # mpqe_kg_sample_rows
+SAGE_MAX_KEEP, SAGE_MAX_RELS = 32, 64                # mpqe_kg_sample_neighbours, mpqe_sage_fwd
 
 
 def bind(cdll):

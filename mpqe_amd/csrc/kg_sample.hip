@@ -26,7 +26,7 @@
 
 #include <vector>
 
-#include "common.h"
+#include "kg_stream.h"
 
 #define KGS_THREADS 256
 #define KGS_WAVES 4
@@ -40,7 +40,6 @@
 #define KGS_MAX_SAMPLE_ROWS MPQE_KG_SAMPLE_MAX_ROWS
 #define KGS_CHUNK_WORDS 64
 #define KGS_MAX_CHUNKS (KGS_MAX_SAMPLE_ROWS / 32 / KGS_CHUNK_WORDS)      // 2 048
-#define KGS_FEISTEL_ROUNDS 8
 
 // ------------------------------------------------------------------------------------------------------ the walk
 struct KgsRel {
@@ -269,25 +268,6 @@ __device__ __forceinline__ uint32_t kgs_word(const uint32_t *__restrict__ bits, 
     uint32_t v = select == MPQE_KG_ROWS_SET ? b : va & ~b;
     if (w == W - 1 && (n & 31)) v &= (1u << (unsigned)(n & 31)) - 1u;
     return v;
-}
-
-// P(j) for the bijection of [0, c) keyed by `key`: Feistel rounds on two halves of h bits, (L, R) -> (R, L ^ F(round, R)),
-// repeated until the value is below c (cycle walking: the orbit of a value below c returns below c).
-__device__ __forceinline__ long long kgs_permute(unsigned long long key, long long c, int h, long long j) {
-    const unsigned long long mask = (1ull << h) - 1ull;
-    unsigned long long x = (unsigned long long)j;
-    do {
-        unsigned long long L = x >> h, R = x & mask;
-#pragma unroll
-        for (int r = 0; r < KGS_FEISTEL_ROUNDS; ++r) {
-            const unsigned long long f = mpqe_mix64(key ^ (((unsigned long long)(r + 1) << 32) | R)) & mask;
-            const unsigned long long nr = L ^ f;
-            L = R;
-            R = nr;
-        }
-        x = (L << h) | R;
-    } while (x >= (unsigned long long)c);
-    return (long long)x;
 }
 
 __global__ __launch_bounds__(KGS_THREADS) void kg_sample_rows_kernel(const uint32_t *__restrict__ bits, long long n,

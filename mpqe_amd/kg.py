@@ -132,6 +132,7 @@ class KGIndex(object):
         self._start_arr = (ctypes.c_void_p * R)(*[t.data_ptr() if t.numel() else None for t in self.start_rows])
         self._start_count = (ctypes.c_int64 * R)(*[t.numel() for t in self.start_rows])
         self._programmes = {}
+        self._maps_dev = None
         self.err = ops.new_error_word(self.device)
 
     @contextlib.contextmanager
@@ -273,6 +274,51 @@ class KGIndex(object):
                     count, int(max_tries), int(seed) & (2 ** 64 - 1), out.data_ptr(), _capi._align256(ws.data_ptr()), need,
                     self.err.data_ptr(), stream), 'mpqe_kg_sample_queries')
         return out
+
+    def rows_of(self, mode, ids):
+        """Table rows of entity ids of `mode`, int64 on the index's device, computed there (ids: a list, an array or a
+        tensor). A negative id -- the null node -- stays -1; an id that is no entity of the mode becomes row n (outside,
+        which the kernels flag)."""
+        ids = torch.as_tensor(ids, dtype=torch.int64).to(self.device).reshape(-1)
+        if self._maps_dev is None:
+            self._maps_dev = torch.from_numpy(self.maps_host).to(self.device)
+        maps, row_ids = self._maps_dev, self.row_ids[mode]
+        n = row_ids.shape[0]
+        inside = (ids >= 0) & (ids < maps.shape[0])
+        cand = torch.where(inside, maps[ids.clamp(0, maps.shape[0] - 1)], torch.full_like(ids, -1))
+        ok = (cand >= 0) & (cand < n)
+        ok &= row_ids[cand.clamp(0, n - 1)] == ids
+        rows = torch.where(ok, cand, torch.full_like(ids, n))
+        return torch.where(ids < 0, torch.full_like(ids, -1), rows)
+
+    def sample_neighbours(self, mode, rows, keep_prob=0.5, max_keep=10, seed=0, relations=None, err=None):
+        """The draws of the reference's MeanAggregator (aggregators.py:51-53) for a batch of source ROWS of `mode` (device
+        int64; rows_of gives them for ids; negative: the null node) and every relation out of the mode, in one launch ->
+        (relations, neigh [R, B, max_keep] int64, counts [R, B] int32) on the device. relations: the (mode, name, mode)
+        triples to use, in that order (the caller's graph.relations[mode] order); by default the index's relations out of
+        `mode` in index order. A pure function of (seed, relation, batch position, the index): min(ceil(len * keep_prob),
+        max_keep) entries of every list, the whole list in CSR order where that is all of it, unused slots -1."""
+        if relations is None:
+            relations = [r for r in self.rels if r[0] == mode]
+        relations = [tuple(r) for r in relations]
+        for r in relations:
+            if r not in self.rel_index or r[0] != mode:
+                raise KeyError('KGIndex.sample_neighbours: no adjacency for relation %r out of mode %r' % (r, mode))
+        rows = rows.to(device=self.device, dtype=torch.int64).reshape(-1).contiguous()
+        R, B, max_keep = len(relations), int(rows.shape[0]), int(max_keep)
+        if R < 1:
+            raise ValueError('KGIndex.sample_neighbours: mode %r has no relation to sample' % (mode,))
+        neigh = torch.empty((R, B, max_keep), dtype=torch.int64, device=self.device)
+        counts = torch.empty((R, B), dtype=torch.int32, device=self.device)
+        use = np.asarray([self.rel_index[r] for r in relations], dtype=np.int32)
+        err = self.err if err is None else err
+        with self._call() as (lib, stream):
+            _capi.check(lib, lib.mpqe_kg_sample_neighbours(
+                self._off_arr, self._rows_arr, self._edges_arr, self.rel_src.ctypes.data, self.rel_dst.ctypes.data,
+                len(self.rels), self.mode_rows.ctypes.data, len(self.modes), use.ctypes.data, R, rows.data_ptr() if B else None,
+                B, float(keep_prob), max_keep, int(seed) & (2 ** 64 - 1), neigh.data_ptr() if B else None,
+                counts.data_ptr() if B else None, err.data_ptr(), stream), 'mpqe_kg_sample_neighbours')
+        return relations, neigh, counts
 
     def _records_by_formula(self, qt_name, records):
         """The accepted slots of a host [Q, 10] array grouped by formula -> {Formula: (slots, target rows [B], anchor rows

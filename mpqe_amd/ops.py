@@ -882,3 +882,92 @@ def gqe_embed(prog, tables, mats, node_map, p_ids, p_rows, err=None):
                                  0 if node_map is None else node_map.shape[0], mat_arr, len(mats), D, _p(p_ids), p_rows,
                                  _p(out), _p(err), _stream()), 'mpqe_gqe_embed')
     return out
+
+
+# --------------------------------------------------------------------------------------------- neighbourhood encoder
+SAGE_MAX_DIM, SAGE_MAX_KEEP, SAGE_MAX_RELS = 256, _capi.SAGE_MAX_KEEP, _capi.SAGE_MAX_RELS
+
+
+def sage_supported(dim_in, dim_out, num_rels=1, max_keep=1):
+    """whether mpqe_sage_fwd covers the shape (include/mpqe_amd.h); what it does not is the caller's to route elsewhere"""
+    return (dim_in % 16 == 0 and 16 <= dim_in <= SAGE_MAX_DIM and dim_out % 16 == 0 and 16 <= dim_out <= SAGE_MAX_DIM
+            and 0 <= num_rels <= SAGE_MAX_RELS and 1 <= max_keep <= SAGE_MAX_KEEP)
+
+
+class _SageEncode(torch.autograd.Function):
+    """One mpqe_sage_fwd per forward, one mpqe_sage_bwd per backward; the differentiable inputs are the source matrices, the
+    compress matrix and the normalisation's gamma / beta (`params` = tables, W[, gamma, beta])."""
+
+    @staticmethod
+    def forward(ctx, spec, num_tables, *params):
+        import ctypes
+        block_table, block_pad, neigh, counts, max_keep, self_rows, eps, err = spec
+        tables = [_f(t, 'source matrix') for t in params[:num_tables]]
+        W = _f(params[num_tables], 'compress matrix')
+        ln = len(params) > num_tables + 1
+        gamma = _f(params[num_tables + 1], 'gamma') if ln else None
+        beta = _f(params[num_tables + 2], 'beta') if ln else None
+        R = len(block_table) - 1
+        din, dout = tables[0].shape[1], W.shape[0]
+        if any(t.dim() != 2 or t.shape[1] != din for t in tables) or tuple(W.shape) != (dout, (R + 1) * din):
+            raise ValueError('sage_encode: every source [rows, dim_in] and W [dim_out, (R + 1) dim_in]')
+        self_rows = _i(self_rows, 'self_rows')
+        B = self_rows.shape[0]
+        if R:
+            neigh = _i(neigh, 'neigh')
+            counts = _need(counts, torch.int32, 'counts')
+            if tuple(neigh.shape) != (R, B, max_keep) or tuple(counts.shape) != (R, B):
+                raise ValueError('sage_encode: neigh [R, B, max_keep] and counts [R, B]')
+        else:
+            neigh = counts = None
+        dev = W.device
+        bt = np.ascontiguousarray(block_table, dtype=np.int32)
+        bp = np.ascontiguousarray(block_pad, dtype=np.int64)
+        tab_arr = (ctypes.c_void_p * len(tables))(*[_p(t) for t in tables])
+        rows_arr = (ctypes.c_int64 * len(tables))(*[t.shape[0] for t in tables])
+        save = any(ctx.needs_input_grad[2:])
+        out = torch.empty((B, dout), dtype=torch.float32, device=dev)
+        L = lib()
+        ws, wp, wb = None, None, 0
+        with torch.cuda.device(dev):
+            if save:
+                wb = L.mpqe_sage_workspace_bytes(B, R, din, dout, max_keep)
+                if wb == 0:
+                    raise ValueError('sage_encode: shape outside what the kernel covers (ops.sage_supported)')
+                ws = _ws(wb + 256, dev)
+                wp = _capi._align256(ws.data_ptr())
+            args = (tab_arr, rows_arr, len(tables), bt.ctypes.data, bp.ctypes.data, R, _p(neigh), _p(counts), max_keep,
+                    _p(self_rows), B, _p(W), din, dout, _p(gamma), _p(beta), eps)
+            _ck(L.mpqe_sage_fwd(*(args + (int(save), _p(out), wp, wb, _p(err), _stream()))), 'mpqe_sage_fwd')
+        ctx.call = (args, wp, wb, err, num_tables, (bt, bp, tab_arr, rows_arr, ws, neigh, counts, self_rows))
+        ctx.save_for_backward(*(tables + [W] + ([gamma, beta] if ln else []) + [out]))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        import ctypes
+        args, wp, wb, err, num_tables, _keep = ctx.call
+        saved = ctx.saved_tensors
+        params, out = saved[:-1], saved[-1]
+        g = _f(g, 'grad_out')
+        grads = [torch.zeros_like(p) if ctx.needs_input_grad[2 + k] else None for k, p in enumerate(params)]
+        gt = (ctypes.c_void_p * num_tables)(*[_p(x) for x in grads[:num_tables]])
+        gW = grads[num_tables]
+        gg, gb = (grads[num_tables + 1], grads[num_tables + 2]) if len(params) > num_tables + 1 else (None, None)
+        with torch.cuda.device(g.device):
+            _ck(lib().mpqe_sage_bwd(*(args + (_p(out), _p(g), gt, _p(gW), _p(gg), _p(gb), wp, wb, _p(err), _stream()))),
+                'mpqe_sage_bwd')
+        return (None, None) + tuple(grads)
+
+
+def sage_encode(tables, block_table, block_pad, neigh, counts, self_rows, W, gamma=None, beta=None, eps=1e-6, err=None):
+    """Encoder.forward for a batch, given its sampled neighbours, in one launch (mpqe_sage_fwd, include/mpqe_amd.h) ->
+    [B, dim_out]. tables: the source matrices [rows, dim_in]; block r of the compress matrix W [dim_out, (R + 1) dim_in] reads
+    tables[block_table[r]] and its null row is block_pad[r]; neigh [R, B, max_keep] int64 / counts [R, B] int32 / self_rows
+    [B] int64 on the device (rows; a negative self row is the null node). Differentiable w.r.t. the tables, W, gamma, beta."""
+    if (gamma is None) != (beta is None):
+        raise ValueError('sage_encode: gamma and beta come together')
+    max_keep = int(neigh.shape[2]) if neigh is not None and len(block_table) > 1 else 1
+    spec = (list(block_table), list(block_pad), neigh, counts, max_keep, self_rows, float(eps), err)
+    params = list(tables) + [W] + ([gamma, beta] if gamma is not None else [])
+    return _SageEncode.apply(spec, len(tables), *params)

@@ -1,6 +1,8 @@
-"""The reference's decoder factories (mpqe/utils.py:132-154) with its option strings."""
+"""The reference's encoder and decoder factories (mpqe/utils.py:97-154) with their option strings."""
 import torch
 
+from .aggregators import MeanAggregator
+from .encoders import DirectEncoder, Encoder
 from .decoders import (BilinearDiagMetapathDecoder, BilinearMetapathDecoder, SetIntersection, SimpleSetIntersection,
                        TransEMetapathDecoder)
 
@@ -30,3 +32,31 @@ def get_intersection_decoder(graph, out_dims, decoder):
     if decoder == "min-simple":
         return SimpleSetIntersection(agg_func=torch.min)
     raise Exception("Intersection decoder not recognized.")
+
+
+def get_encoder(depth, graph, out_dims, feature_modules, cuda, node_maps=None, index=None):
+    """reference utils.py:97-130: depth 0 the DirectEncoder, depth 1..3 the neighbourhood-aggregating Encoder stacked on
+    itself -- including its line 123 as written: the third encoder aggregates the second's outputs over the neighbours but
+    takes the node's OWN features from the first. node_maps: the id -> table row map (DirectEncoder then runs its fused
+    kernel). index: a kg.KGIndex over graph.adj_lists; with it every Encoder takes the device path (draws on the index,
+    one encode launch per call) and the graph need not carry Python adjacency dicts."""
+    if depth < 0 or depth > 3:
+        raise Exception("Depth must be between 0 and 3 (inclusive)")
+    if depth == 0:
+        return DirectEncoder(graph.features, feature_modules, node_maps)
+    adj = getattr(graph, 'adj_lists', None)
+
+    def through(enc):
+        return lambda nodes, mode: enc(nodes, mode).t().squeeze()
+    enc1 = Encoder(graph.features, graph.feature_dims, out_dims, graph.relations, adj, feature_modules=feature_modules,
+                   cuda=cuda, aggregator=MeanAggregator(graph.features), index=index, node_maps=node_maps)
+    enc = enc1
+    if depth >= 2:
+        enc2 = Encoder(through(enc1), enc1.out_dims, out_dims, graph.relations, adj, base_model=enc1, cuda=cuda,
+                       aggregator=MeanAggregator(through(enc1)), index=index, node_maps=node_maps)
+        enc = enc2
+        if depth >= 3:
+            enc3 = Encoder(through(enc1), enc2.out_dims, out_dims, graph.relations, adj, base_model=enc2, cuda=cuda,
+                           aggregator=MeanAggregator(through(enc2)), index=index, node_maps=node_maps, self_model=enc1)
+            enc = enc3
+    return enc

@@ -12,6 +12,8 @@ type), loss.backward(), Adam; evaluation by ROC-AUC with one sampled negative pe
     python tools/train_synthetic.py --model gqe --kg small --embed-dim 64 --batch-size 64 --steps 300 # the GQE baseline
     python tools/train_synthetic.py --model gqe --kg small --steps 300 --kg-index    # its filtered metrics through kg.KGIndex
     python tools/train_synthetic.py --model gqe --kg small --steps 300 --device-queries   # queries sampled on the device index
+    python tools/train_synthetic.py --model gqe --kg small --steps 100 --depth 1 --kg-index    # the neighbourhood encoder, on the index
+    python tools/train_synthetic.py --kg small --steps 100 --depth 2 --kg-index                 # ... two layers, under the R-GCN model
 
 Prints one JSON line: loss curves, AUC before / after training on held-out queries of the same KG (both sides).
 Only tests/ and this tool's --oracle leg use oracle/ (the checker, never the thing trained or shipped).
@@ -159,8 +161,14 @@ def main(argv=None):
     ap.add_argument('--device-queries', action='store_true',
                     help='sample the train / test queries and their negatives on the device index (kg.KGIndex.sample_query_sets: '
                          'the reference\'s KG sampler) instead of the host stand-in synthetic.sample_grounded_queries')
+    ap.add_argument('--depth', type=int, default=0, choices=[0, 1, 2],
+                    help='entity encoder (the reference\'s --depth): 0 the embedding lookup (everything above), 1 / 2 the '
+                         'neighbourhood-aggregating Encoder of utils.get_encoder under either --model, trained through '
+                         'model.margin_loss; on the device index with --kg-index or --device-queries, else the host path')
     args = ap.parse_args(argv)
-    if args.model == 'gqe':
+    if args.depth:
+        out = run_depth(args)
+    elif args.model == 'gqe':
         out = run_gqe(args)
     else:
         out = run_dropin(args) if args.dropin else run(args)
@@ -458,6 +466,72 @@ def run_gqe(args):
                 loss_last20=float(np.mean(losses[-20:])), auc_before=float(auc0), auc_after=float(auc1),
                 filtered_mrr_before=rank0['mrr'], filtered_mrr_after=rank1['mrr'], filtered_hits10_before=rank0['hits@10'],
                 filtered_hits10_after=rank1['hits@10'], known_answers='kg-index' if getattr(args, 'kg_index', False) else 'host',
+                loss_curve=losses)
+
+
+def run_depth(args):
+    """--depth 1 | 2: either model on utils.get_encoder's neighbourhood encoder, through the reference's loop body
+    (_reference_loop: margin_loss per batch on the models' module / composed paths, loss.backward(), Adam) and ROC-AUC
+    before and after. With --kg-index or --device-queries the encoder draws and encodes on the device index
+    (Encoder(index=...)); otherwise it walks the Python adjacency (the host path; a node without neighbours and the null
+    node then read their table's padding row, which the reference's own closure cannot look up)."""
+    import random
+    from mpqe_amd import evaluation, optim, synthetic
+    from mpqe_amd.model import QueryEncoderDecoder, RGCNEncoderDecoder
+    from mpqe_amd.utils import get_encoder, get_intersection_decoder, get_metapath_decoder
+    device = torch.device('cuda:0')
+    schema, graph, node_maps, plain, train, test = build(args, device)
+    graph.full_lists = {m: [int(v) for v in ids] for m, ids in graph.full_lists.items()}
+    fm = plain.enc.feature_modules
+    on_index = bool(getattr(args, 'kg_index', False) or getattr(args, 'device_queries', False))
+    index = kg_index(args, schema, node_maps, device) if on_index else None
+    maps_dev = node_maps.to(device)
+    if index is None:
+        graph.adj_lists = synthetic.make_adjacency(schema, degree=args.degree, seed=args.seed)
+
+        def features(nodes, mode):
+            ids = torch.as_tensor(nodes, dtype=torch.long, device=device)
+            table = fm[mode]
+            return table(torch.where(ids < 0, torch.full_like(ids, table.weight.shape[0] - 1), maps_dev[ids.clamp(min=0)]))
+        graph.features = features
+    dims = {m: args.embed_dim for m in schema.modes}
+    torch.manual_seed(args.seed)
+    enc = get_encoder(args.depth, graph, dims, fm, True, node_maps=node_maps, index=index)
+    if args.model == 'gqe':
+        model = QueryEncoderDecoder(graph, enc, get_metapath_decoder(graph, dims, args.decoder, vector_decoders=True),
+                                    get_intersection_decoder(graph, dims, args.inter_decoder))
+    else:
+        model = RGCNEncoderDecoder(graph, enc, readout=args.readout, num_layers=3, shared_layers=False,
+                                   adaptive=args.readout == 'mp', weight_decay=0)
+    model = model.to(device)
+    tq = test_dict(test)
+    order = [qt for qt, _ in synthetic.FULL_MIX]
+    query_types = list(dict.fromkeys(order))
+
+    def batches(qt):
+        rng = np.random.RandomState(args.seed + 11 + query_types.index(qt))
+        pos = [0] * len(train[qt])
+        while True:
+            fi = int(rng.randint(len(train[qt])))
+            f, qs = train[qt][fi]
+            lo = pos[fi] % len(qs)
+            pos[fi] = lo + args.batch_size
+            yield f, qs[lo:lo + args.batch_size]
+    iterators = {qt: batches(qt) for qt in query_types}
+    with torch.no_grad():
+        auc0, _ = evaluation.eval_auc_queries(tq, model, batch_size=128, seed=0)
+    opt = optim.Adam(model.parameters(), lr=args.lr)
+    random.seed(args.seed + 12)
+    t0 = time.perf_counter()
+    losses = _reference_loop(model, iterators, query_types, opt, args.steps,
+                             lambda batch, hard: model.margin_loss(*batch, hard_negatives=hard))
+    torch.cuda.synchronize()
+    train_s = time.perf_counter() - t0
+    with torch.no_grad():
+        auc1, _ = evaluation.eval_auc_queries(tq, model, batch_size=128, seed=0)
+    return dict(model=args.model, depth=args.depth, encoder_path='kg-index' if on_index else 'host', kg=args.kg,
+                embed_dim=args.embed_dim, batch_size=args.batch_size, steps=args.steps, train_seconds=train_s,
+                loss_first=losses[0], loss_last20=float(np.mean(losses[-20:])), auc_before=float(auc0), auc_after=float(auc1),
                 loss_curve=losses)
 
 
