@@ -987,6 +987,35 @@ int mpqe_branch_agg_fwd(const float *x0, const float *x1, const float *x2, int64
 int mpqe_branch_agg_bwd(const float *x0, const float *x1, const float *x2, int64_t count, int agg, const float *grad_out,
                         float *grad_x0, float *grad_x1, float *grad_x2, void *stream);
 
+/* ---- the evaluation metrics on device scores (csrc/eval.hip) -- added under ABI 7: entries only ---------------------------
+ * reference: eval_auc_queries / eval_perc_queries utils.py:34-95 and _get_perc_scores utils.py:25-32. Integer work only
+ * (comparisons, counts, a sort of 32-bit keys, integer sums): a call gives the same bits every run. Arguments are checked
+ * before any launch.
+ *
+ * mpqe_eval_counts: scores [B + total] fp32 in forward()'s layout -- B target scores, then the negatives' scores in CSR
+ * order -- and neg_offsets [B + 1] int64. counts [2, B] int64: counts[0][i] = the negatives of query i that score < its
+ * target, counts[1][i] = those that score <= it (utils.py:25-32 hands scipy.stats.percentileofscore exactly these two;
+ * the percentile is (lt + le + (le > lt)) * 50.0 / n in float64, NaN for n = 0). The comparisons are plain IEEE: NaN is
+ * neither below nor equal on either side, -0.0 equals +0.0, a negative that IS the target ties with it.
+ * A query whose offsets are out of order or outside [0, total] ORs MPQE_FLAG_BAD_INDEX into err and its two counts are
+ * NOT written; the others are. B, total < 2^31 (MPQE_ERR_UNSUPPORTED above). B == 0: nothing is launched. No alignment
+ * beyond the element types'. */
+int mpqe_eval_counts(const float *scores, const int64_t *neg_offsets, int64_t B, int64_t total, int64_t *counts /*[2, B]*/,
+                     int32_t *err, void *stream);
+
+/* mpqe_eval_auc: the exact ROC-AUC statistic of pos [n_pos] against neg [n_neg] (the roc_auc_score call of utils.py:60-68,
+ * one label per array): *u2 = sum over positives p of 2 |{neg < p}| + |{neg == p}|, so that AUC = u2 / (2 n_pos n_neg) is ONE
+ * float64 division of integers. Scores compare as np.nan_to_num and == leave them on the host path: NaN counts as 0.0,
+ * -0.0 as +0.0, +-inf are the extremes and tie among themselves. The negatives' order-preserving 32-bit keys are sorted with
+ * the library's radix sort (csrc/radix_sort.h), every positive binary-searches its two bounds, the workgroups' integer sums
+ * are added with integer atomics (order-free). n_pos == 0 or n_neg == 0: MPQE_ERR_INVALID_ARG (one class only: the AUC is
+ * not defined); n_pos, n_neg < 2^31 (MPQE_ERR_UNSUPPORTED above). u2: 8-byte aligned; workspace: 4-byte aligned,
+ * mpqe_eval_auc_workspace_bytes (exact: a byte less is MPQE_ERR_WORKSPACE and nothing is written; 0: arguments out of
+ * range). pos and neg are only read. */
+size_t mpqe_eval_auc_workspace_bytes(int64_t n_pos, int64_t n_neg);
+int mpqe_eval_auc(const float *pos, int64_t n_pos, const float *neg, int64_t n_neg, uint64_t *u2, void *workspace,
+                  size_t workspace_bytes, void *stream);
+
 /* Diagnostics, not part of the data path: while `device_buffer` (8 int64 per workgroup, num_blocks
  * workgroups) is set, every chain-kernel launch with at most num_blocks workgroups writes per workgroup the
  * device wall clock (100 MHz) at its phase boundaries [0..6] and HW_ID | XCC_ID << 32 in [7]; workgroup g of a

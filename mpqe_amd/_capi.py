@@ -121,6 +121,9 @@ PROTOTYPES = {
     'mpqe_sage_workspace_bytes': (Z, [L, I, L, L, I]),
     'mpqe_sage_fwd': (I, [P, P, I, P, P, I, P, P, I, P, L, P, L, L, P, P, F, I, P, P, Z, P, P]),
     'mpqe_sage_bwd': (I, [P, P, I, P, P, I, P, P, I, P, L, P, L, L, P, P, F, P, P, P, P, P, P, P, Z, P, P]),
+    'mpqe_eval_counts': (I, [P, P, L, L, P, P, P]),
+    'mpqe_eval_auc_workspace_bytes': (Z, [L, L]),
+    'mpqe_eval_auc': (I, [P, L, P, L, P, P, Z, P]),
     'mpqe_branch_agg_fwd': (I, [P, P, P, L, I, P, P]),
     'mpqe_branch_agg_bwd': (I, [P, P, P, L, I, P, P, P, P, P]),
     'mpqe_debug_chain_stamps': (None, [P, Z]),

@@ -1,0 +1,193 @@
+// The two metrics of the reference's evaluation (utils.py:25-95) on scores that are already on the device. Integer work
+// only: comparisons, counts, a sort of 32-bit keys and integer sums -- no float arithmetic, no float atomics, so a call
+// gives the same bits every run.
+//
+// mpqe_eval_counts  _get_perc_scores (utils.py:25-32): per query the number of its negatives that score below / not above
+//   its target, from the flat score vector forward() returns (B target scores, then the negatives' in CSR order). Two
+//   launches over the same queries: a list of up to EV_LONG scores is one wave's (four queries a workgroup, a butterfly of
+//   the two counts); a longer one -- the complement of an answer set, up to a whole mode -- is a workgroup's, in rounds of
+//   EV_THREADS scores, combined through LDS with integer adds. Each kernel leaves the other's queries alone. The
+//   comparisons are the hardware's IEEE ones: NaN is neither below nor equal, -0.0 equals +0.0.
+//
+// mpqe_eval_auc  the Mann-Whitney statistic behind ROC-AUC, doubled so that it is an integer:
+//   U2 = sum over positives p of 2 |{negatives < p}| + |{negatives == p}|,   AUC = U2 / (2 n_pos n_neg).
+//   Scores become order-preserving 32-bit keys (ev_key), the negatives' keys are sorted by the library's own radix sort
+//   (radix_sort.h), every positive binary-searches its lower and upper bound (their sum is its term) and the workgroups'
+//   sums are added to the output word with one 64-bit integer atomic each: integer adds commute, the result does not depend
+//   on their order.
+#include "radix_sort.h"
+
+#define EV_THREADS 256
+#define EV_WAVES 4
+#define EV_LONG 512                 // lists longer than this are a workgroup's, not a wave's
+#define EV_MAX_BLOCKS 1024          // mpqe_eval_auc: at most this many workgroups share the positives
+
+// lo / hi of query q's list; false for a segment that is out of order or outside [0, total]
+__device__ __forceinline__ bool ev_segment(const long long *__restrict__ off, long long q, long long total, long long *lo,
+                                           long long *hi) {
+    *lo = off[q];
+    *hi = off[q + 1];
+    return *lo >= 0 && *hi >= *lo && *hi <= total;
+}
+
+__global__ __launch_bounds__(EV_THREADS) void eval_counts_wave_kernel(const float *__restrict__ scores,
+                                                                      const long long *__restrict__ off, long long B,
+                                                                      long long total, long long *__restrict__ out,
+                                                                      int32_t *err) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long q = (long long)blockIdx.x * EV_WAVES + wave;
+    if (q >= B) return;                             // (wave-uniform, as is every exit below; no workgroup barrier here)
+    long long lo, hi;
+    if (!ev_segment(off, q, total, &lo, &hi)) {
+        if (lane == 0) flag_error(err, MPQE_FLAG_BAD_INDEX);
+        return;
+    }
+    if (hi - lo > EV_LONG) return;                  // eval_counts_block_kernel's
+    const float t = scores[q];
+    const float *neg = scores + B;
+    int lt = 0, le = 0;
+    for (long long j = lo + lane; j < hi; j += 64) {
+        const float s = neg[j];
+        lt += s < t ? 1 : 0;
+        le += s <= t ? 1 : 0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        lt += __shfl_xor(lt, o, 64);
+        le += __shfl_xor(le, o, 64);
+    }
+    if (lane == 0) {
+        out[q] = lt;
+        out[B + q] = le;
+    }
+}
+
+__global__ __launch_bounds__(EV_THREADS) void eval_counts_block_kernel(const float *__restrict__ scores,
+                                                                       const long long *__restrict__ off, long long B,
+                                                                       long long total, long long *__restrict__ out) {
+    __shared__ long long part[2][EV_WAVES];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const long long q = blockIdx.x;
+    long long lo, hi;
+    if (!ev_segment(off, q, total, &lo, &hi) || hi - lo <= EV_LONG) return;         // (uniform; the wave kernel flags / counts)
+    const float tgt = scores[q];
+    const float *neg = scores + B;
+    int lt = 0, le = 0;                             // (total < 2^31: a lane's count fits, and so does a wave's)
+    for (long long j = lo + t; j < hi; j += EV_THREADS) {
+        const float s = neg[j];
+        lt += s < tgt ? 1 : 0;
+        le += s <= tgt ? 1 : 0;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        lt += __shfl_xor(lt, o, 64);
+        le += __shfl_xor(le, o, 64);
+    }
+    if (lane == 0) {
+        part[0][wave] = lt;
+        part[1][wave] = le;
+    }
+    __syncthreads();
+    if (t < 2) {
+        long long sum = 0;
+#pragma unroll
+        for (int w = 0; w < EV_WAVES; ++w) sum += part[t][w];
+        out[(long long)t * B + q] = sum;
+    }
+}
+
+extern "C" int mpqe_eval_counts(const float *scores, const int64_t *neg_offsets, int64_t B, int64_t total, int64_t *counts,
+                                int32_t *err, void *stream) {
+    if (B < 0 || total < 0) return MPQE_ERR_INVALID_ARG;
+    if (B >= ((int64_t)1 << 31) || total >= ((int64_t)1 << 31)) return MPQE_ERR_UNSUPPORTED;
+    if (B == 0) return MPQE_OK;
+    if (!scores || !neg_offsets || !counts) return MPQE_ERR_INVALID_ARG;
+    hipStream_t s = as_stream(stream);
+    const long long *off = reinterpret_cast<const long long *>(neg_offsets);
+    long long *out = reinterpret_cast<long long *>(counts);
+    hipLaunchKernelGGL(eval_counts_wave_kernel, dim3((unsigned)((B + EV_WAVES - 1) / EV_WAVES)), dim3(EV_THREADS), 0, s,
+                       scores, off, (long long)B, (long long)total, out, err);
+    if (total > EV_LONG)                            // (no list can be that long otherwise)
+        hipLaunchKernelGGL(eval_counts_block_kernel, dim3((unsigned)B), dim3(EV_THREADS), 0, s, scores, off, (long long)B,
+                           (long long)total, out);
+    return mpqe_launch_status();
+}
+
+// ----------------------------------------------------------------------------------------------------------- ROC-AUC
+// A score as the host path ranks it (np.nan_to_num, then == on doubles): NaN is 0.0, -0.0 is +0.0; then the usual map of
+// IEEE bits to unsigned keys of the same order (negative: all bits flipped, otherwise the sign bit set). +-inf stay the
+// extremes and tie among themselves.
+__device__ __forceinline__ unsigned ev_key(float s) {
+    if (s != s) s = 0.f;
+    unsigned b = __float_as_uint(s);
+    if (b == 0x80000000u) b = 0u;
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+__global__ __launch_bounds__(EV_THREADS) void eval_auc_keys_kernel(const float *__restrict__ neg, long long n,
+                                                                   unsigned *__restrict__ keys) {
+    const long long i = (long long)blockIdx.x * EV_THREADS + threadIdx.x;
+    if (i < n) keys[i] = ev_key(neg[i]);
+}
+
+__global__ __launch_bounds__(EV_THREADS) void eval_auc_search_kernel(const float *__restrict__ pos, long long n_pos,
+                                                                     const unsigned *__restrict__ keys, long long n_neg,
+                                                                     unsigned long long *__restrict__ out) {
+    __shared__ unsigned long long part[EV_THREADS];
+    const int t = threadIdx.x;
+    unsigned long long acc = 0ull;
+    for (long long i = (long long)blockIdx.x * EV_THREADS + t; i < n_pos; i += (long long)gridDim.x * EV_THREADS) {
+        const unsigned k = ev_key(pos[i]);
+        long long a = 0, b = n_neg;                 // the first index whose key is >= k
+        while (a < b) {
+            const long long mid = (a + b) >> 1;
+            if (keys[mid] < k) a = mid + 1; else b = mid;
+        }
+        const long long below = a;
+        b = n_neg;                                  // the first index whose key is > k (not before `below`)
+        while (a < b) {
+            const long long mid = (a + b) >> 1;
+            if (keys[mid] <= k) a = mid + 1; else b = mid;
+        }
+        acc += (unsigned long long)(below + a);     // 2 below + (a - below) ties
+    }
+    part[t] = acc;
+    __syncthreads();
+    for (int s = EV_THREADS / 2; s > 0; s >>= 1) {
+        if (t < s) part[t] += part[t + s];
+        __syncthreads();
+    }
+    if (t == 0 && part[0]) atomicAdd(out, part[0]);
+}
+
+// workspace: keys [n_neg] | sorted keys [n_neg] | the sort's item numbers [n_neg] (unused) | the sort's scratch
+static inline size_t ev_keys_bytes(int64_t n_neg) { return align_up((size_t)n_neg * 4, 256); }
+
+extern "C" size_t mpqe_eval_auc_workspace_bytes(int64_t n_pos, int64_t n_neg) {
+    if (n_pos < 1 || n_neg < 1 || n_pos >= ((int64_t)1 << 31) || n_neg >= ((int64_t)1 << 31)) return 0;
+    return 3 * ev_keys_bytes(n_neg) + radix_sort_tmp_bytes<unsigned>((long long)n_neg);
+}
+
+extern "C" int mpqe_eval_auc(const float *pos, int64_t n_pos, const float *neg, int64_t n_neg, uint64_t *u2, void *workspace,
+                             size_t workspace_bytes, void *stream) {
+    if (n_pos < 1 || n_neg < 1 || !pos || !neg || !u2) return MPQE_ERR_INVALID_ARG;
+    if (n_pos >= ((int64_t)1 << 31) || n_neg >= ((int64_t)1 << 31)) return MPQE_ERR_UNSUPPORTED;
+    if (!workspace || ((uintptr_t)workspace & 3) || ((uintptr_t)u2 & 7)) return MPQE_ERR_INVALID_ARG;
+    if (workspace_bytes < mpqe_eval_auc_workspace_bytes(n_pos, n_neg)) return MPQE_ERR_WORKSPACE;
+    hipStream_t s = as_stream(stream);
+    char *wb = reinterpret_cast<char *>(workspace);
+    const size_t kb = ev_keys_bytes(n_neg);
+    unsigned *keys = reinterpret_cast<unsigned *>(wb), *sorted = reinterpret_cast<unsigned *>(wb + kb);
+    int *perm = reinterpret_cast<int *>(wb + 2 * kb);
+    if (hipMemsetAsync(u2, 0, sizeof(uint64_t), s) != hipSuccess) return MPQE_ERR_LAUNCH;
+    hipLaunchKernelGGL(eval_auc_keys_kernel, dim3((unsigned)((n_neg + EV_THREADS - 1) / EV_THREADS)), dim3(EV_THREADS), 0, s,
+                       neg, (long long)n_neg, keys);
+    const int st = radix_sort_pairs_own<unsigned>(wb + 3 * kb, (const unsigned *)keys, sorted, nullptr, perm,
+                                                  (long long)n_neg, 32, s);
+    if (st != MPQE_OK) return st;
+    long long blocks = (n_pos + EV_THREADS - 1) / EV_THREADS;
+    if (blocks > EV_MAX_BLOCKS) blocks = EV_MAX_BLOCKS;
+    hipLaunchKernelGGL(eval_auc_search_kernel, dim3((unsigned)blocks), dim3(EV_THREADS), 0, s, pos, (long long)n_pos,
+                       (const unsigned *)sorted, (long long)n_neg, reinterpret_cast<unsigned long long *>(u2));
+    return mpqe_launch_status();
+}

@@ -281,21 +281,30 @@ class RGCNQueryDataset(QueryDataset):
         return v
 
     @staticmethod
-    def get_query_graph(formula, queries, rel_ids, mode_ids):
+    def get_query_template(formula, batch_size, rel_ids, mode_ids):
+        """-> (var_ids, q_graphs): the part of get_query_graph that depends on the formula and the batch size alone (the
+        variables' mode ids and the batch of template graphs) -- all a caller needs whose anchor ids are on the device
+        already (RGCNEncoderDecoder.score_ids)."""
         info = ops.template_info(formula.query_type)
-        B, A, V, E = len(queries), info.num_anchors, info.num_vars, info.num_edges
+        A, V, E = info.num_anchors, info.num_vars, info.num_edges
         if A != len(formula.anchor_modes):
             raise ValueError('formula %s has %d anchor modes, template expects %d'
                              % (formula, len(formula.anchor_modes), A))
-        anchor_ids = np.empty((B, A), dtype=np.int64)
-        for i in range(A):
-            anchor_ids[:, i] = [q.anchor_nodes[i] for q in queries]
         nodes = formula.get_nodes()
         var_ids = np.array([mode_ids[nodes[info.var_node[k]]] for k in range(V)], dtype=np.int64)
         rels = formula.get_rels()
         edge_type = [rel_ids[reverse_relation(rels[info.rel_label[e]])] for e in range(E)]
-        graph = QueryGraphBatch(ops.Template(formula.query_type, B, edge_type))
-        return torch.from_numpy(anchor_ids), torch.from_numpy(var_ids), graph
+        graph = QueryGraphBatch(ops.Template(formula.query_type, int(batch_size), edge_type))
+        return torch.from_numpy(var_ids), graph
+
+    @staticmethod
+    def get_query_graph(formula, queries, rel_ids, mode_ids):
+        var_ids, graph = RGCNQueryDataset.get_query_template(formula, len(queries), rel_ids, mode_ids)
+        B, A = len(queries), len(formula.anchor_modes)
+        anchor_ids = np.empty((B, A), dtype=np.int64)
+        for i in range(A):
+            anchor_ids[:, i] = [q.anchor_nodes[i] for q in queries]
+        return torch.from_numpy(anchor_ids), var_ids, graph
 
 
 def make_data_iterator(data_loader):

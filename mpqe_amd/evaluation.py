@@ -57,9 +57,102 @@ def _batches(formula_queries, batch_size):
         yield offset, min(offset + batch_size, len(formula_queries))
 
 
-def eval_auc_queries(test_queries, enc_dec, batch_size=128, hard_negatives=False, seed=0):
+def _on_device(test_queries):
+    """whether the formulas' values are kg.QuerySets (the device route) rather than lists of Query"""
+    from .kg import QuerySet
+    kinds = {isinstance(v, QuerySet) for v in test_queries.values()}
+    if kinds == {True, False}:
+        raise TypeError('evaluation: every formula\'s queries as a kg.QuerySet, or every one as a list of Query')
+    return kinds == {True}
+
+
+def auc_batch_seed(seed, formula_position, batch_position):
+    """The seed of the negatives' draw for one batch of eval_auc_queries over QuerySets: seed * 2^40 + formula position *
+    2^20 + batch position (mod 2^64) -- the formula's position in the dict's iteration order, the batch's among the
+    formula's windows [lo, lo + batch_size). Distinct for distinct (formula, batch), both below 2^20."""
+    if not (0 <= formula_position < 2 ** 20 and 0 <= batch_position < 2 ** 20):
+        raise ValueError('eval_auc_queries: at most 2^20 formulas and 2^20 batches a formula')
+    return (int(seed) * 2 ** 40 + formula_position * 2 ** 20 + batch_position) & (2 ** 64 - 1)
+
+
+def _eval_auc_sets(test_sets, enc_dec, batch_size, hard_negatives, seed, lib):
+    """eval_auc_queries over {formula: kg.QuerySet}: ids and scores stay on the device. Per batch one draw of the library's
+    sampler (sampling.NegativeSampler.from_csr over the set's own lists -- also for a 1-chain, as the reference's
+    evaluation has it, unlike margin_loss) with auc_batch_seed's seed, one enc_dec.score_ids call; per formula the target
+    and negative scores fill two buffers [Q] and one ops.eval_auc gives the integer statistic; one more over all formulas."""
+    import torch
+
+    from . import ops
+    from .sampling import NegativeSampler
+    formula_aucs, all_pos, all_neg, errs = {}, [], [], {}
+    for f, (formula, qs) in enumerate(test_sets.items()):
+        Q, dev = len(qs), qs.index.device
+        if hard_negatives and qs.hard is None:
+            raise Exception("Hard negative examples can only be used with "
+                            "intersection queries")                   # reference model.py:467-469
+        sampler = NegativeSampler.from_csr(qs.neg, qs.hard, dev, lib=lib)
+        sampler.err = errs.setdefault(dev, sampler.err)         # one error word for all formulas: read once, below
+        pos = torch.empty(Q, dtype=torch.float32, device=dev)
+        neg = torch.empty(Q, dtype=torch.float32, device=dev)
+        for b, (lo, hi) in enumerate(_batches(qs.targets, batch_size)):
+            window = torch.arange(lo, hi, dtype=torch.long, device=dev)
+            negatives = sampler.sample(window, auc_batch_seed(seed, f, b), hard_negatives)
+            offsets = torch.arange(hi - lo + 1, dtype=torch.long, device=dev)
+            scores = enc_dec.score_ids(formula, qs.anchors[lo:hi], qs.targets[lo:hi], neg=(negatives, offsets))
+            pos[lo:hi] = scores[:hi - lo].to(dev)
+            neg[lo:hi] = scores[hi - lo:].to(dev)
+        formula_aucs[formula] = ops.auc_from_statistic(ops.eval_auc(pos, neg, lib=lib), Q, Q)
+        all_pos.append(pos)
+        all_neg.append(neg)
+    for err in errs.values():
+        ops.raise_on_flags(err)         # (an empty list: IndexError, the reference's random.choice([]))
+    pos, neg = torch.cat(all_pos), torch.cat(all_neg)
+    return ops.auc_from_statistic(ops.eval_auc(pos, neg, lib=lib), pos.shape[0], neg.shape[0]), formula_aucs
+
+
+def _eval_perc_sets(test_sets, enc_dec, batch_size, hard_negatives, lib):
+    """eval_perc_queries over {formula: kg.QuerySet}: per window the CSR of ALL its negatives is sliced with the offsets'
+    host mirror (lengths only), enc_dec.score_ids scores targets and negatives, ops.eval_counts counts; the float64
+    percentiles stay on the device and so does their mean -- one 8-byte read at the end."""
+    import torch
+
+    from . import ops
+    percentiles, errs = [], {}
+    for formula, qs in test_sets.items():
+        dev = qs.index.device
+        if hard_negatives and qs.hard is None:
+            raise Exception("Hard negative examples can only be used with "
+                            "intersection queries")
+        pair, host = (qs.hard, qs.offsets_host(True)) if hard_negatives else (qs.neg, qs.offsets_host(False))
+        if dev not in errs:
+            errs[dev] = ops.new_error_word(dev)         # one error word for all windows: read once, below
+        err = errs[dev]
+        for lo, hi in _batches(qs.targets, batch_size):
+            a, b = int(host[lo]), int(host[hi])
+            offsets = pair[1][lo:hi + 1] - a
+            scores = enc_dec.score_ids(formula, qs.anchors[lo:hi], qs.targets[lo:hi], neg=(pair[0][a:b], offsets))
+            counts = ops.eval_counts(scores.to(dev), offsets, hi - lo, lib=lib, err=err)
+            percentiles.append(ops.eval_percentiles(counts, offsets))
+    if not percentiles:
+        return np.mean([])
+    mean = torch.cat(percentiles).mean()
+    for err in errs.values():
+        ops.raise_on_flags(err)
+    return np.float64(mean.item())
+
+
+def eval_auc_queries(test_queries, enc_dec, batch_size=128, hard_negatives=False, seed=0, lib=None):
     """-> (overall AUC, {formula: AUC}). One negative per query, drawn with random.choice after
-    random.seed(seed) (reference utils.py:34-69)."""
+    random.seed(seed) (reference utils.py:34-69).
+
+    {formula: kg.QuerySet} (KGIndex.sample_query_sets) takes the device route: same windows [lo, lo + batch_size), same
+    metric -- ops.eval_auc's integer Mann-Whitney statistic, which is roc_auc(np.nan_to_num(scores)) to the bit -- with no id
+    list and no score on the host; enc_dec scores through score_ids(formula, anchors, targets, neg). The one negative per
+    query comes from the library's counter stream (mpqe_sample_negatives, seeded per batch by auc_batch_seed), NOT from
+    Python's Mersenne Twister: for a given `seed` the draws differ from the list path's -- the same distribution, other
+    numbers; the deviation sampling.py states. lib: the stand-in library of the sets' index (kg.KGIndex(lib=...)), if any."""
+    if _on_device(test_queries):
+        return _eval_auc_sets(test_queries, enc_dec, batch_size, hard_negatives, seed, lib)
     predictions, labels, formula_aucs = [], [], {}
     random.seed(seed)
     for formula in test_queries:
@@ -80,8 +173,14 @@ def eval_auc_queries(test_queries, enc_dec, batch_size=128, hard_negatives=False
     return roc_auc(labels, np.nan_to_num(predictions)), formula_aucs
 
 
-def eval_perc_queries(test_queries, enc_dec, batch_size=128, hard_negatives=False):
-    """-> mean percentile rank of the target's score among ALL negatives of its query (reference utils.py:72-95)."""
+def eval_perc_queries(test_queries, enc_dec, batch_size=128, hard_negatives=False, lib=None):
+    """-> mean percentile rank of the target's score among ALL negatives of its query (reference utils.py:72-95).
+
+    {formula: kg.QuerySet} takes the device route (see eval_auc_queries): ops.eval_counts per window, the per-query
+    percentiles -- percentile_of_score's to the bit -- and their mean in float64 on the device. The mean may differ from
+    np.mean's by the order of the additions: at most Q * 2^-52 relative over Q non-negative terms."""
+    if _on_device(test_queries):
+        return _eval_perc_sets(test_queries, enc_dec, batch_size, hard_negatives, lib)
     perc_scores = []
     for formula in test_queries:
         formula_queries = test_queries[formula]

@@ -550,6 +550,37 @@ class QuerySet(object):
     def __len__(self):
         return int(self.targets.shape[0])
 
+    def offsets_host(self, hard=False):
+        """The host mirror of the negatives' (hard: the hard negatives') offsets, int64 [B + 1]: lengths only, copied once.
+        It sizes a window's buffers without a synchronisation (evaluation.eval_*_queries)."""
+        mirror = self.__dict__.setdefault('_offsets_host', {})
+        if hard not in mirror:
+            pair = self.hard if hard else self.neg
+            mirror[hard] = None if pair is None else pair[1].cpu().numpy()
+        return mirror[hard]
+
+    def __getitem__(self, window):
+        """The queries [lo, hi) of a slice (step 1) as a QuerySet of views: the id tensors are slices of this set's, the
+        CSRs' offsets are re-based to start at 0. Nothing is copied to the host beyond offsets_host()."""
+        if not isinstance(window, slice) or window.step not in (None, 1):
+            raise TypeError('QuerySet[...]: a slice with step 1')
+        lo, hi, _ = window.indices(len(self))
+        hi = max(hi, lo)
+        mirror = {}
+
+        def cut(pair, hard):
+            if pair is None:
+                mirror[hard] = None
+                return None
+            host = self.offsets_host(hard)
+            a, b = int(host[lo]), int(host[hi])
+            mirror[hard] = host[lo:hi + 1] - a
+            return pair[0][a:b], pair[1][lo:hi + 1] - a
+        out = QuerySet(self.index, self.formula, self.targets[lo:hi], self.anchors[lo:hi], self.variables[lo:hi],
+                       cut(self.neg, False), cut(self.hard, True))
+        out.__dict__['_offsets_host'] = mirror
+        return out
+
     def negative_sampler(self):
         """NegativeSampler over the sampled lists; a 1-chain draws from the whole mode as the reference does (model.py:473)"""
         from .sampling import NegativeSampler

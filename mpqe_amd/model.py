@@ -434,6 +434,23 @@ class RGCNEncoderDecoder(nn.Module, _EntityRanking):
         self._check()
         return scores
 
+    def score_ids(self, formula, anchors, targets, neg=None):
+        """forward()'s scores for ids that are on the device already (kg.QuerySet: evaluation.eval_*_queries): anchors
+        [B, A] and targets [B] int64, neg None or (ids, offsets [B + 1]) -- every query's negatives, CSR. -> fp32
+        [B + total] on the device in forward()'s layout (the B target scores, then the negatives' in CSR order), under
+        no_grad. No id and no score visits the host: the template graph depends on the formula and B alone, and the
+        module path's ops take the rest as tensors -- one lookup-and-normalise and one ragged cosine over targets and
+        negatives together, each row computed as forward()'s module path computes it."""
+        with torch.no_grad():
+            device = self._device()
+            anchors, targets, neg_ids, q_row = _device_ids(anchors, targets, neg, device, len(formula.anchor_modes))
+            var_ids, q_graphs = RGCNQueryDataset.get_query_template(formula, anchors.shape[0], self.rel_ids, self.mode_ids)
+            out = self.encode(formula, None, anchors, var_ids, q_graphs)
+            ids = targets if neg_ids is None else torch.cat([targets, neg_ids])
+            scores = ops.cosine(out, self._target_embeds(ids, formula.target_mode, device), q_row=q_row)
+            self._check()
+        return scores
+
     # ------------------------------------------------------------------ answering a query (no counterpart in the reference)
     def _query_embeddings(self, formula, queries, anchor_ids, var_ids, q_graphs):
         d = self.dropin()
@@ -553,6 +570,28 @@ class TargetMLPReadout(nn.Module):
 # ------------------------------------------------------------------------------------------------ the GQE baseline
 def _anchor_ids(queries, slot):
     return [query.anchor_nodes[slot] for query in queries]
+
+
+def _device_ids(anchors, targets, neg, device, num_anchors):
+    """score_ids' operands checked and on `device`: (anchors [B, A], targets [B], negative ids [total] or None, the row map
+    [B + total] of forward()'s ragged layout -- arange(B), then query i repeated once per negative -- or None). The
+    negatives' count is the id tensor's length, so nothing is read back."""
+    def ids(t, what):
+        if not torch.is_tensor(t) or t.dtype != torch.long:
+            raise TypeError('score_ids: %s must be an int64 tensor' % what)
+        return t.to(device).contiguous()
+    anchors, targets = ids(anchors, 'anchors'), ids(targets, 'targets')
+    B = int(targets.shape[0])
+    if anchors.dim() != 2 or targets.dim() != 1 or tuple(anchors.shape) != (B, num_anchors):
+        raise ValueError('score_ids: anchors [B, %d] and targets [B]' % num_anchors)
+    if neg is None:
+        return anchors, targets, None, None
+    neg_ids, offsets = ids(neg[0], 'the negatives'), ids(neg[1], 'the negatives\' offsets')
+    if neg_ids.dim() != 1 or offsets.dim() != 1 or offsets.shape[0] != B + 1:
+        raise ValueError('score_ids: neg = (ids [total], offsets [B + 1])')
+    rows = torch.arange(B, dtype=torch.long, device=device)
+    q_row = torch.cat([rows, torch.repeat_interleave(rows, offsets[1:] - offsets[:-1], output_size=int(neg_ids.shape[0]))])
+    return anchors, targets, neg_ids, q_row
 
 
 def gqe_plan(formula):
@@ -747,6 +786,62 @@ class QueryEncoderDecoder(nn.Module, _EntityRanking):
         o_dev = rest.pop(0) if neg_off is not None else None
         return ops.gqe_scores(prog, [enc.table(m) for m in modes], mats, enc.node_maps, p_dev, e_dev, q_dev, o_dev, n,
                               self._error_word(device))
+
+    def score_ids(self, formula, anchors, targets, neg=None):
+        """forward()'s scores for ids that are on the device already (kg.QuerySet: evaluation.eval_*_queries): anchors
+        [B, A] and targets [B] int64, neg None or (ids, offsets [B + 1]) -- every query's negatives, CSR. -> fp32
+        [B + total] on the device in forward()'s layout, under no_grad. The integer operands of ops.gqe_scores are put
+        together with tensor ops -- the launch is _fused_scores', so the bits are forward()'s; where the fused kernel does
+        not cover the model the composed path runs on the same tensors. No id and no score visits the host."""
+        plan = self._plan(formula)
+        form, branches, imode, tail, emode = plan
+        with torch.no_grad():
+            device = self._device()
+            anchors, targets, neg_ids, q_row = _device_ids(anchors, targets, neg, device, len(formula.anchor_modes))
+            B = int(targets.shape[0])
+            tnodes = targets if neg_ids is None else torch.cat([targets, neg_ids])
+            n = int(tnodes.shape[0])
+            if self._fused_ok(plan):
+                prog, modes, mats = self._programme(plan)
+                qrow = neg_off = None
+                if form == 0:
+                    p_ids, e_ids = tnodes.reshape(1, n), anchors[:, 0].contiguous()
+                    qrow = q_row if q_row is not None else torch.arange(B, dtype=torch.long, device=device)
+                else:
+                    slots = [slot for slot, _, _ in branches if slot is not None]
+                    p_ids, e_ids = anchors[:, slots].t().contiguous(), tnodes
+                    if n > B:
+                        neg_off = neg[1].to(device).contiguous()
+                scores = ops.gqe_scores(prog, [self.enc.table(m) for m in modes], mats, self.enc.node_maps, p_ids, e_ids,
+                                        qrow, neg_off, n, self._error_word(device))
+            else:
+                scores = self._composed_ids(formula, anchors, tnodes, q_row, plan)
+            self._check()
+        return scores
+
+    def _composed_ids(self, formula, anchors, tnodes, q_row, plan):
+        """_composed_scores on id tensors (enc(ids, mode) takes them)"""
+        form, branches, imode, tail, emode = plan
+        target_embeds = self.enc(tnodes, formula.target_mode)
+        if form == 0:
+            first = self.enc(anchors[:, 0], formula.anchor_modes[0])
+            if hasattr(self.path_dec, 'vecs'):
+                return self.path_dec(target_embeds, first if q_row is None else first[:, q_row],
+                                     [rel for rel, _ in branches[0][2]])
+            act = target_embeds.t()
+            for rel, _ in branches[0][2]:
+                act = ops.linear(act, self.path_dec.mats[rel].t())
+            return ops.cosine(first.t(), act, q_row=q_row)
+        embeds = []
+        for slot, mode, steps in branches:
+            e = self.enc(anchors[:, slot], mode)
+            for rel, _ in steps:
+                e = self.path_dec.project(e, rel)
+            embeds.append(e)
+        q = self.inter_dec(embeds[0], embeds[1], imode, *embeds[2:])
+        for rel, _ in tail:
+            q = self.path_dec.project(q, rel)
+        return ops.cosine(q.t(), target_embeds.t(), q_row=q_row)
 
     # ------------------------------------------------------------------ the composed path (model.py:70-116 op by op)
     def _composed_scores(self, formula, queries, target_nodes, neg_nodes, neg_lengths, plan):

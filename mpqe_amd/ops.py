@@ -3,6 +3,8 @@ device memory (caching allocator), the current HIP stream and autograd bookkeepi
 arithmetic runs in the gfx950 kernels; tensors must be CUDA fp32/int64 and contiguous,
 anything else raises -- there is no CPU or eager-PyTorch path.
 """
+import contextlib
+
 import numpy as np
 import torch
 
@@ -971,3 +973,82 @@ def sage_encode(tables, block_table, block_pad, neigh, counts, self_rows, W, gam
     spec = (list(block_table), list(block_pad), neigh, counts, max_keep, self_rows, float(eps), err)
     params = list(tables) + [W] + ([gamma, beta] if gamma is not None else [])
     return _SageEncode.apply(spec, len(tables), *params)
+
+
+# --------------------------------------------------------------------------------------------- evaluation metrics
+def _eval_operand(t, dtype, what, lib_):
+    """a contiguous tensor of `dtype`: on the GPU for the product library; wherever a stand-in `lib_` (the tests' host
+    emulator of the kernels) can read it otherwise"""
+    if lib_ is None:
+        return _need(t, dtype, what)
+    if not torch.is_tensor(t) or t.dtype != dtype:
+        raise TypeError('mpqe_amd: %s must be a %s tensor' % (what, dtype))
+    return t.contiguous()
+
+
+def _eval_lib(device, lib_):
+    """(library, stream) for a call on `device` (made current by the caller)"""
+    return (lib(), _stream()) if lib_ is None else (lib_, None)
+
+
+def eval_counts(scores, neg_offsets, B, lib=None, err=None):
+    """counts [2, B] int64 on the scores' device (mpqe_eval_counts, include/mpqe_amd.h): per query the number of its
+    negatives that score < / <= its target -- what scipy's percentileofscore takes (reference utils.py:25-32). scores
+    [B + total] fp32 in forward()'s layout, neg_offsets [B + 1] int64. err: the caller's error word, read by the caller
+    (a list whose offsets are out of order keeps garbage counts and sets FLAG_BAD_INDEX there); None: one of this call's,
+    read before it returns (IndexError). lib: a bound C-ABI library to call instead of the product's, as on kg.KGIndex."""
+    B = int(B)
+    scores, neg_offsets = _eval_operand(scores, torch.float32, 'scores', lib), _eval_operand(neg_offsets, torch.int64,
+                                                                                             'neg_offsets', lib)
+    total = int(scores.shape[0]) - B
+    if scores.dim() != 1 or neg_offsets.dim() != 1 or B < 0 or total < 0 or neg_offsets.shape[0] != B + 1:
+        raise ValueError('eval_counts: scores [B + total] and neg_offsets [B + 1]')
+    dev = scores.device
+    own = err is None
+    if own:
+        err = new_error_word(dev)
+    out = torch.empty((2, B), dtype=torch.int64, device=dev)
+    if B:
+        with (torch.cuda.device(dev) if lib is None else contextlib.nullcontext()):
+            L, stream = _eval_lib(dev, lib)
+            _capi.check(L, L.mpqe_eval_counts(_p(scores), _p(neg_offsets), B, total, _p(out), _p(err), stream),
+                        'mpqe_eval_counts')
+        if own:
+            raise_on_flags(err)
+    return out
+
+
+def eval_percentiles(counts, neg_offsets):
+    """float64 [B] on the device: scipy.stats.percentileofscore(kind='rank') from eval_counts' two counts -- (lt + le +
+    (le > lt)) * 50.0 / n, NaN for n = 0. Every step is one correctly rounded IEEE operation (the integer sum is exact), so
+    the values are evaluation.percentile_of_score's to the bit."""
+    lt, le = counts[0], counts[1]
+    n = (neg_offsets[1:] - neg_offsets[:-1]).to(torch.float64)
+    return (lt + le + (le > lt).to(torch.int64)).to(torch.float64) * 50.0 / n
+
+
+def eval_auc(pos, neg, lib=None):
+    """The Python int U2 = sum over positives p of 2 |{neg < p}| + |{neg == p}| (mpqe_eval_auc, include/mpqe_amd.h), after
+    np.nan_to_num's reading of the scores; ROC-AUC = U2 / (2 * len(pos) * len(neg)). pos, neg: fp32 vectors on the device.
+    One 8-byte read. ValueError when either is empty, as sklearn's roc_auc_score has it."""
+    pos, neg = _eval_operand(pos, torch.float32, 'pos', lib), _eval_operand(neg, torch.float32, 'neg', lib)
+    if pos.dim() != 1 or neg.dim() != 1:
+        raise ValueError('eval_auc: two score vectors')
+    n_pos, n_neg = int(pos.shape[0]), int(neg.shape[0])
+    if n_pos == 0 or n_neg == 0:
+        raise ValueError('Only one class present in y_true. ROC AUC score is not defined in that case.')
+    dev = pos.device
+    out = torch.empty(1, dtype=torch.int64, device=dev)
+    with (torch.cuda.device(dev) if lib is None else contextlib.nullcontext()):
+        L, stream = _eval_lib(dev, lib)
+        need = L.mpqe_eval_auc_workspace_bytes(n_pos, n_neg)
+        if need == 0:
+            raise ValueError('eval_auc: more scores than the kernel covers (2^31 a side)')
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        _capi.check(L, L.mpqe_eval_auc(_p(pos), n_pos, _p(neg), n_neg, _p(out), _p(ws), need, stream), 'mpqe_eval_auc')
+    return int(out.item()) & (2 ** 64 - 1)
+
+
+def auc_from_statistic(u2, n_pos, n_neg):
+    """ROC-AUC from eval_auc's integer: one float64 division (what evaluation.roc_auc rounds to as well, n below 2^26)"""
+    return u2 / (2 * n_pos * n_neg)

@@ -11,6 +11,8 @@ Mersenne Twister.
     negs = sampler.sample(idx, seed)                               # idx: positions of the batch's queries
     sampler.sample(idx, seed, out=ids[lo:hi])      # or straight into the device id tensor handed to FusedTrainStep.pack(ids=...)
 """
+import contextlib
+
 import numpy as np
 import torch
 
@@ -39,11 +41,14 @@ class NegativeSampler(object):
         self.err = ops.new_error_word(self.device)
 
     @classmethod
-    def from_csr(cls, neg, hard, device, full_list=None):
+    def from_csr(cls, neg, hard, device, full_list=None, lib=None):
         """From candidate lists that are CSR already: neg / hard = (ids, offsets [n + 1]) int64 tensors or arrays, hard may
-        be None (kg.KGAnswers.negative_csr() / hard_csr() give them on the device: no Query object holds a Python list)."""
+        be None (kg.KGAnswers.negative_csr() / hard_csr() give them on the device: no Query object holds a Python list).
+        lib: a bound C-ABI library to draw with instead of the product's, as on kg.KGIndex (the tests' host emulator of the
+        kernels, with the lists on the CPU)."""
         self = cls.__new__(cls)
         self.device = torch.device(device)
+        self.lib = lib
 
         def pair(p):
             ids, off = (torch.as_tensor(a, dtype=torch.long).to(self.device).contiguous() for a in p)
@@ -69,9 +74,10 @@ class NegativeSampler(object):
             out = torch.empty(nq, dtype=torch.long, device=self.device)
         if out.shape[0] != nq or out.dtype != torch.long or not out.is_contiguous():
             raise ValueError('out must be a contiguous int64 tensor with one slot per query')
-        lib = ops.lib()
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream().cuda_stream
+        own = getattr(self, 'lib', None)
+        lib = ops.lib() if own is None else own
+        with (torch.cuda.device(self.device) if own is None else contextlib.nullcontext()):
+            stream = torch.cuda.current_stream().cuda_stream if own is None else None
             if hard_negatives:
                 if self.hard is None:
                     raise Exception("Hard negative examples can only be used with "

@@ -12,6 +12,7 @@ type), loss.backward(), Adam; evaluation by ROC-AUC with one sampled negative pe
     python tools/train_synthetic.py --model gqe --kg small --embed-dim 64 --batch-size 64 --steps 300 # the GQE baseline
     python tools/train_synthetic.py --model gqe --kg small --steps 300 --kg-index    # its filtered metrics through kg.KGIndex
     python tools/train_synthetic.py --model gqe --kg small --steps 300 --device-queries   # queries sampled on the device index
+    python tools/train_synthetic.py --model gqe --kg small --steps 300 --device-queries --device-eval   # ... and scored there
     python tools/train_synthetic.py --model gqe --kg small --steps 100 --depth 1 --kg-index    # the neighbourhood encoder, on the index
     python tools/train_synthetic.py --kg small --steps 100 --depth 2 --kg-index                 # ... two layers, under the R-GCN model
 
@@ -95,6 +96,7 @@ def device_queries(args, schema, adj, node_maps, device):
     for f, qs in train_sets.items():
         args.query_sets[(f.query_type, len(train[f.query_type]))] = qs
         train[f.query_type].append((f, qs.queries()))
+    args.test_sets = test_sets
     for f, qs in test_sets.items():
         test[f.query_type].append((f, qs.queries()))
     args.sampled = {'train_queries': sum(len(q) for v in train.values() for _, q in v),
@@ -130,6 +132,12 @@ def test_dict(test):
     return out
 
 
+def model_queries(args, tq):
+    """What the model's evaluation takes: the test QuerySets themselves under --device-eval (evaluation.eval_*_queries then
+    score and rank on the device: no Query object, no id list, no score on the host), else the lists of Query."""
+    return args.test_sets if getattr(args, 'device_eval', False) else tq
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--kg', default='small')
@@ -161,11 +169,17 @@ def main(argv=None):
     ap.add_argument('--device-queries', action='store_true',
                     help='sample the train / test queries and their negatives on the device index (kg.KGIndex.sample_query_sets: '
                          'the reference\'s KG sampler) instead of the host stand-in synthetic.sample_grounded_queries')
+    ap.add_argument('--device-eval', action='store_true',
+                    help='with --device-queries: evaluate the model on the test QuerySets themselves (AUC and percentile rank '
+                         'computed on the device, evaluation.eval_auc_queries / eval_perc_queries over kg.QuerySet); the '
+                         'sampled negatives then come from the library\'s stream, not Python\'s')
     ap.add_argument('--depth', type=int, default=0, choices=[0, 1, 2],
                     help='entity encoder (the reference\'s --depth): 0 the embedding lookup (everything above), 1 / 2 the '
                          'neighbourhood-aggregating Encoder of utils.get_encoder under either --model, trained through '
                          'model.margin_loss; on the device index with --kg-index or --device-queries, else the host path')
     args = ap.parse_args(argv)
+    if args.device_eval and (not args.device_queries or args.depth):
+        ap.error('--device-eval needs --device-queries and the embedding-lookup encoder (--depth 0)')
     if args.depth:
         out = run_depth(args)
     elif args.model == 'gqe':
@@ -202,7 +216,7 @@ def run(args):
     fstep = FusedTrainStep(model)
     opt = FlatOptimizer(fstep, lr=args.lr, opt='adam')
     with torch.no_grad():
-        auc0, _ = evaluation.eval_auc_queries(tq, model, batch_size=128, seed=0)
+        auc0, _ = evaluation.eval_auc_queries(model_queries(args, tq), model, batch_size=128, seed=0)
     losses, negs_used, aucs = [], [], []
     t0 = time.perf_counter()
     for it, row in enumerate(steps):
@@ -220,7 +234,7 @@ def run(args):
         negs_used.append(negs_row)
         if args.eval_every and (it + 1) % args.eval_every == 0:
             with torch.no_grad():
-                aucs.append((it + 1, evaluation.eval_auc_queries(tq, model, batch_size=128, seed=0)[0]))
+                aucs.append((it + 1, evaluation.eval_auc_queries(model_queries(args, tq), model, batch_size=128, seed=0)[0]))
     fstep.check()
     for s in samplers.values():
         s.check()
@@ -228,11 +242,14 @@ def run(args):
     train_s = time.perf_counter() - t0
     losses = torch.stack(losses).cpu().numpy()            # [steps, 1 + 11]
     with torch.no_grad():
-        auc1, per1 = evaluation.eval_auc_queries(tq, model, batch_size=128, seed=0)
+        auc1, per1 = evaluation.eval_auc_queries(model_queries(args, tq), model, batch_size=128, seed=0)
     out = dict(kg=args.kg, embed_dim=args.embed_dim, batch_size=args.batch_size, steps=args.steps, readout=args.readout,
                chain_form=bool(fstep.uses_chain(packed)), train_seconds=train_s,
                loss_first=float(losses[0, 0]), loss_last20=float(losses[-20:, 0].mean()), auc_before=float(auc0),
                auc_after=float(auc1), auc_curve=aucs, loss_curve=[float(v) for v in losses[:, 0]])
+    if getattr(args, 'device_eval', False):
+        with torch.no_grad():
+            out['perc_after'] = float(evaluation.eval_perc_queries(args.test_sets, model, batch_size=128))
     if args.oracle:
         out.update(run_oracle(args, graph, node_maps, model, cpu_state, train, tq, steps, negs_used, anchors, targets))
     return out
@@ -331,7 +348,7 @@ def run_dropin(args):
         return {qt: get_queries_iterator(by_type[qt], args.batch_size, m) for qt in by_type}
     # ---- the product path
     with torch.no_grad():
-        auc0, _ = evaluation.eval_auc_queries(tq, model, batch_size=128, seed=0)
+        auc0, _ = evaluation.eval_auc_queries(model_queries(args, tq), model, batch_size=128, seed=0)
     assert model.dropin() is not None, 'the model did not take the fused step'
     opt = FlatOptimizer(model.dropin().step, lr=args.lr, opt='adam')
     random.seed(args.seed + 12)
@@ -342,7 +359,7 @@ def run_dropin(args):
     train_s = time.perf_counter() - t0
     model.dropin()._check_mirror()
     with torch.no_grad():
-        auc1, _ = evaluation.eval_auc_queries(tq, model, batch_size=128, seed=0)
+        auc1, _ = evaluation.eval_auc_queries(model_queries(args, tq), model, batch_size=128, seed=0)
     out = dict(kg=args.kg, embed_dim=args.embed_dim, batch_size=args.batch_size, steps=args.steps, readout=args.readout,
                train_seconds=train_s, fused_backward_steps=model.dropin().steps, node_impl=model.dropin().node_impl,
                loss_first=losses[0], loss_last20=float(np.mean(losses[-20:])), auc_before=float(auc0), auc_after=float(auc1),
@@ -448,7 +465,7 @@ def run_gqe(args):
             yield f, qs[lo:lo + args.batch_size]
     iterators = {qt: batches(qt) for qt in query_types}
     with torch.no_grad():
-        auc0, _ = evaluation.eval_auc_queries(tq, model, batch_size=128, seed=0)
+        auc0, _ = evaluation.eval_auc_queries(model_queries(args, tq), model, batch_size=128, seed=0)
     rank0 = evaluation.eval_rank_queries(tq, model.eval(), batch_size=128, ks=(10,), known_answers=known)
     model.train()
     opt = optim.Adam(model.parameters(), lr=args.lr)
@@ -459,14 +476,18 @@ def run_gqe(args):
     torch.cuda.synchronize()
     train_s = time.perf_counter() - t0
     with torch.no_grad():
-        auc1, _ = evaluation.eval_auc_queries(tq, model, batch_size=128, seed=0)
+        auc1, _ = evaluation.eval_auc_queries(model_queries(args, tq), model, batch_size=128, seed=0)
     rank1 = evaluation.eval_rank_queries(tq, model.eval(), batch_size=128, ks=(10,), known_answers=known)
-    return dict(model='gqe', decoder=args.decoder, inter_decoder=args.inter_decoder, kg=args.kg, embed_dim=args.embed_dim,
-                batch_size=args.batch_size, steps=args.steps, train_seconds=train_s, loss_first=losses[0],
-                loss_last20=float(np.mean(losses[-20:])), auc_before=float(auc0), auc_after=float(auc1),
-                filtered_mrr_before=rank0['mrr'], filtered_mrr_after=rank1['mrr'], filtered_hits10_before=rank0['hits@10'],
-                filtered_hits10_after=rank1['hits@10'], known_answers='kg-index' if getattr(args, 'kg_index', False) else 'host',
-                loss_curve=losses)
+    out = dict(model='gqe', decoder=args.decoder, inter_decoder=args.inter_decoder, kg=args.kg, embed_dim=args.embed_dim,
+               batch_size=args.batch_size, steps=args.steps, train_seconds=train_s, loss_first=losses[0],
+               loss_last20=float(np.mean(losses[-20:])), auc_before=float(auc0), auc_after=float(auc1),
+               filtered_mrr_before=rank0['mrr'], filtered_mrr_after=rank1['mrr'], filtered_hits10_before=rank0['hits@10'],
+               filtered_hits10_after=rank1['hits@10'], known_answers='kg-index' if getattr(args, 'kg_index', False) else 'host',
+               loss_curve=losses)
+    if getattr(args, 'device_eval', False):
+        with torch.no_grad():
+            out['perc_after'] = float(evaluation.eval_perc_queries(args.test_sets, model, batch_size=128))
+    return out
 
 
 def run_depth(args):
@@ -519,7 +540,7 @@ def run_depth(args):
             yield f, qs[lo:lo + args.batch_size]
     iterators = {qt: batches(qt) for qt in query_types}
     with torch.no_grad():
-        auc0, _ = evaluation.eval_auc_queries(tq, model, batch_size=128, seed=0)
+        auc0, _ = evaluation.eval_auc_queries(model_queries(args, tq), model, batch_size=128, seed=0)
     opt = optim.Adam(model.parameters(), lr=args.lr)
     random.seed(args.seed + 12)
     t0 = time.perf_counter()
@@ -528,7 +549,7 @@ def run_depth(args):
     torch.cuda.synchronize()
     train_s = time.perf_counter() - t0
     with torch.no_grad():
-        auc1, _ = evaluation.eval_auc_queries(tq, model, batch_size=128, seed=0)
+        auc1, _ = evaluation.eval_auc_queries(model_queries(args, tq), model, batch_size=128, seed=0)
     return dict(model=args.model, depth=args.depth, encoder_path='kg-index' if on_index else 'host', kg=args.kg,
                 embed_dim=args.embed_dim, batch_size=args.batch_size, steps=args.steps, train_seconds=train_s,
                 loss_first=losses[0], loss_last20=float(np.mean(losses[-20:])), auc_before=float(auc0), auc_after=float(auc1),
