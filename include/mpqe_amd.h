@@ -898,6 +898,68 @@ int mpqe_kg_sample_rows(const uint32_t *bits, int64_t num_queries, int64_t n, co
                         int select, const int64_t *offsets /*[Q + 1]*/, int64_t *rows_out, int64_t rows_cap, int k,
                         uint64_t seed, int32_t *err, void *stream);
 
+/* ---- queries of DIFFERENT formulas in one launch (csrc/kg.hip, csrc/kg_sample.hip) -- added under ABI 7: entries only -----
+ * mpqe_kg_answers and mpqe_kg_sample_rows take one formula (one mode) a launch; a sampled batch on a schema of ~100 typed
+ * relations meets nearly as many formulas as it has queries. These entries fix only the QUERY TYPE per launch and take the
+ * relations from every query's own record, through a device table of the index built once.
+ *
+ * mpqe_kg_table_build: the table (mpqe_kg_table_bytes; 0: num_rels outside 1 .. 4 096 or num_modes outside 1 .. 16; 8-byte
+ * aligned). Per relation: the CSR pointers and edge count of mpqe_kg_answers, the row counts and indices of its two modes,
+ * and rel_reverse_host[i], the index of reverse_relation(relation i) in the same index (-1: absent). Per mode: its row count,
+ * mode_valid_host[m] -> uint32 [W(m)] on the device, the rows that are entities (the array or an entry NULL: all), and
+ * mode_row_ids_host[m] -> int64 [n] row -> entity id (NULL: none; ids_out below then holds -1). The host writes the table
+ * on `stream`; it is read-only afterwards and holds device addresses, so it lives as long as the arrays it names.
+ *
+ * mpqe_kg_answers_mixed: one workgroup per query. records [Q, MPQE_KG_QUERY_INTS] int64 (device) in exactly the layout
+ * mpqe_kg_sample_queries writes; read are the status, the relation indices, the destination rows of the leaf edges (the
+ * anchors) and edge 0's source row (the probe). The hop structure is query_type's, hops in the order of kg.query_hops: the hop
+ * for query edge (x, rel, y) walks the CSR of table[rel].reverse.
+ *   1-chain e0 | 2-chain e1, e0 | 3-chain e2, e1, e0 | 2-inter e0 & e1 | 3-inter e0 & e1 & e2 | 3-inter_chain e0 & (e2, e1) |
+ *   3-chain_inter (e1 & e2), then e0
+ *   status 0       empty sets, counts 0, target_mode -1, member 0; no flag.
+ *   malformed      a status other than 0 / 1, a relation index outside the table, a missing reverse, a relation whose source
+ *                  mode is not the frontier's, branches that end in different modes, an anchor outside its mode, a CSR
+ *                  offset or row outside its range: MPQE_FLAG_BAD_INDEX is ORed into err, THAT query gets what status 0
+ *                  gets, the other queries are unaffected.
+ *   answers, hard  [Q, out_words] or NULL, out_words >= W(widest mode of the index). Every word is written; the words at or
+ *                  above the query's own W(target mode) are 0. With both NULL no bitmap leaves the workgroup.
+ *   counts         [2, Q] int64 or NULL: |answers|, |hard|; |hard| is 0 unless `hard` is given or flags has
+ *                  MPQE_KG_COUNT_HARD (the hard flavour is then walked for its count alone).
+ *   target_mode    [Q] int32: the mode the query's walk ends in, -1 for a query that produced nothing.
+ *   member         [Q] int32 or NULL: 1 if probe_rows[q] (probe_rows NULL: the record's target row, edge 0's source) is in
+ *                  the answer set; a probe outside the mode gives 0.
+ *   flags          MPQE_KG_GLOBAL_BITS as for mpqe_kg_answers (LDS holds the working bitmaps up to 2 432 words of the
+ *                  WIDEST mode), MPQE_KG_COUNT_HARD.
+ *   workspace      mpqe_kg_mixed_workspace_bytes for the same flags (0: arguments out of range; 256 when the bitmaps live in
+ *                  LDS: not touched); not assumed zeroed. No spin waits, no float work; the same bits every run.
+ * num_queries == 0: nothing is launched. mode_rows_host must be the array the table was built from (the kernel refuses a
+ * relation whose bitmaps would not fit: malformed).
+ *
+ * mpqe_kg_sample_rows_mixed: mpqe_kg_sample_rows with n and valid taken per query from mode_of_query [Q] int32 and the table,
+ * query q's bitmap at bits + q * bits_stride words (bits_stride >= W(widest mode)), and q_base (>= 0) added to the query's
+ * position in the draw key: the bijection is keyed by (seed, q_base + q), so a batch cut into chunks draws what the whole
+ * batch draws. The draw itself is unchanged. A query of mode -1 must have an empty segment (MPQE_FLAG_BAD_INDEX otherwise);
+ * a mode outside [-1, num_modes) is flagged and nothing is written. rows_out and ids_out may each be NULL; ids_out receives
+ * the same lists as entity ids through the table's row -> id arrays. */
+#define MPQE_KG_COUNT_HARD 2
+size_t mpqe_kg_table_bytes(int num_rels, int num_modes);
+int mpqe_kg_table_build(const int64_t *const *rel_offsets_host, const int64_t *const *rel_rows_host,
+                        const int64_t *rel_edges_host, const int32_t *rel_src_mode_host, const int32_t *rel_dst_mode_host,
+                        const int32_t *rel_reverse_host, int num_rels, const int64_t *mode_rows_host,
+                        const uint32_t *const *mode_valid_host, const int64_t *const *mode_row_ids_host, int num_modes,
+                        void *table, size_t table_bytes, void *stream);
+size_t mpqe_kg_mixed_workspace_bytes(int64_t num_queries, const int64_t *mode_rows_host, int num_modes, int flags);
+int mpqe_kg_answers_mixed(const void *table, const int64_t *mode_rows_host, int num_modes, int query_type,
+                          const int64_t *records /*[Q, 10] device*/, int64_t num_queries,
+                          const int64_t *probe_rows /*[Q] or NULL*/, uint32_t *answers /*[Q, out_words] or NULL*/,
+                          uint32_t *hard /*[Q, out_words] or NULL*/, int64_t out_words, int64_t *counts /*[2, Q] or NULL*/,
+                          int32_t *target_mode /*[Q]*/, int32_t *member /*[Q] or NULL*/, int flags, void *workspace,
+                          size_t workspace_bytes, int32_t *err, void *stream);
+int mpqe_kg_sample_rows_mixed(const void *table, const int64_t *mode_rows_host, int num_modes, const uint32_t *bits,
+                              int64_t bits_stride, const int32_t *mode_of_query /*[Q]*/, int64_t num_queries, int64_t q_base,
+                              int select, const int64_t *offsets /*[Q + 1]*/, int64_t *rows_out, int64_t *ids_out,
+                              int64_t rows_cap, int k, uint64_t seed, int32_t *err, void *stream);
+
 /* ---- the neighbourhood-aggregating entity encoder on the KG index (csrc/sage.hip) -- added under ABI 7: entries only ------
  * reference: utils.get_encoder utils.py:97-130, Encoder encoders.py:47-129, MeanAggregator aggregators.py:17-68 (`--depth
  * 1..3`). Conventions of the KG and GQE entries above: *_host arrays are host arrays (of device pointers); everything is in

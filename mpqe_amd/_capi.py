@@ -117,6 +117,12 @@ PROTOTYPES = {
     'mpqe_kg_sample_workspace_bytes': (Z, [I, I]),
     'mpqe_kg_sample_queries': (I, [P, P, P, P, P, P, P, I, P, I, I, L, I, ctypes.c_uint64, P, P, Z, P, P]),
     'mpqe_kg_sample_rows': (I, [P, L, L, P, I, P, P, L, I, ctypes.c_uint64, P, P]),
+    # queries of different formulas in one launch (added under ABI 7: entries only)
+    'mpqe_kg_table_bytes': (Z, [I, I]),
+    'mpqe_kg_table_build': (I, [P, P, P, P, P, P, I, P, P, P, I, P, Z, P]),
+    'mpqe_kg_mixed_workspace_bytes': (Z, [L, P, I, I]),
+    'mpqe_kg_answers_mixed': (I, [P, P, I, I, P, L, P, P, P, L, P, P, P, I, P, Z, P, P]),
+    'mpqe_kg_sample_rows_mixed': (I, [P, P, I, P, L, P, L, L, I, P, P, P, L, I, ctypes.c_uint64, P, P]),
     'mpqe_kg_sample_neighbours': (I, [P, P, P, P, P, I, P, I, P, I, P, L, DBL, I, ctypes.c_uint64, P, P, P, P]),
     'mpqe_sage_workspace_bytes': (Z, [L, I, L, L, I]),
     'mpqe_sage_fwd': (I, [P, P, I, P, P, I, P, P, I, P, L, P, L, L, P, P, F, I, P, P, Z, P, P]),
@@ -186,6 +192,7 @@ SCATTER_IDS = {'add': 0, 'max': 1, 'mean': 2}
 FLAG_BAD_NODE_ID, FLAG_BAD_EDGE, FLAG_BAD_RELATION, FLAG_BAD_INDEX = 1, 2, 4, 8
 FLAG_INTERNAL, FLAG_TOUCH_RETRY = 16, 32
 KG_GLOBAL_BITS = 1                                   # mpqe_kg_answers flags
+KG_COUNT_HARD = 2                                    # mpqe_kg_answers_mixed: |hard| without the hard bitmaps
 KG_ROWS_SET, KG_ROWS_COMPLEMENT, KG_ROWS_WITH_HOLES = 0, 1, 2       # mpqe_kg_rows select
 KG_QUERY_INTS = 10                                   # mpqe_kg_sample_queries: ints of one record
 KG_SAMPLE_MAX_K, KG_SAMPLE_MAX_ROWS = 1024, 1 << 22  # mpqe_kg_sample_rows

@@ -406,3 +406,343 @@ extern "C" int mpqe_kg_rows(const uint32_t *bits, int64_t num_queries, int64_t n
                        reinterpret_cast<long long *>(rows_out), (long long)rows_cap, err);
     return mpqe_launch_status();
 }
+
+// ------------------------------------------------------------------------- queries of DIFFERENT formulas, one launch
+// mpqe_kg_answers_mixed: the kernel above with the programme taken per QUERY. The launch fixes the query type -- the hop
+// structure, KgShape, in the hop order of kg.query_hops -- and every workgroup reads its relations from its own record
+// (the layout mpqe_kg_sample_queries writes) and follows them through the index's device table (kg_table.h): the hop of
+// query edge (x, rel, y) walks the CSR of table[rel].reverse. Thread 0 resolves and checks the record into LDS; the walk is
+// the one above (kg_or_list, kg_scan_hop, both homes of the bitmaps, W = the widest mode of the index).
+// CSR faults are collected in an LDS word of the workgroup, not in the caller's: a query that met one gets empty sets like
+// any other malformed query, and the caller's word takes one atomic a faulty workgroup instead of one a faulty entry.
+#include <vector>
+
+#include "kg_table.h"
+
+struct KgShape {
+    int branches, tail_edge;    // tail_edge: the query edge of the hop after the merge, -1: none
+    int hops[3];
+    int edge[3][3];             // [b][s]: the query edge whose reverse relation hop s of branch b walks
+};
+
+enum { KGM_OK = 0, KGM_NONE = 1, KGM_BAD = 2 };
+
+struct KgMixedQuery {
+    KgHop hop[3];               // per query EDGE: the CSR of the edge's reverse relation
+    int src[3], dst[3];         // its modes
+    long long anchor[3];        // per branch
+    long long probe;
+    int state, n_merge, n_out, target;
+};
+
+__device__ __forceinline__ void kg_mixed_resolve(const KgShape &S, const char *table, int W, const long long *rec,
+                                                 const long long *probe_rows, long long q, KgMixedQuery &M) {
+    const KgtHead &H = *kgt_head(table);
+    const KgtRel *rel = kgt_rels(table);
+    M.state = KGM_BAD;
+    M.n_merge = M.n_out = 0;
+    M.target = -1;
+    M.probe = -1;
+    if (rec[0] == 0) {
+        M.state = KGM_NONE;
+        return;
+    }
+    if (rec[0] != 1 || H.magic != KGT_MAGIC || H.num_rels < 1 || H.num_rels > KGT_MAX_RELS) return;
+    bool used[3] = {false, false, false};
+    for (int b = 0; b < S.branches; ++b)
+        for (int s = 0; s < S.hops[b]; ++s) used[S.edge[b][s]] = true;
+    if (S.tail_edge >= 0) used[S.tail_edge] = true;
+    for (int e = 0; e < 3; ++e) {
+        if (!used[e]) continue;
+        const long long r = rec[2 + 3 * e];
+        if (r < 0 || r >= H.num_rels) return;
+        const int rv = rel[r].reverse;
+        if (rv < 0 || rv >= H.num_rels) return;
+        const KgtRel &R = rel[rv];
+        // (a table of another index than the host's mode_rows: its bitmaps would not fit the W words of this launch)
+        if (R.n_src < 1 || R.n_dst < 1 || kg_words(R.n_src) > W || kg_words(R.n_dst) > W || R.edges < 0) return;
+        M.hop[e].off = R.off;
+        M.hop[e].rows = R.rows;
+        M.hop[e].edges = R.edges;
+        M.hop[e].n_src = R.n_src;
+        M.hop[e].n_dst = R.n_dst;
+        M.src[e] = R.src;
+        M.dst[e] = R.dst;
+    }
+    int merge = -1;
+    for (int b = 0; b < S.branches; ++b) {
+        const int first = S.edge[b][0];
+        int mode = M.src[first];
+        const long long a = rec[3 + 3 * first];         // the leaf edge's destination row
+        if (a < 0 || a >= M.hop[first].n_src) return;
+        M.anchor[b] = a;
+        for (int s = 0; s < S.hops[b]; ++s) {
+            const int e = S.edge[b][s];
+            if (M.src[e] != mode) return;
+            mode = M.dst[e];
+        }
+        if (merge >= 0 && mode != merge) return;
+        merge = mode;
+    }
+    int last = merge;
+    if (S.tail_edge >= 0) {
+        if (M.src[S.tail_edge] != merge) return;
+        last = M.dst[S.tail_edge];
+    }
+    if (merge < 0 || merge >= H.num_modes || last < 0 || last >= H.num_modes) return;
+    M.n_merge = (int)H.mode_rows[merge];
+    M.n_out = (int)H.mode_rows[last];
+    if (kg_words(M.n_merge) > W || kg_words(M.n_out) > W) return;
+    M.target = last;
+    M.probe = probe_rows ? probe_rows[q] : rec[1];
+    M.state = KGM_OK;
+}
+
+template <bool G>
+__global__ __launch_bounds__(KG_THREADS) void kg_answers_mixed_kernel(
+    KgShape S, const char *__restrict__ table, int W, bool want_hard, const long long *__restrict__ records,
+    const long long *__restrict__ probe_rows, long long Q, uint32_t *__restrict__ answers, uint32_t *__restrict__ hard,
+    long long out_words, long long *__restrict__ counts, int32_t *__restrict__ target_mode, int32_t *__restrict__ member,
+    uint32_t *ws, int32_t *err) {
+    __shared__ uint32_t lds[G ? 1 : 4 * KG_LDS_WORDS];
+    __shared__ int red[2 * KG_WAVES];
+    __shared__ KgMixedQuery M;
+    __shared__ int32_t wg_err;
+    const long long q = blockIdx.x;
+    const int t = threadIdx.x;
+    if (t == 0) {
+        wg_err = 0;
+        kg_mixed_resolve(S, table, W, records + q * MPQE_KG_QUERY_INTS, probe_rows, q, M);
+    }
+    __syncthreads();
+    uint32_t *ans = answers ? answers + (size_t)q * (size_t)out_words : nullptr;
+    uint32_t *hrd = hard ? hard + (size_t)q * (size_t)out_words : nullptr;
+    bool empty = M.state != KGM_OK;             // (uniform)
+    const uint32_t *res_and = nullptr, *res_or = nullptr;
+    if (!empty) {
+        uint32_t *base = G ? ws + (size_t)q * 4 * (size_t)W : lds;
+        uint32_t *F[2] = {base, base + W};
+        uint32_t *AND = base + 2 * (size_t)W, *OR = base + 3 * (size_t)W;
+        for (int b = 0; b < S.branches; ++b) {
+            const uint32_t *cur = nullptr;
+            for (int s = 0; s < S.hops[b]; ++s) {
+                const KgHop &h = M.hop[S.edge[b][s]];
+                uint32_t *out = F[s & 1];
+                kg_clear<G>(out, h.n_dst);
+                __syncthreads();
+                if (s == 0) kg_or_list(h, M.anchor[b], out, nullptr, t, KG_THREADS, &wg_err);
+                else kg_scan_hop<G>(h, cur, nullptr, out, nullptr, &wg_err);
+                __syncthreads();
+                cur = out;
+            }
+            const int Wm = kg_words(M.n_merge);
+            for (int w = t; w < Wm; w += KG_THREADS) {
+                const uint32_t v = kg_load<G>(cur + w);
+                if (b == 0) {
+                    kg_store<G>(AND + w, v);
+                    kg_store<G>(OR + w, v);
+                } else {
+                    kg_store<G>(AND + w, kg_load<G>(AND + w) & v);
+                    kg_store<G>(OR + w, kg_load<G>(OR + w) | v);
+                }
+            }
+            __syncthreads();
+        }
+        res_and = AND;
+        res_or = OR;
+        if (S.tail_edge >= 0) {
+            const KgHop &h = M.hop[S.tail_edge];
+            kg_clear<G>(F[0], h.n_dst);
+            if (want_hard) kg_clear<G>(F[1], h.n_dst);
+            __syncthreads();
+            if (want_hard) kg_scan_hop<G>(h, OR, AND, F[1], F[0], &wg_err);
+            else kg_scan_hop<G>(h, AND, nullptr, F[0], nullptr, &wg_err);
+            __syncthreads();
+            res_and = F[0];
+            res_or = F[1];
+        }
+        empty = wg_err != 0;                    // (every OR into it lies before a barrier met above)
+    }
+    if (empty) {
+        for (long long w = t; w < out_words; w += KG_THREADS) {
+            if (ans) ans[w] = 0u;
+            if (hrd) hrd[w] = 0u;
+        }
+        if (t == 0) {
+            if (M.state != KGM_NONE) flag_error(err, MPQE_FLAG_BAD_INDEX);
+            if (counts) {
+                counts[q] = 0;
+                counts[Q + q] = 0;
+            }
+            target_mode[q] = -1;
+            if (member) member[q] = 0;
+        }
+        return;
+    }
+    const int Wout = kg_words(M.n_out);
+    int ca = 0, ch = 0;
+    for (int w = t; w < Wout; w += KG_THREADS) {
+        const uint32_t v = kg_load<G>(res_and + w);
+        if (ans) ans[w] = v;
+        ca += __builtin_popcount(v);
+        if (want_hard) {
+            const uint32_t u = kg_load<G>(res_or + w) & ~v;
+            if (hrd) hrd[w] = u;
+            ch += __builtin_popcount(u);
+        }
+    }
+    for (long long w = Wout + t; w < out_words; w += KG_THREADS) {
+        if (ans) ans[w] = 0u;
+        if (hrd) hrd[w] = 0u;
+    }
+    if (t == 0) {
+        target_mode[q] = M.target;
+        if (member) {
+            const long long p = M.probe;
+            member[q] = p >= 0 && p < M.n_out ? (int)((kg_load<G>(res_and + (p >> 5)) >> (unsigned)(p & 31)) & 1u) : 0;
+        }
+    }
+    if (!counts) return;        // (uniform)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        ca += __shfl_xor(ca, o, 64);
+        ch += __shfl_xor(ch, o, 64);
+    }
+    if ((t & 63) == 0) {
+        red[t >> 6] = ca;
+        red[KG_WAVES + (t >> 6)] = ch;
+    }
+    __syncthreads();
+    if (t == 0) {
+        counts[q] = (long long)red[0] + red[1] + red[2] + red[3];
+        counts[Q + q] = (long long)red[4] + red[5] + red[6] + red[7];
+    }
+}
+
+// the hop structure of a query type: kg.query_hops in query EDGES (mpqe_kg_sample_queries' edge order)
+static bool kg_shape(int qt, KgShape &S) {
+    memset(&S, 0, sizeof(S));
+    S.tail_edge = -1;
+    auto branch = [&](int e0, int e1, int e2) {
+        const int b = S.branches++;
+        S.edge[b][0] = e0;
+        S.edge[b][1] = e1 < 0 ? 0 : e1;
+        S.edge[b][2] = e2 < 0 ? 0 : e2;
+        S.hops[b] = 1 + (e1 >= 0) + (e2 >= 0);
+    };
+    switch (qt) {
+    case MPQE_Q_1CHAIN: branch(0, -1, -1); return true;
+    case MPQE_Q_2CHAIN: branch(1, 0, -1); return true;
+    case MPQE_Q_3CHAIN: branch(2, 1, 0); return true;
+    case MPQE_Q_2INTER: branch(0, -1, -1); branch(1, -1, -1); return true;
+    case MPQE_Q_3INTER: branch(0, -1, -1); branch(1, -1, -1); branch(2, -1, -1); return true;
+    case MPQE_Q_3INTER_CHAIN: branch(0, -1, -1); branch(2, 1, -1); return true;
+    case MPQE_Q_3CHAIN_INTER: branch(1, -1, -1); branch(2, -1, -1); S.tail_edge = 0; return true;
+    default: return false;
+    }
+}
+
+// the widest mode's words; 0: arguments out of range
+static int kg_mixed_words(const int64_t *mode_rows, int num_modes) {
+    if (!mode_rows || num_modes < 1 || num_modes > KGT_MAX_MODES) return 0;
+    int64_t widest = 0;
+    for (int m = 0; m < num_modes; ++m) {
+        if (mode_rows[m] < 1 || mode_rows[m] > KG_MAX_ROWS) return 0;
+        if (mode_rows[m] > widest) widest = mode_rows[m];
+    }
+    return (int)((widest + 31) / 32);
+}
+
+static bool kg_mixed_in_lds(int W, int flags) { return W <= KG_LDS_WORDS && !(flags & MPQE_KG_GLOBAL_BITS); }
+
+extern "C" size_t mpqe_kg_mixed_workspace_bytes(int64_t num_queries, const int64_t *mode_rows_host, int num_modes,
+                                                int flags) {
+    const int W = kg_mixed_words(mode_rows_host, num_modes);
+    if (W == 0 || num_queries < 0 || num_queries > KG_MAX_ROWS) return 0;
+    if (kg_mixed_in_lds(W, flags)) return 256;
+    return align_up((size_t)num_queries * 4 * (size_t)W * 4, 256) + 256;
+}
+
+extern "C" size_t mpqe_kg_table_bytes(int num_rels, int num_modes) {
+    if (num_rels < 1 || num_rels > KGT_MAX_RELS || num_modes < 1 || num_modes > KGT_MAX_MODES) return 0;
+    return align_up(sizeof(KgtHead) + (size_t)num_rels * sizeof(KgtRel), 256);
+}
+
+extern "C" int mpqe_kg_table_build(const int64_t *const *rel_offsets_host, const int64_t *const *rel_rows_host,
+                                   const int64_t *rel_edges_host, const int32_t *rel_src_mode_host,
+                                   const int32_t *rel_dst_mode_host, const int32_t *rel_reverse_host, int num_rels,
+                                   const int64_t *mode_rows_host, const uint32_t *const *mode_valid_host,
+                                   const int64_t *const *mode_row_ids_host, int num_modes, void *table, size_t table_bytes,
+                                   void *stream) {
+    const size_t need = mpqe_kg_table_bytes(num_rels, num_modes);
+    if (need == 0 || !rel_offsets_host || !rel_rows_host || !rel_edges_host || !rel_src_mode_host || !rel_dst_mode_host ||
+        !rel_reverse_host || kg_mixed_words(mode_rows_host, num_modes) == 0)
+        return MPQE_ERR_INVALID_ARG;
+    if (!table || ((uintptr_t)table & 7)) return MPQE_ERR_INVALID_ARG;
+    if (table_bytes < need) return MPQE_ERR_WORKSPACE;
+    static thread_local std::vector<char> store;       // (outlives the copy below, as mpqe_kg_sample_queries' does)
+    store.assign(need, 0);
+    char *image = store.data();
+    KgtHead *H = reinterpret_cast<KgtHead *>(image);
+    KgtRel *R = reinterpret_cast<KgtRel *>(image + sizeof(KgtHead));
+    H->num_rels = num_rels;
+    H->num_modes = num_modes;
+    H->magic = KGT_MAGIC;
+    for (int m = 0; m < num_modes; ++m) {
+        H->mode_rows[m] = mode_rows_host[m];
+        H->valid[m] = mode_valid_host ? mode_valid_host[m] : nullptr;
+        H->row_ids[m] = mode_row_ids_host ? reinterpret_cast<const long long *>(mode_row_ids_host[m]) : nullptr;
+    }
+    for (int i = 0; i < num_rels; ++i) {
+        const int src = rel_src_mode_host[i], dst = rel_dst_mode_host[i], rv = rel_reverse_host[i];
+        if (src < 0 || src >= num_modes || dst < 0 || dst >= num_modes || rv < -1 || rv >= num_rels) return MPQE_ERR_INVALID_ARG;
+        if (!rel_offsets_host[i] || rel_edges_host[i] < 0 || (rel_edges_host[i] > 0 && !rel_rows_host[i]))
+            return MPQE_ERR_INVALID_ARG;
+        R[i].off = reinterpret_cast<const long long *>(rel_offsets_host[i]);
+        R[i].rows = reinterpret_cast<const long long *>(rel_rows_host[i]);
+        R[i].edges = rel_edges_host[i];
+        R[i].n_src = (int)mode_rows_host[src];
+        R[i].n_dst = (int)mode_rows_host[dst];
+        R[i].src = src;
+        R[i].dst = dst;
+        R[i].reverse = rv;
+    }
+    hipStream_t s = as_stream(stream);
+    if (hipMemcpyAsync(table, image, need, hipMemcpyHostToDevice, s) != hipSuccess) return MPQE_ERR_LAUNCH;
+    return MPQE_OK;
+}
+
+extern "C" int mpqe_kg_answers_mixed(const void *table, const int64_t *mode_rows_host, int num_modes, int query_type,
+                                     const int64_t *records, int64_t num_queries, const int64_t *probe_rows,
+                                     uint32_t *answers, uint32_t *hard, int64_t out_words, int64_t *counts,
+                                     int32_t *target_mode, int32_t *member, int flags, void *workspace,
+                                     size_t workspace_bytes, int32_t *err, void *stream) {
+    const int64_t Q = num_queries;
+    const int W = kg_mixed_words(mode_rows_host, num_modes);
+    KgShape S;
+    if (W == 0 || Q < 0 || Q > KG_MAX_ROWS || !kg_shape(query_type, S)) return MPQE_ERR_INVALID_ARG;
+    if (flags & ~(MPQE_KG_GLOBAL_BITS | MPQE_KG_COUNT_HARD)) return MPQE_ERR_INVALID_ARG;
+    if ((answers || hard) && out_words < W) return MPQE_ERR_INVALID_ARG;
+    if (Q == 0) return MPQE_OK;
+    if (!table || ((uintptr_t)table & 7) || !records || !target_mode) return MPQE_ERR_INVALID_ARG;
+    const bool in_lds = kg_mixed_in_lds(W, flags);
+    const size_t need = in_lds ? 256 : align_up((size_t)Q * 4 * (size_t)W * 4, 256) + 256;
+    if (!in_lds && (!workspace || ((uintptr_t)workspace & 3))) return MPQE_ERR_INVALID_ARG;
+    if (workspace_bytes < need) return MPQE_ERR_WORKSPACE;
+    const bool want_hard = hard != nullptr || (flags & MPQE_KG_COUNT_HARD);
+    const long long words = answers || hard ? (long long)out_words : 0;
+    hipStream_t s = as_stream(stream);
+    const char *tab = reinterpret_cast<const char *>(table);
+    const long long *rec = reinterpret_cast<const long long *>(records);
+    const long long *probe = reinterpret_cast<const long long *>(probe_rows);
+    long long *cnt = reinterpret_cast<long long *>(counts);
+    if (in_lds) {
+        hipLaunchKernelGGL(kg_answers_mixed_kernel<false>, dim3((unsigned)Q), dim3(KG_THREADS), 0, s, S, tab, W, want_hard,
+                           rec, probe, (long long)Q, answers, hard, words, cnt, target_mode, member, (uint32_t *)nullptr, err);
+        return mpqe_launch_status();
+    }
+    hipLaunchKernelGGL(kg_answers_mixed_kernel<true>, dim3((unsigned)Q), dim3(KG_THREADS), 0, s, S, tab, W, want_hard, rec,
+                       probe, (long long)Q, answers, hard, words, cnt, target_mode, member,
+                       reinterpret_cast<uint32_t *>(workspace), err);
+    return mpqe_launch_status();
+}

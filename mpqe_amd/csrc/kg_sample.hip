@@ -371,3 +371,137 @@ extern "C" int mpqe_kg_sample_rows(const uint32_t *bits, int64_t num_queries, in
                        reinterpret_cast<long long *>(rows_out), (long long)rows_cap, k, (unsigned long long)seed, err);
     return mpqe_launch_status();
 }
+
+// --------------------------------------------------------- at most k members of a set, queries of DIFFERENT modes
+// mpqe_kg_sample_rows with n and valid taken per query from mode_of_query [Q] and the index's device table (kg_table.h),
+// a row stride for `bits` (the rows of mpqe_kg_answers_mixed: W of the widest mode) and q_base added to the query's
+// position in the draw key, so a batch cut into chunks draws what the whole batch draws. ids_out: the same lists as entity
+// ids, through the table's row -> id arrays. The draw is the one above, statement for statement.
+#include "kg_table.h"
+
+__global__ __launch_bounds__(KGS_THREADS) void kg_sample_rows_mixed_kernel(
+    const char *__restrict__ table, const uint32_t *__restrict__ bits, long long stride,
+    const int32_t *__restrict__ mode_of_query, long long q_base, int select, const long long *__restrict__ offsets,
+    long long *__restrict__ rows_out, long long *__restrict__ ids_out, long long cap, int k, unsigned long long seed,
+    int32_t *err) {
+    __shared__ int csum[KGS_MAX_CHUNKS + 1];        // chunk sums, then their exclusive scan; [chunks] = the total
+    __shared__ int wsum[KGS_WAVES];
+    const long long q = blockIdx.x;
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    const KgtHead &H = *kgt_head(table);
+    const long long lo = offsets[q], hi = offsets[q + 1];
+    const int mode = mode_of_query[q];
+    if (lo < 0 || hi < lo || hi > cap || H.magic != KGT_MAGIC || mode < -1 || mode >= H.num_modes) {     // (uniform)
+        if (t == 0) flag_error(err, MPQE_FLAG_BAD_INDEX);
+        return;
+    }
+    if (mode < 0) {             // a query that produced nothing: its segment must be empty
+        if (t == 0 && hi != lo) flag_error(err, MPQE_FLAG_BAD_INDEX);
+        return;
+    }
+    const long long n = H.mode_rows[mode];
+    const long long W = (n + 31) >> 5;
+    if (n < 1 || n > KGS_MAX_SAMPLE_ROWS || W > stride) {       // (uniform; the host checked its own copy of the modes)
+        if (t == 0) flag_error(err, MPQE_FLAG_BAD_INDEX);
+        return;
+    }
+    const uint32_t *valid = H.valid[mode];
+    const long long *row_ids = H.row_ids[mode];
+    const int chunks = (int)((W + KGS_CHUNK_WORDS - 1) / KGS_CHUNK_WORDS);
+    const uint32_t *mine = bits + q * stride;
+    for (int c = wave; c < chunks; c += KGS_WAVES) {
+        const long long w = (long long)c * KGS_CHUNK_WORDS + lane;
+        int pc = w < W ? __builtin_popcount(kgs_word(mine, valid, select, W, n, w)) : 0;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) pc += __shfl_xor(pc, o, 64);
+        if (lane == 0) csum[c] = pc;
+    }
+    __syncthreads();
+    int own[8], sum = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        own[i] = 8 * t + i < chunks ? csum[8 * t + i] : 0;
+        sum += own[i];
+    }
+    int incl = sum;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int up = __shfl(incl, lane >= o ? lane - o : lane, 64);
+        if (lane >= o) incl += up;
+    }
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    int before = 0, total = 0;
+#pragma unroll
+    for (int i = 0; i < KGS_WAVES; ++i) {
+        before += i < wave ? wsum[i] : 0;
+        total += wsum[i];
+    }
+    int run = before + incl - sum;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        if (8 * t + i < chunks) csum[8 * t + i] = run;
+        run += own[i];
+    }
+    if (t == 0) csum[chunks] = total;
+    __syncthreads();
+
+    const long long c = total;
+    const int m = c < k ? (int)c : k;
+    if (t == 0 && hi - lo != m) flag_error(err, MPQE_FLAG_BAD_INDEX);
+    int h = 1;
+    while (((long long)1 << (2 * h)) < c) ++h;
+    const unsigned long long key = mpqe_mix64(seed ^ mpqe_mix64((unsigned long long)(q_base + q)));
+    for (int j = t; j < m; j += KGS_THREADS) {
+        if (lo + j >= hi) break;                        // a segment shorter than the list: flagged above
+        int rank = (int)(c > k ? kgs_permute(key, c, h, j) : j);
+        int a = 0, b = chunks;                          // the chunk with csum[a] <= rank < csum[a + 1]
+        while (b - a > 1) {
+            const int mid = (a + b) >> 1;
+            if (csum[mid] <= rank) a = mid; else b = mid;
+        }
+        rank -= csum[a];
+        long long w = (long long)a * KGS_CHUNK_WORDS;
+        const long long w_end = w + KGS_CHUNK_WORDS < W ? w + KGS_CHUNK_WORDS : W;
+        uint32_t v = 0u;
+        for (; w < w_end; ++w) {
+            v = kgs_word(mine, valid, select, W, n, w);
+            const int pc = __builtin_popcount(v);
+            if (rank < pc) break;
+            rank -= pc;
+        }
+        if (w >= w_end) {                               // (never: the sums came from the same words)
+            flag_error(err, MPQE_FLAG_INTERNAL);
+            continue;
+        }
+        for (; rank > 0; --rank) v &= v - 1;
+        const long long row = w * 32 + __builtin_ctz(v);
+        if (rows_out) rows_out[lo + j] = row;
+        if (ids_out) ids_out[lo + j] = row_ids ? row_ids[row] : -1;
+    }
+}
+
+extern "C" int mpqe_kg_sample_rows_mixed(const void *table, const int64_t *mode_rows_host, int num_modes,
+                                         const uint32_t *bits, int64_t bits_stride, const int32_t *mode_of_query,
+                                         int64_t num_queries, int64_t q_base, int select, const int64_t *offsets,
+                                         int64_t *rows_out, int64_t *ids_out, int64_t rows_cap, int k, uint64_t seed,
+                                         int32_t *err, void *stream) {
+    if (num_queries < 0 || num_queries > KGS_MAX_SLOTS || q_base < 0 || rows_cap < 0 || k < 1) return MPQE_ERR_INVALID_ARG;
+    if (select != MPQE_KG_ROWS_SET && select != MPQE_KG_ROWS_COMPLEMENT) return MPQE_ERR_INVALID_ARG;
+    if (!mode_rows_host || num_modes < 1 || num_modes > KGS_MAX_MODES) return MPQE_ERR_INVALID_ARG;
+    int64_t widest = 0;
+    for (int m = 0; m < num_modes; ++m) {
+        if (mode_rows_host[m] < 1) return MPQE_ERR_INVALID_ARG;
+        if (mode_rows_host[m] > widest) widest = mode_rows_host[m];
+    }
+    if (k > KGS_MAX_K || widest > KGS_MAX_SAMPLE_ROWS) return MPQE_ERR_UNSUPPORTED;
+    if (bits_stride < (widest + 31) / 32) return MPQE_ERR_INVALID_ARG;
+    if (num_queries == 0) return MPQE_OK;
+    if (!table || ((uintptr_t)table & 7) || !bits || !mode_of_query || !offsets) return MPQE_ERR_INVALID_ARG;
+    if (rows_cap > 0 && !rows_out && !ids_out) return MPQE_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(kg_sample_rows_mixed_kernel, dim3((unsigned)num_queries), dim3(KGS_THREADS), 0, as_stream(stream),
+                       reinterpret_cast<const char *>(table), bits, (long long)bits_stride, mode_of_query, (long long)q_base,
+                       select, reinterpret_cast<const long long *>(offsets), reinterpret_cast<long long *>(rows_out),
+                       reinterpret_cast<long long *>(ids_out), (long long)rows_cap, k, (unsigned long long)seed, err);
+    return mpqe_launch_status();
+}

@@ -17,9 +17,17 @@ sample_test_queries graph.py:227-260, sample_query_subgraph_bytype graph.py:321-
     ans.sample_negative_csr(100, seed), ans.sample_hard_csr(100, seed) # at most 100 negatives a query, on the device
     sets = index.sample_query_sets(['2-chain', '3-inter'], 10000, seed, train_index=None)      # {Formula: QuerySet}
     sets[f].negative_sampler(); sets[f].queries()
+
+Queries of DIFFERENT formulas in one launch (mpqe_kg_answers_mixed, mpqe_kg_sample_rows_mixed; the relations come from every
+query's own record, through a device table of the index built once):
+
+    mixed = index.answers_mixed('3-inter', records, hard=True)         # KGAnswersMixed: counts, target_mode, member, bits
+    mixed.sample_negative_csr(100, seed), mixed.sample_hard_csr(100, seed)
+    sets = index.sample_query_sets(types, 10000, seed, batched=True)   # a cost per type, not per formula
 """
 import contextlib
 import ctypes
+import time
 
 import numpy as np
 import torch
@@ -133,6 +141,8 @@ class KGIndex(object):
         self._start_count = (ctypes.c_int64 * R)(*[t.numel() for t in self.start_rows])
         self._programmes = {}
         self._maps_dev = None
+        self._table = None
+        self.section_times = None       # a dict: sample_query_sets(batched=True) adds its sections' seconds (it then synchronises)
         self.err = ops.new_error_word(self.device)
 
     @contextlib.contextmanager
@@ -320,6 +330,83 @@ class KGIndex(object):
                 counts.data_ptr() if B else None, err.data_ptr(), stream), 'mpqe_kg_sample_neighbours')
         return relations, neigh, counts
 
+    # ------------------------------------------------------------------------------------------ mixed formulas
+    def table(self):
+        """The index as one device table (mpqe_kg_table_build), built on first use and kept -> its aligned address."""
+        if self._table is None:
+            if not self.rels:
+                raise ValueError('KGIndex: the index has no relation')
+            R, M = len(self.rels), len(self.modes)
+            reverse = np.asarray([self.rel_index.get(reverse_relation(r), -1) for r in self.rels], dtype=np.int32)
+            valid = (ctypes.c_void_p * M)(*[self.valid[m].data_ptr() for m in self.modes])
+            row_ids = (ctypes.c_void_p * M)(*[self.row_ids[m].data_ptr() for m in self.modes])
+            with self._call() as (lib, stream):
+                need = lib.mpqe_kg_table_bytes(R, M)
+                if need == 0:
+                    raise ValueError('KGIndex: more relations or modes than the device table covers')
+                buf = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+                ptr = _capi._align256(buf.data_ptr())
+                _capi.check(lib, lib.mpqe_kg_table_build(self._off_arr, self._rows_arr, self._edges_arr, self.rel_src.ctypes.data,
+                                                         self.rel_dst.ctypes.data, reverse.ctypes.data, R,
+                                                         self.mode_rows.ctypes.data, valid, row_ids, M, ptr, need, stream),
+                            'mpqe_kg_table_build')
+            ne = np.asarray([self.num_entities[m] for m in self.modes], dtype=np.int64)
+            base = np.zeros(M, dtype=np.int64)
+            base[1:] = np.cumsum(self.mode_rows)[:-1]
+            self._table = (buf, ptr)
+            self._num_entities_host, self._mode_base_host = ne, base
+            self._num_entities_dev = torch.from_numpy(ne).to(self.device)
+            self._row_ids_cat_host = np.concatenate([self.row_ids_host[m] for m in self.modes])
+        return self._table[1]
+
+    def records_of(self, formulas, queries):
+        """Records [Q, 10] int64 on the device, in the layout sample_queries writes, of graph.Query objects (or anchor id
+        lists) with their formulas: one formula for all of them, or one per query. Only what answers_mixed reads is filled:
+        the relation indices, the anchors' rows as the leaf edges' destinations, and edge 0's source row (the target's, -1
+        without a Query); every other row is -1. All formulas must be of one query type."""
+        formulas = [formulas] * len(queries) if isinstance(formulas, Formula) else list(formulas)
+        if len(formulas) != len(queries):
+            raise ValueError('KGIndex.records_of: one formula per query')
+        out = np.full((len(queries), _capi.KG_QUERY_INTS), -1, dtype=np.int64)
+        if formulas and len(set(f.query_type for f in formulas)) != 1:
+            raise ValueError('KGIndex.records_of: queries of one query type')
+        for i, (f, q) in enumerate(zip(formulas, queries)):
+            qt, rels = f.query_type, f.rels
+            flat = [tuple(r) for r in (rels if qt.endswith('-chain') or qt.endswith('-inter') else
+                                       (rels[0], rels[1][0], rels[1][1]))]
+            # (edge, anchor slot) of the leaf edges
+            leaves = {'1-chain': [(0, 0)], '2-chain': [(1, 0)], '3-chain': [(2, 0)], '2-inter': [(0, 0), (1, 1)],
+                      '3-inter': [(0, 0), (1, 1), (2, 2)], '3-inter_chain': [(0, 0), (2, 1)],
+                      '3-chain_inter': [(1, 0), (2, 1)]}[qt]
+            for e, r in enumerate(flat):
+                if r not in self.rel_index:
+                    raise KeyError('KGIndex: no adjacency for relation %r' % (r,))
+                out[i, 2 + 3 * e] = self.rel_index[r]
+            anchors = q.anchor_nodes if hasattr(q, 'anchor_nodes') else q
+            for e, slot in leaves:
+                out[i, 3 + 3 * e] = self._rows_of(f.anchor_modes[slot], np.asarray([anchors[slot]], dtype=np.int64))[0]
+            if hasattr(q, 'target_node'):
+                out[i, 1] = self._rows_of(f.target_mode, np.asarray([q.target_node], dtype=np.int64))[0]
+            out[i, 0] = 1
+        return torch.from_numpy(out).to(self.device)
+
+    def answers_mixed(self, query_type, records, hard=False, probe_rows=None, bits=True, global_bits=False,
+                      max_bitmap_bytes=1 << 30):
+        """The exact answers of a batch of queries of one query type whose relations differ per query, one launch (per
+        chunk): records [Q, 10] int64 on the device as sample_queries / records_of give them -> KGAnswersMixed. hard: the
+        hard negatives' sets and counts too. probe_rows [Q]: the rows whose membership in the answers `member` reports
+        (default: the records' target rows). bits=False: counts, target_mode and member only, no bitmap leaves the kernel.
+        The bitmaps are [Q, W(widest mode)]; where they -- with the workspace of modes too wide for LDS -- pass
+        max_bitmap_bytes, the batch is walked in chunks and the bitmaps are not kept: the sampled CSRs recompute them
+        chunk by chunk (the draw key takes the query's position in the whole batch, so the chunking changes nothing)."""
+        qt = _capi.QUERY_TYPE_IDS[query_type] if isinstance(query_type, str) else int(query_type)
+        records = records.to(device=self.device, dtype=torch.int64).contiguous()
+        if probe_rows is not None:
+            probe_rows = probe_rows.to(device=self.device, dtype=torch.int64).contiguous()
+        out = KGAnswersMixed(self, qt, records, bool(hard), probe_rows, bool(global_bits), int(max_bitmap_bytes))
+        out._fill(bool(bits))
+        return out
+
     def _records_by_formula(self, qt_name, records):
         """The accepted slots of a host [Q, 10] array grouped by formula -> {Formula: (slots, target rows [B], anchor rows
         [B, A], variable rows [B, V])}; the same reading of the query tuple as graph.Query's."""
@@ -348,13 +435,29 @@ class KGIndex(object):
         return out
 
     def sample_query_sets(self, query_types, per_type, seed, neg_sample_max=100, train_index=None, max_rounds=8,
-                          max_tries=8):
+                          max_tries=8, batched=False):
         """The reference's Graph.sample_queries (train_index None) / sample_test_queries pipeline on the device: walk,
         group the accepted slots by formula, one answers(hard=True) call per formula, keep a query only if it has a
         negative (and, for the intersection types, a hard negative) and -- with train_index, an index of the same modes and
         node map over the training edges -- only if its target does NOT answer it on the training graph; then at most
         neg_sample_max negatives / hard negatives per kept query. Rounds repeat until `per_type` queries per type or
-        max_rounds. -> {Formula: QuerySet}. A pure function of (seed, the index)."""
+        max_rounds. -> {Formula: QuerySet}. A pure function of (seed, the index).
+
+        batched=True: the same walk, filter and "first `want` accepted slots" rule, and so the same queries per formula in
+        the same order, at a cost per query TYPE instead of per formula: per type and round one answers_mixed(hard) call
+        over all slots, one member-only call on train_index, the filter as tensor operations, one read-back, one negative
+        and one hard draw. The kept queries of a type are ordered by (formula's relation indices ascending, round, slot)
+        in one store; every formula's QuerySet is a slice of it with its offsets_host mirror filled.
+        Seeds. With type_seed = seed * 1000003 + 7919 * type id (mod 2^63), round r walks with type_seed + 104729 r in both
+        forms. The default draws formula number g's negatives (g = 0, 1, ... in ascending relation indices within the
+        round) with that + 15485863 (g + 1), the hard negatives with one more, keyed by the query's position among the
+        formula's kept queries of the round. batched=True draws the whole round with type_seed + 104729 r + 15485863 (hard:
+        one more), keyed by the query's position among ALL the round's kept queries in the store's order; QuerySet.draw
+        holds (seed, position) per query. With neg_sample_max at or above every list's length both forms give every
+        list whole and ascending, hence the same sets; below it they draw different uniform subsets."""
+        if batched:
+            return self._sample_query_sets_batched(query_types, int(per_type), seed, int(neg_sample_max), train_index,
+                                                   int(max_rounds), max_tries)
         sets = {}
         for qt_name in query_types:
             have, parts = 0, {}
@@ -398,6 +501,171 @@ class KGIndex(object):
                 sets[formula] = QuerySet._from_parts(self, formula, chunks)
         return sets
 
+    def _formula_of(self, qt_name, rel_ids):
+        rels = [self.rels[int(r)] for r in rel_ids]
+        if qt_name.endswith('-chain') or qt_name.endswith('-inter'):
+            return Formula(qt_name, tuple(rels))
+        return Formula(qt_name, (rels[0], (rels[1], rels[2])))
+
+    def _sample_query_sets_batched(self, query_types, per_type, seed, k, train_index, max_rounds, max_tries):
+        dev = self.device
+        self.table()
+        remap = None
+        if train_index is not None:
+            # a relation's index in the training index; -1 where that index cannot walk it (it lacks the relation itself --
+            # the record names it -- or its inverse, whose CSR the hop walks)
+            remap_host = np.asarray([train_index.rel_index[r] if r in train_index.rel_index and
+                                     reverse_relation(r) in train_index.rel_index else -1 for r in self.rels], dtype=np.int64)
+            remap = torch.from_numpy(remap_host).to(dev)
+        n_edges_of = {'1-chain': 1, '2-chain': 2, '3-chain': 3, '2-inter': 2, '3-inter': 3, '3-inter_chain': 3,
+                      '3-chain_inter': 3}
+        columns = {'3-inter_chain': ([0, 2], [1]), '3-chain_inter': ([1, 2], [0])}        # (anchor edges, variable edges)
+        sets = {}
+        clock = [time.perf_counter()]
+
+        def tick(section):
+            if self.section_times is not None:
+                if dev.type == 'cuda':
+                    torch.cuda.synchronize(dev)
+                now = time.perf_counter()
+                self.section_times[section] = self.section_times.get(section, 0.0) + now - clock[0]
+                clock[0] = now
+        for qt_name in query_types:
+            n_e, inter = n_edges_of[qt_name], 'inter' in qt_name
+            rel_cols = slice(2, 2 + 3 * n_e, 3)
+            if qt_name.endswith('-chain'):
+                a_cols, v_cols = [n_e - 1], list(range(n_e - 1))
+            elif qt_name.endswith('-inter'):
+                a_cols, v_cols = list(range(n_e)), []
+            else:
+                a_cols, v_cols = columns[qt_name]
+            have, parts = 0, []
+            type_seed = (int(seed) * 1000003 + 7919 * _capi.QUERY_TYPE_IDS[qt_name]) & (2 ** 63 - 1)
+            for rnd in range(max_rounds):
+                want = per_type - have
+                if want <= 0:
+                    break
+                slots = 2 * want + 64
+                round_seed = type_seed + 104729 * rnd
+                records = self.sample_queries(qt_name, slots, round_seed, max_tries)
+                tick('walk')
+                ans = self.answers_mixed(qt_name, records, hard=inter)
+                tick('answers')
+                found = records[:, 0] == 1
+                ok = found & (ans.target_mode >= 0) & (ans.negative_counts() > 0)
+                if inter:
+                    ok &= ans.counts[1] > 0
+                missing = torch.zeros_like(ok)
+                if train_index is not None:
+                    named = records[:, rel_cols]
+                    mapped = torch.where(named >= 0, remap[named.clamp(min=0)], torch.full_like(named, -1))
+                    missing = found & (mapped < 0).any(dim=1)
+                    on_train = records.clone()
+                    on_train[:, rel_cols] = mapped
+                    on_train[:, 0] = torch.where(missing, torch.zeros_like(records[:, 0]), records[:, 0])
+                    ok &= train_index.answers_mixed(qt_name, on_train, bits=False).member == 0
+                    tick('train filter')
+                host = torch.cat([records, ok.long().unsqueeze(1), missing.long().unsqueeze(1), ans.counts.t(),
+                                  ans.target_mode.long().unsqueeze(1)], dim=1).cpu().numpy()      # the round's one read-back
+                tick('filter + read-back')
+                rec, ok_h, missing_h = host[:, :_capi.KG_QUERY_INTS], host[:, 10] != 0, host[:, 11] != 0
+                if missing_h.any():
+                    for r in rec[np.nonzero(missing_h)[0][0], rel_cols]:
+                        for rel in (reverse_relation(self.rels[int(r)]), self.rels[int(r)]):
+                            if rel not in train_index.rel_index:
+                                raise KeyError('KGIndex: no adjacency for relation %r' % (rel,))
+                accepted = np.nonzero(ok_h)[0]
+                last = accepted[want - 1] if accepted.size >= want else slots
+                keep = accepted[accepted <= last]
+                if keep.size == 0:
+                    continue
+                rel = rec[keep][:, rel_cols]
+                keep = keep[np.lexsort(tuple(rel[:, c] for c in reversed(range(n_e))))]       # (stable: slots ascending)
+                K = keep.size
+                rec_k, c0, c1, mode = rec[keep], host[keep, 12], host[keep, 13], host[keep, 14]
+                sub = ans.subset(torch.from_numpy(keep).to(dev))
+                tick('host pick + subset')
+
+                def scan(lengths):
+                    off = np.zeros(K + 1, dtype=np.int64)
+                    np.cumsum(np.minimum(lengths, k), out=off[1:])
+                    return off
+                neg_off = scan(self._num_entities_host[mode] - c0)
+                hard_off = scan(c1) if inter else None
+                drawn = sub._sample_many([(0, k, round_seed + 15485863, neg_off)] +
+                                         ([(1, k, round_seed + 15485864, hard_off)] if inter else []))
+                neg, hard = drawn[0][0], drawn[1][0] if inter else None
+                tick('draws')
+                e = rec_k[:, 1:1 + 3 * n_e].reshape(K, n_e, 3)
+                src_ids = self._row_ids_cat_host[self._mode_base_host[self.rel_src[e[:, :, 1]]] + e[:, :, 0]]
+                dst_ids = self._row_ids_cat_host[self._mode_base_host[self.rel_dst[e[:, :, 1]]] + e[:, :, 2]]
+                parts.append(dict(rel=e[:, :, 1], rnd=np.full(K, rnd), slot=keep, targets=src_ids[:, 0], anchors=dst_ids[:, a_cols],
+                                  variables=dst_ids[:, v_cols], neg=neg, neg_off=neg_off, hard=hard, hard_off=hard_off,
+                                  seed=np.full(K, round_seed + 15485863), pos=np.arange(K)))
+                have += K
+            if parts:
+                self._store_sets(qt_name, parts, sets)
+            tick('ids + sets')
+        return sets
+
+    def _store_sets(self, qt_name, parts, sets):
+        """the rounds' kept queries as ONE store ordered by (relation indices, round, slot), and its slices per formula"""
+        dev = self.device
+        cat = lambda key: np.concatenate([p[key] for p in parts])                       # noqa: E731
+        rel = cat('rel')
+        n_e = rel.shape[1]
+        perm = None
+        if len(parts) > 1:
+            perm = np.lexsort((cat('slot'), cat('rnd')) + tuple(rel[:, c] for c in reversed(range(n_e))))
+            rel = rel[perm]
+
+        def csr(ids_key, off_key):
+            if parts[0][ids_key] is None:
+                return None, None
+            ids = torch.cat([p[ids_key] for p in parts])
+            lens = np.concatenate([np.diff(p[off_key]) for p in parts])
+            starts = np.zeros(lens.size + 1, dtype=np.int64)
+            np.cumsum(lens, out=starts[1:])
+            if perm is None:
+                return (ids, torch.from_numpy(starts).to(dev)), starts
+            off = np.zeros(lens.size + 1, dtype=np.int64)
+            np.cumsum(lens[perm], out=off[1:])
+            take = np.repeat(starts[:-1][perm] - off[:-1], lens[perm]) + np.arange(int(off[-1]))
+            return (ids[torch.from_numpy(take).to(dev)], torch.from_numpy(off).to(dev)), off
+
+        def ids(key):
+            a = cat(key)
+            return torch.from_numpy(np.ascontiguousarray(a if perm is None else a[perm])).to(dev)
+        neg, neg_off = csr('neg', 'neg_off')
+        hard, hard_off = csr('hard', 'hard_off')
+        targets, anchors, variables = ids('targets'), ids('anchors'), ids('variables')
+        seeds, pos = cat('seed'), cat('pos')
+        if perm is not None:
+            seeds, pos = seeds[perm], pos[perm]
+        keys, first = np.unique(rel, axis=0, return_index=True)
+        bounds = [int(b) for b in first] + [int(rel.shape[0])]
+        G = len(keys)
+
+        def rebased(off):
+            """every formula's own offsets (from 0), end to end: one upload; a formula's are a view of it"""
+            if off is None:
+                return None, None
+            host = [off[bounds[g]:bounds[g + 1] + 1] - off[bounds[g]] for g in range(G)]
+            return host, torch.from_numpy(np.concatenate(host)).to(dev)
+        neg_host, neg_dev = rebased(neg_off)
+        hard_host, hard_dev = rebased(hard_off)
+        for g, rel_ids in enumerate(keys):
+            lo, hi = bounds[g], bounds[g + 1]
+
+            def cut(pair, off, dev_off):
+                if pair is None:
+                    return None
+                return pair[0][int(off[lo]):int(off[hi])], dev_off[lo + g:hi + g + 1]
+            qs = QuerySet(self, self._formula_of(qt_name, rel_ids), targets[lo:hi], anchors[lo:hi], variables[lo:hi],
+                          cut(neg, neg_off, neg_dev), cut(hard, hard_off, hard_dev))
+            qs.__dict__['_offsets_host'] = {False: neg_host[g], True: None if hard_host is None else hard_host[g]}
+            qs.draw = (seeds[lo:hi], pos[lo:hi])
+            sets[qs.formula] = qs
 
 class KGAnswers(object):
     """What KGIndex.answers returns. On the device: bits [Q, W] (the answers), hard_bits [Q, W] or None, counts [2, Q]
@@ -502,6 +770,168 @@ class KGAnswers(object):
     def negative_lists(self):
         valid = self.index.valid[self.mode]
         return self._lists(valid.unsqueeze(0) & ~self.bits)
+
+    def check(self):
+        self.index.check()
+
+
+class KGAnswersMixed(object):
+    """What KGIndex.answers_mixed returns, on the device: counts [2, Q] int64 (|answers|, |hard|; the latter 0 without
+    hard=True), target_mode [Q] int32 (mode INDEX, -1 for a record without a query and for a malformed one), member [Q] int32
+    (is the probe row an answer), and -- when asked for and within max_bitmap_bytes -- bits / hard_bits [Q, W(widest mode)]
+    int32 holding uint32 words (None otherwise: recomputed per chunk where needed)."""
+
+    def __init__(self, index, qt, records, hard, probe_rows, global_bits, max_bitmap_bytes):
+        self.index, self.qt, self.records, self.hard, self.probe_rows = index, qt, records, hard, probe_rows
+        self.global_bits, self.max_bitmap_bytes = global_bits, max_bitmap_bytes
+        self.W = _words(int(index.mode_rows.max()))
+        self.bits = self.hard_bits = None
+        Q, dev = len(self), index.device
+        self.counts = torch.zeros((2, Q), dtype=torch.int64, device=dev)
+        self.target_mode = torch.full((Q,), -1, dtype=torch.int32, device=dev)
+        self.member = torch.zeros((Q,), dtype=torch.int32, device=dev)
+
+    def __len__(self):
+        return int(self.records.shape[0])
+
+    def _flags(self):
+        return (_capi.KG_GLOBAL_BITS if self.global_bits else 0) | (_capi.KG_COUNT_HARD if self.hard else 0)
+
+    def _chunk(self, with_bits):
+        """queries a launch: the bitmaps that leave it and, for modes too wide for LDS, its workspace within the budget"""
+        index = self.index
+        with index._call() as (lib, _):
+            one = lib.mpqe_kg_mixed_workspace_bytes(1, index.mode_rows.ctypes.data, len(index.modes), self._flags())
+        if one == 0:
+            raise ValueError('KGIndex.answers_mixed: modes outside what the kernel covers')
+        per = (16 * self.W if one > 256 else 0) + (4 * self.W * (2 if self.hard else 1) if with_bits else 0)
+        return max(1, min(len(self), self.max_bitmap_bytes // per)) if per else max(1, len(self))
+
+    def _run(self, lo, hi, with_bits, results):
+        """one launch over the queries [lo, hi) -> (bits, hard_bits) or (None, None); results: also fill counts etc."""
+        index, dev, n = self.index, self.index.device, hi - lo
+        bits = torch.empty((n, self.W), dtype=torch.int32, device=dev) if with_bits else None
+        hard_bits = torch.empty((n, self.W), dtype=torch.int32, device=dev) if with_bits and self.hard else None
+        counts = torch.empty((2, n), dtype=torch.int64, device=dev) if results else None
+        target = torch.empty((n,), dtype=torch.int32, device=dev)
+        member = torch.empty((n,), dtype=torch.int32, device=dev) if results else None
+        table = index.table()
+        with index._call() as (lib, stream):
+            need = lib.mpqe_kg_mixed_workspace_bytes(n, index.mode_rows.ctypes.data, len(index.modes), self._flags())
+            ws = torch.empty(need + 256, dtype=torch.uint8, device=dev)
+            _capi.check(lib, lib.mpqe_kg_answers_mixed(
+                table, index.mode_rows.ctypes.data, len(index.modes), self.qt, self.records[lo:hi].data_ptr(), n,
+                None if self.probe_rows is None else self.probe_rows[lo:hi].data_ptr(), ops._p(bits), ops._p(hard_bits),
+                self.W, ops._p(counts), target.data_ptr(), ops._p(member), self._flags(), _capi._align256(ws.data_ptr()), need,
+                index.err.data_ptr(), stream), 'mpqe_kg_answers_mixed')
+        if results:
+            self.counts[:, lo:hi], self.target_mode[lo:hi], self.member[lo:hi] = counts, target, member
+        return bits, hard_bits
+
+    def _fill(self, want_bits):
+        Q = len(self)
+        if Q == 0:
+            return
+        keep = want_bits and self._chunk(True) >= Q
+        step = self._chunk(keep)
+        for lo in range(0, Q, step):
+            got = self._run(lo, min(Q, lo + step), keep, True)
+            if keep:
+                self.bits, self.hard_bits = got         # (keep: one chunk holds the whole batch)
+
+    def _bit_chunks(self):
+        """(lo, hi, bits, hard_bits) over the batch: the kept bitmaps, or each chunk's recomputed"""
+        Q = len(self)
+        if self.bits is not None or Q == 0:
+            if Q:
+                yield 0, Q, self.bits, self.hard_bits
+            return
+        step = self._chunk(True)
+        for lo in range(0, Q, step):
+            hi = min(Q, lo + step)
+            yield (lo, hi) + self._run(lo, hi, True, False)
+
+    def subset(self, pick):
+        """the answers of the queries `pick` (a device index tensor) alone, in that order"""
+        out = KGAnswersMixed(self.index, self.qt, self.records[pick].contiguous(), self.hard,
+                             None if self.probe_rows is None else self.probe_rows[pick].contiguous(), self.global_bits,
+                             self.max_bitmap_bytes)
+        out.counts, out.target_mode, out.member = self.counts[:, pick].contiguous(), self.target_mode[pick].contiguous(), \
+            self.member[pick].contiguous()
+        if self.bits is not None:
+            out.bits = self.bits[pick].contiguous()
+            out.hard_bits = None if self.hard_bits is None else self.hard_bits[pick].contiguous()
+        return out
+
+    def negative_counts(self):
+        """[Q] int64: entities of the query's target mode that are no answer (0 for a query that produced nothing)"""
+        self.index.table()
+        mode = self.target_mode.long()
+        full = self.index._num_entities_dev[mode.clamp(min=0)]
+        return torch.where(mode >= 0, full - self.counts[0], torch.zeros_like(full))
+
+    def _sample_many(self, draws):
+        """draws: [(0 answers' complement | 1 hard set, k, seed, offsets_host or None)] -> [(ids, offsets)] on the device:
+        mpqe_kg_sample_rows_mixed per chunk of bitmaps and draw, q_base = the chunk's first query. The bitmaps that were
+        not kept are recomputed ONCE per chunk for all the draws. offsets_host: the exclusive scan of min(length, k) where
+        the caller has it already (no read-back then)."""
+        index, dev, Q = self.index, self.index.device, len(self)
+        plans = []
+        for which, k, seed, offsets_host in draws:
+            if which and not self.hard:
+                raise ValueError('KGAnswersMixed: computed without hard=True')
+            k = int(k)
+            if offsets_host is not None:
+                offsets = torch.from_numpy(np.ascontiguousarray(offsets_host, dtype=np.int64)).to(dev)
+                total = int(offsets_host[-1])
+            else:
+                offsets = torch.zeros(Q + 1, dtype=torch.int64, device=dev)
+                if Q:
+                    torch.cumsum(torch.clamp(self.counts[1] if which else self.negative_counts(), max=k), 0, out=offsets[1:])
+                total = int(offsets[-1].item()) if Q else 0
+            plans.append((which, k, int(seed) & (2 ** 64 - 1), offsets, total, torch.empty(total, dtype=torch.int64, device=dev)))
+        if Q:
+            table = index.table()
+            for lo, hi, bits, hard_bits in self._bit_chunks():
+                for which, k, seed, offsets, total, ids in plans:
+                    with index._call() as (lib, stream):
+                        _capi.check(lib, lib.mpqe_kg_sample_rows_mixed(
+                            table, index.mode_rows.ctypes.data, len(index.modes), (hard_bits if which else bits).data_ptr(),
+                            self.W, self.target_mode[lo:hi].data_ptr(), hi - lo, lo,
+                            _capi.KG_ROWS_SET if which else _capi.KG_ROWS_COMPLEMENT, offsets[lo:].data_ptr(), None,
+                            ids.data_ptr() if total else None, total, k, seed, index.err.data_ptr(), stream),
+                            'mpqe_kg_sample_rows_mixed')
+        return [(p[5], p[3]) for p in plans]
+
+    def sample_negative_csr(self, k, seed, offsets_host=None):
+        """(ids, offsets): per query at most k entities of its target mode that are no answer -- KGAnswers.sample_negative_csr
+        with the mode taken per query; the draw of query q is keyed by (seed, q), q its position in this batch."""
+        return self._sample_many([(0, k, seed, offsets_host)])[0]
+
+    def sample_hard_csr(self, k, seed, offsets_host=None):
+        return self._sample_many([(1, k, seed, offsets_host)])[0]
+
+    def _lists(self, which):
+        index, out = self.index, []
+        for lo, hi, bits, hard_bits in self._bit_chunks():
+            words = (hard_bits if which else bits).cpu().numpy()
+            modes = self.target_mode[lo:hi].cpu().numpy()
+            for w, m in zip(words, modes):
+                if m < 0:
+                    out.append(np.zeros(0, dtype=np.int64))
+                else:
+                    name = index.modes[int(m)]
+                    out.append(index.row_ids_host[name][_unpack(w[None, :], int(index.mode_rows[int(m)]))[0]])
+        return out
+
+    def lists(self):
+        """per query the answers as global entity ids (host arrays; for tests and small uses)"""
+        return self._lists(0)
+
+    def hard_lists(self):
+        if not self.hard:
+            raise ValueError('KGAnswersMixed: computed without hard=True')
+        return self._lists(1)
 
     def check(self):
         self.index.check()

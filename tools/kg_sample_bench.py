@@ -9,7 +9,9 @@ queries, on
 
 Rows: `walk` mpqe_kg_sample_queries alone for `count` slots (device events around blocks of calls); `sets` the whole
 sample_query_sets call until `count` queries of the type are kept (host clock, ends in a device synchronise; its formulas
-are whichever the walk meets, so it is many small answers() calls -- the row says how many); `host` the stand-in for ONE
+are whichever the walk meets, so it is many small answers() calls -- the row says how many); `batched` the same call with
+batched=True (one answers_mixed launch per type and round, in the same process, timed the same way; sections_ms: one further
+call synchronised between its sections); `host` the stand-in for ONE
 formula, at most --host-cap queries (its cost is per query; the row gives microseconds per query for both sides). The two
 sides do not sample the same distribution: the host draws a target uniformly in the formula's mode and 8 negatives with
 replacement, the device follows the reference's walk and keeps up to 100 distinct negatives. Medians of --blocks timed
@@ -68,6 +70,17 @@ def run_kg(kg, args, device, emit):
             kept = sum(len(s) for s in last['sets'].values())
             emit(dict(base, row='sets', kept=kept, formulas=len(last['sets']), ms=ms, us_per_query=1e3 * ms[0] / max(kept, 1),
                       negatives=int(sum(int(s.neg[0].shape[0]) for s in last['sets'].values()))))
+
+            def batched():
+                last['batched'] = index.sample_query_sets([qt], count, args.seed + 1, neg_sample_max=100, batched=True)
+            ms = kab.host_timed(batched, warm, blocks)
+            kept = sum(len(s) for s in last['batched'].values())
+            index.section_times = {}                # one more call, synchronised between its sections: where the time goes
+            batched()
+            sections, index.section_times = {k: 1e3 * v for k, v in index.section_times.items()}, None
+            emit(dict(base, row='batched', kept=kept, formulas=len(last['batched']), ms=ms,
+                      us_per_query=1e3 * ms[0] / max(kept, 1), sections_ms=sections,
+                      negatives=int(sum(int(s.neg[0].shape[0]) for s in last['batched'].values()))))
             if has_adj:
                 formula = formulas[qt]
                 n = min(count, args.host_cap)
@@ -110,17 +123,19 @@ def main(argv=None):
     except (OSError, IndexError):
         host['cpu'] = 'unknown'
     print(json.dumps(dict(row='host_cpu', **host)), flush=True)
-    print('| kg | query type | count | walk ms | found | sets ms | kept | formulas | sets us/query | host us/query |')
-    print('|---|---|---:|---:|---:|---:|---:|---:|---:|---:|')
+    print('| kg | query type | count | walk ms | found | sets ms | kept | formulas | sets us/query | batched ms | '
+          'batched us/query | host us/query |')
+    print('|---|---|---:|---:|---:|---:|---:|---:|---:|---:|---:|---:|')
     keyed = {}
     for r in rows:
         keyed.setdefault((r['kg'], r['count'], r['query_type']), {})[r['row']] = r
     for (kg, count, qt), d in keyed.items():
         h = '%.1f' % d['host']['us_per_query'] if 'host' in d else 'none'
         s = d['sets']
-        print('| %s | %s | %d | %.3f (%.3f - %.3f) | %.2f | %.1f (%.1f - %.1f) | %d | %d | %.2f | %s |'
+        b = d['batched']
+        print('| %s | %s | %d | %.3f (%.3f - %.3f) | %.2f | %.1f (%.1f - %.1f) | %d | %d | %.2f | %.1f (%.1f - %.1f) | %.2f | %s |'
               % ((kg, qt, count) + tuple(d['walk']['ms']) + (d['walk']['found'],) + tuple(s['ms']) +
-                 (s['kept'], s['formulas'], s['us_per_query'], h)))
+                 (s['kept'], s['formulas'], s['us_per_query']) + tuple(b['ms']) + (b['us_per_query'], h)))
     if args.out:
         with open(args.out, 'w') as f:
             json.dump(dict(host=host, args=vars(args), rows=rows), f, indent=1)

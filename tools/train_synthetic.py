@@ -85,9 +85,10 @@ def device_queries(args, schema, adj, node_maps, device):
     train_index = KGIndex.from_edges(schema, kept, node_maps, device)
     types = sorted(set(q for q, _ in synthetic.FULL_MIX))
     t0 = time.perf_counter()
-    train_sets = train_index.sample_query_sets(types, args.formulas * args.train_queries, args.seed + 1)
+    batched = bool(getattr(args, 'batched_queries', False))
+    train_sets = train_index.sample_query_sets(types, args.formulas * args.train_queries, args.seed + 1, batched=batched)
     test_sets = index.sample_query_sets(types, args.formulas * args.test_queries, args.seed + 2, train_index=train_index,
-                                        max_rounds=32)
+                                        max_rounds=32, batched=batched)
     index.check()
     train_index.check()
     torch.cuda.synchronize()
@@ -169,6 +170,9 @@ def main(argv=None):
     ap.add_argument('--device-queries', action='store_true',
                     help='sample the train / test queries and their negatives on the device index (kg.KGIndex.sample_query_sets: '
                          'the reference\'s KG sampler) instead of the host stand-in synthetic.sample_grounded_queries')
+    ap.add_argument('--batched-queries', action='store_true',
+                    help='with --device-queries: sample_query_sets(batched=True) -- queries of different formulas answered in one '
+                         'launch per query type, the same queries per formula; the draws below the cap of 100 negatives differ')
     ap.add_argument('--device-eval', action='store_true',
                     help='with --device-queries: evaluate the model on the test QuerySets themselves (AUC and percentile rank '
                          'computed on the device, evaluation.eval_auc_queries / eval_perc_queries over kg.QuerySet); the '
@@ -178,6 +182,8 @@ def main(argv=None):
                          'neighbourhood-aggregating Encoder of utils.get_encoder under either --model, trained through '
                          'model.margin_loss; on the device index with --kg-index or --device-queries, else the host path')
     args = ap.parse_args(argv)
+    if args.batched_queries and not args.device_queries:
+        ap.error('--batched-queries needs --device-queries')
     if args.device_eval and (not args.device_queries or args.depth):
         ap.error('--device-eval needs --device-queries and the embedding-lookup encoder (--depth 0)')
     if args.depth:
