@@ -24,9 +24,19 @@
 // Determinism: the only concurrent writes are integer ORs into a bitmap, whose result does not depend on their order;
 // the output is a set, bit-identical run to run by construction. The workspace need not be zeroed: a bitmap is cleared
 // by the workgroup right before it is ORed into, and every word of every output is written.
+//
+// Two kernels walk this programme: kg_answers_kernel (one formula a launch, the hops a KgPlan in kernel arguments) and
+// kg_answers_mixed_kernel (the programme per QUERY, from its record; below). They share kg_or_list, kg_scan_hop and the
+// bitmap helpers, and each still spells its own branch loop, merge, tail hop and write-out: a shared walk behind an
+// accessor was measured 0.3 - 0.5 us slower on the AM shape's scanned hops and not kept. DESIGN.md section 10 lists what
+// differs between the two; a change to one body belongs in the other.
 #include <string.h>
 
+#include <vector>
+
 #include "common.h"
+#include "kg_scan.h"
+#include "kg_table.h"
 
 #define KG_THREADS 256
 #define KG_WAVES 4
@@ -240,9 +250,9 @@ __global__ __launch_bounds__(KG_THREADS) void kg_rows_kernel(const uint32_t *__r
                                                              const long long *__restrict__ offsets,
                                                              long long *__restrict__ rows_out, long long cap,
                                                              int32_t *err) {
-    __shared__ int wsum[KG_WAVES];
+    __shared__ int wsum[KG_SCAN_WAVES];
     const long long q = blockIdx.x;
-    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    const int t = threadIdx.x;
     const long long W = (n + 31) >> 5;
     const long long lo = offsets[q], hi = offsets[q + 1];
     if (lo < 0 || hi < lo || hi > cap) {        // (uniform)
@@ -260,22 +270,8 @@ __global__ __launch_bounds__(KG_THREADS) void kg_rows_kernel(const uint32_t *__r
             v = select == MPQE_KG_ROWS_SET ? b : (select == MPQE_KG_ROWS_COMPLEMENT ? va & ~b : b | ~va);
             if (w == W - 1 && (n & 31)) v &= (1u << (unsigned)(n & 31)) - 1u;
         }
-        const int c = __builtin_popcount(v);
-        int incl = c;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int up = __shfl(incl, lane >= o ? lane - o : lane, 64);
-            if (lane >= o) incl += up;
-        }
-        if (lane == 63) wsum[wave] = incl;
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int i = 0; i < KG_WAVES; ++i) {
-            before += i < wave ? wsum[i] : 0;
-            total += wsum[i];
-        }
-        long long p = run + before + incl - c;
+        int total;
+        long long p = run + kg_workgroup_scan(__builtin_popcount(v), wsum, total);
         while (v) {
             const int b = __builtin_ctz(v);
             v &= v - 1;
@@ -350,15 +346,35 @@ static int kg_compile(const int32_t *prog, const int64_t *const *rel_offsets, co
     return MPQE_OK;
 }
 
-static bool kg_in_lds(const KgPlan &P, int flags) { return P.W <= KG_LDS_WORDS && !(flags & MPQE_KG_GLOBAL_BITS); }
+// The home of the bitmaps of W words each, what the workspace must hold for Q queries, and the launch: both answers entry
+// points size, check and start their kernel here.
+static bool kg_in_lds(int W, int flags) { return W <= KG_LDS_WORDS && !(flags & MPQE_KG_GLOBAL_BITS); }
+
+static size_t kg_bitmap_bytes(int64_t Q, int W, int flags) {
+    return kg_in_lds(W, flags) ? 256 : align_up((size_t)Q * 4 * (size_t)W * 4, 256) + 256;
+}
+
+// One workgroup a query of `lds_kernel` or `global_kernel`, the <false> and <true> of one kernel template, whose arguments
+// are `args`, then the bitmaps' workspace (NULL in LDS) and the error word.
+template <class... P, class... A>
+static int kg_launch(void (*lds_kernel)(P...), void (*global_kernel)(P...), int64_t Q, int W, int flags, void *workspace,
+                     size_t workspace_bytes, int32_t *err, void *stream, A... args) {
+    const bool in_lds = kg_in_lds(W, flags);
+    if (!in_lds && (!workspace || ((uintptr_t)workspace & 3))) return MPQE_ERR_INVALID_ARG;
+    // (short of what the size query returns for these flags -- in LDS too, where the 256 bytes are not touched)
+    if (workspace_bytes < kg_bitmap_bytes(Q, W, flags)) return MPQE_ERR_WORKSPACE;
+    void (*kernel)(P...) = in_lds ? lds_kernel : global_kernel;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)Q), dim3(KG_THREADS), 0, as_stream(stream), args...,
+                       in_lds ? nullptr : reinterpret_cast<uint32_t *>(workspace), err);
+    return mpqe_launch_status();
+}
 
 extern "C" size_t mpqe_kg_workspace_bytes(const int32_t *prog_host, int64_t num_queries, const int64_t *mode_rows_host,
                                           int num_modes, int flags) {
     KgPlan P;
     if (num_queries < 0 || num_queries > KG_MAX_ROWS) return 0;
     if (kg_compile(prog_host, nullptr, nullptr, nullptr, 0, mode_rows_host, num_modes, P) != MPQE_OK) return 0;
-    if (kg_in_lds(P, flags)) return 256;
-    return align_up((size_t)num_queries * 4 * (size_t)P.W * 4, 256) + 256;
+    return kg_bitmap_bytes(num_queries, P.W, flags);
 }
 
 extern "C" int mpqe_kg_answers(const int32_t *prog_host, const int64_t *const *rel_offsets_host,
@@ -376,21 +392,9 @@ extern "C" int mpqe_kg_answers(const int32_t *prog_host, const int64_t *const *r
     if (st != MPQE_OK) return st;
     if (Q == 0) return MPQE_OK;
     if (!anchor_rows || !answers) return MPQE_ERR_INVALID_ARG;
-    // (short of what the size query returns for these flags -- in LDS too, where the 256 bytes are not touched)
-    const size_t need = kg_in_lds(P, flags) ? 256 : align_up((size_t)Q * 4 * (size_t)P.W * 4, 256) + 256;
-    if (!kg_in_lds(P, flags) && (!workspace || ((uintptr_t)workspace & 3))) return MPQE_ERR_INVALID_ARG;
-    if (workspace_bytes < need) return MPQE_ERR_WORKSPACE;
-    hipStream_t s = as_stream(stream);
-    const long long *anc = reinterpret_cast<const long long *>(anchor_rows);
-    long long *cnt = reinterpret_cast<long long *>(counts);
-    if (kg_in_lds(P, flags)) {
-        hipLaunchKernelGGL(kg_answers_kernel<false>, dim3((unsigned)Q), dim3(KG_THREADS), 0, s, P, anc, (long long)Q,
-                           answers, hard, cnt, (uint32_t *)nullptr, err);
-        return mpqe_launch_status();
-    }
-    hipLaunchKernelGGL(kg_answers_kernel<true>, dim3((unsigned)Q), dim3(KG_THREADS), 0, s, P, anc, (long long)Q, answers,
-                       hard, cnt, reinterpret_cast<uint32_t *>(workspace), err);
-    return mpqe_launch_status();
+    return kg_launch(kg_answers_kernel<false>, kg_answers_kernel<true>, Q, P.W, flags, workspace, workspace_bytes, err,
+                     stream, P, reinterpret_cast<const long long *>(anchor_rows), (long long)Q, answers, hard,
+                     reinterpret_cast<long long *>(counts));
 }
 
 extern "C" int mpqe_kg_rows(const uint32_t *bits, int64_t num_queries, int64_t n, const uint32_t *valid, int select,
@@ -415,10 +419,6 @@ extern "C" int mpqe_kg_rows(const uint32_t *bits, int64_t num_queries, int64_t n
 // the one above (kg_or_list, kg_scan_hop, both homes of the bitmaps, W = the widest mode of the index).
 // CSR faults are collected in an LDS word of the workgroup, not in the caller's: a query that met one gets empty sets like
 // any other malformed query, and the caller's word takes one atomic a faulty workgroup instead of one a faulty entry.
-#include <vector>
-
-#include "kg_table.h"
-
 struct KgShape {
     int branches, tail_edge;    // tail_edge: the query edge of the hop after the merge, -1: none
     int hops[3];
@@ -448,12 +448,12 @@ __device__ __forceinline__ void kg_mixed_resolve(const KgShape &S, const char *t
         return;
     }
     if (rec[0] != 1 || H.magic != KGT_MAGIC || H.num_rels < 1 || H.num_rels > KGT_MAX_RELS) return;
-    bool used[3] = {false, false, false};
+    unsigned used = 0u;         // a bit per query edge
     for (int b = 0; b < S.branches; ++b)
-        for (int s = 0; s < S.hops[b]; ++s) used[S.edge[b][s]] = true;
-    if (S.tail_edge >= 0) used[S.tail_edge] = true;
+        for (int s = 0; s < S.hops[b]; ++s) used |= 1u << S.edge[b][s];
+    if (S.tail_edge >= 0) used |= 1u << S.tail_edge;
     for (int e = 0; e < 3; ++e) {
-        if (!used[e]) continue;
+        if (!((used >> e) & 1u)) continue;
         const long long r = rec[2 + 3 * e];
         if (r < 0 || r >= H.num_rels) return;
         const int rv = rel[r].reverse;
@@ -644,23 +644,15 @@ static bool kg_shape(int qt, KgShape &S) {
 
 // the widest mode's words; 0: arguments out of range
 static int kg_mixed_words(const int64_t *mode_rows, int num_modes) {
-    if (!mode_rows || num_modes < 1 || num_modes > KGT_MAX_MODES) return 0;
-    int64_t widest = 0;
-    for (int m = 0; m < num_modes; ++m) {
-        if (mode_rows[m] < 1 || mode_rows[m] > KG_MAX_ROWS) return 0;
-        if (mode_rows[m] > widest) widest = mode_rows[m];
-    }
-    return (int)((widest + 31) / 32);
+    const int64_t widest = kgt_widest_mode(mode_rows, num_modes);
+    return widest > KG_MAX_ROWS ? 0 : (int)((widest + 31) / 32);
 }
-
-static bool kg_mixed_in_lds(int W, int flags) { return W <= KG_LDS_WORDS && !(flags & MPQE_KG_GLOBAL_BITS); }
 
 extern "C" size_t mpqe_kg_mixed_workspace_bytes(int64_t num_queries, const int64_t *mode_rows_host, int num_modes,
                                                 int flags) {
     const int W = kg_mixed_words(mode_rows_host, num_modes);
     if (W == 0 || num_queries < 0 || num_queries > KG_MAX_ROWS) return 0;
-    if (kg_mixed_in_lds(W, flags)) return 256;
-    return align_up((size_t)num_queries * 4 * (size_t)W * 4, 256) + 256;
+    return kg_bitmap_bytes(num_queries, W, flags);
 }
 
 extern "C" size_t mpqe_kg_table_bytes(int num_rels, int num_modes) {
@@ -725,24 +717,10 @@ extern "C" int mpqe_kg_answers_mixed(const void *table, const int64_t *mode_rows
     if ((answers || hard) && out_words < W) return MPQE_ERR_INVALID_ARG;
     if (Q == 0) return MPQE_OK;
     if (!table || ((uintptr_t)table & 7) || !records || !target_mode) return MPQE_ERR_INVALID_ARG;
-    const bool in_lds = kg_mixed_in_lds(W, flags);
-    const size_t need = in_lds ? 256 : align_up((size_t)Q * 4 * (size_t)W * 4, 256) + 256;
-    if (!in_lds && (!workspace || ((uintptr_t)workspace & 3))) return MPQE_ERR_INVALID_ARG;
-    if (workspace_bytes < need) return MPQE_ERR_WORKSPACE;
     const bool want_hard = hard != nullptr || (flags & MPQE_KG_COUNT_HARD);
     const long long words = answers || hard ? (long long)out_words : 0;
-    hipStream_t s = as_stream(stream);
-    const char *tab = reinterpret_cast<const char *>(table);
-    const long long *rec = reinterpret_cast<const long long *>(records);
-    const long long *probe = reinterpret_cast<const long long *>(probe_rows);
-    long long *cnt = reinterpret_cast<long long *>(counts);
-    if (in_lds) {
-        hipLaunchKernelGGL(kg_answers_mixed_kernel<false>, dim3((unsigned)Q), dim3(KG_THREADS), 0, s, S, tab, W, want_hard,
-                           rec, probe, (long long)Q, answers, hard, words, cnt, target_mode, member, (uint32_t *)nullptr, err);
-        return mpqe_launch_status();
-    }
-    hipLaunchKernelGGL(kg_answers_mixed_kernel<true>, dim3((unsigned)Q), dim3(KG_THREADS), 0, s, S, tab, W, want_hard, rec,
-                       probe, (long long)Q, answers, hard, words, cnt, target_mode, member,
-                       reinterpret_cast<uint32_t *>(workspace), err);
-    return mpqe_launch_status();
+    return kg_launch(kg_answers_mixed_kernel<false>, kg_answers_mixed_kernel<true>, Q, W, flags, workspace, workspace_bytes,
+                     err, stream, S, reinterpret_cast<const char *>(table), W, want_hard,
+                     reinterpret_cast<const long long *>(records), reinterpret_cast<const long long *>(probe_rows),
+                     (long long)Q, answers, hard, words, reinterpret_cast<long long *>(counts), target_mode, member);
 }

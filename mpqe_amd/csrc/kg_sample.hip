@@ -22,11 +22,17 @@
 //   members the ranks are 0 .. c - 1 (the list of mpqe_kg_rows, bit for bit); with more, rank j = P(j), j < k, for a keyed
 //   bijection P of [0, c): a KGS_FEISTEL_ROUNDS-round balanced Feistel network over [0, 4^h), 4^h >= c, walked along its
 //   cycle until it lands below c. No memory, no sort; distinct by construction.
+//
+// mpqe_kg_sample_rows_mixed  the same draw (kgs_chunk_sums, kgs_member, kgs_draw: ONE copy) for queries of different modes:
+//   n and valid per query from the index's device table (kg_table.h), a row stride for `bits`, q_base in the draw key, and
+//   the lists as entity ids too.
 #include <string.h>
 
 #include <vector>
 
+#include "kg_scan.h"
 #include "kg_stream.h"
+#include "kg_table.h"
 
 #define KGS_THREADS 256
 #define KGS_WAVES 4
@@ -261,13 +267,103 @@ extern "C" int mpqe_kg_sample_queries(const int64_t *const *rel_offsets_host, co
 }
 
 // ------------------------------------------------------------------------------------ at most k members of a set
-__device__ __forceinline__ uint32_t kgs_word(const uint32_t *__restrict__ bits, const uint32_t *__restrict__ valid,
-                                             int select, long long W, long long n, long long w) {
-    const uint32_t b = bits[w];
-    const uint32_t va = valid ? valid[w] : ~0u;
-    uint32_t v = select == MPQE_KG_ROWS_SET ? b : va & ~b;
-    if (w == W - 1 && (n & 31)) v &= (1u << (unsigned)(n & 31)) - 1u;
-    return v;
+// One query's selected set: the rows below n whose bit in `bits` is set (MPQE_KG_ROWS_SET), or is not and whose bit in
+// `valid` is (MPQE_KG_ROWS_COMPLEMENT; valid NULL: every row below n).
+struct KgsSet {
+    const uint32_t *bits, *valid;
+    int select;
+    long long n, W;
+    int chunks;                 // of KGS_CHUNK_WORDS words
+    __device__ __forceinline__ KgsSet(const uint32_t *bits_, const uint32_t *valid_, int select_, long long n_)
+        : bits(bits_), valid(valid_), select(select_), n(n_), W((n_ + 31) >> 5),
+          chunks((int)((W + KGS_CHUNK_WORDS - 1) / KGS_CHUNK_WORDS)) {}
+    __device__ __forceinline__ uint32_t word(long long w) const {
+        const uint32_t b = bits[w];
+        const uint32_t va = valid ? valid[w] : ~0u;
+        uint32_t v = select == MPQE_KG_ROWS_SET ? b : va & ~b;
+        if (w == W - 1 && (n & 31)) v &= (1u << (unsigned)(n & 31)) - 1u;
+        return v;
+    }
+};
+
+// csum[i] = the members in the chunks below i, i <= S.chunks: the population counts of the selected words summed per chunk,
+// then their exclusive scan over the workgroup; -> csum[S.chunks], the size of the set. csum: KGS_MAX_CHUNKS + 1 ints and
+// wsum: KG_SCAN_WAVES ints of the kernel's LDS. Ends on a barrier.
+__device__ __forceinline__ int kgs_chunk_sums(const KgsSet &S, int *csum, int *wsum) {
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    for (int c = wave; c < S.chunks; c += KGS_WAVES) {
+        const long long w = (long long)c * KGS_CHUNK_WORDS + lane;
+        int pc = w < S.W ? __builtin_popcount(S.word(w)) : 0;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) pc += __shfl_xor(pc, o, 64);
+        if (lane == 0) csum[c] = pc;
+    }
+    __syncthreads();
+    int own[8], sum = 0;        // thread t owns the 8 entries from 8 t
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        own[i] = 8 * t + i < S.chunks ? csum[8 * t + i] : 0;
+        sum += own[i];
+    }
+    int total;
+    int run = kg_workgroup_scan(sum, wsum, total);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        if (8 * t + i < S.chunks) csum[8 * t + i] = run;
+        run += own[i];
+    }
+    if (t == 0) csum[S.chunks] = total;
+    __syncthreads();
+    return total;
+}
+
+// The row of the member of rank `rank` (< the size of the set): a binary search over the chunk sums, a walk over the chunk's
+// words, a select inside the word. -1 (flagged): never.
+__device__ __forceinline__ long long kgs_member(const KgsSet &S, const int *csum, int rank, int32_t *err) {
+    int a = 0, b = S.chunks;                            // the chunk with csum[a] <= rank < csum[a + 1]
+    while (b - a > 1) {
+        const int mid = (a + b) >> 1;
+        if (csum[mid] <= rank) a = mid; else b = mid;
+    }
+    rank -= csum[a];
+    long long w = (long long)a * KGS_CHUNK_WORDS;
+    const long long w_end = w + KGS_CHUNK_WORDS < S.W ? w + KGS_CHUNK_WORDS : S.W;
+    uint32_t v = 0u;
+    for (; w < w_end; ++w) {
+        v = S.word(w);
+        const int pc = __builtin_popcount(v);
+        if (rank < pc) break;
+        rank -= pc;
+    }
+    if (w >= w_end) {                                   // (never: the sums came from the same words)
+        flag_error(err, MPQE_FLAG_INTERNAL);
+        return -1;
+    }
+    for (; rank > 0; --rank) v &= v - 1;
+    return w * 32 + __builtin_ctz(v);
+}
+
+// min(c, k) members of the set of c into the slots [lo, hi) of rows_out (may be NULL) and, as entity ids through row_ids
+// (NULL: -1), of ids_out (may be NULL): all of them ascending, or those of rank P(j), j < k, for the bijection keyed by `key`.
+__device__ __forceinline__ void kgs_draw(const KgsSet &S, const int *csum, long long c, unsigned long long key, int k,
+                                         long long lo, long long hi, long long *rows_out, long long *ids_out,
+                                         const long long *row_ids, int32_t *err) {
+    const int t = threadIdx.x;
+    const int m = c < k ? (int)c : k;
+    if (t == 0 && hi - lo != m) flag_error(err, MPQE_FLAG_BAD_INDEX);
+    int h = 1;
+    while (((long long)1 << (2 * h)) < c) ++h;
+    for (int j = t; j < m; j += KGS_THREADS) {
+        if (lo + j >= hi) break;                        // a segment shorter than the list: flagged above
+        const long long row = kgs_member(S, csum, (int)(c > k ? kgs_permute(key, c, h, j) : j), err);
+        if (row < 0) continue;
+        if (rows_out) rows_out[lo + j] = row;
+        if (ids_out) ids_out[lo + j] = row_ids ? row_ids[row] : -1;
+    }
+}
+
+__device__ __forceinline__ unsigned long long kgs_draw_key(unsigned long long seed, long long position) {
+    return mpqe_mix64(seed ^ mpqe_mix64((unsigned long long)position));
 }
 
 __global__ __launch_bounds__(KGS_THREADS) void kg_sample_rows_kernel(const uint32_t *__restrict__ bits, long long n,
@@ -275,87 +371,17 @@ __global__ __launch_bounds__(KGS_THREADS) void kg_sample_rows_kernel(const uint3
                                                                      const long long *__restrict__ offsets,
                                                                      long long *__restrict__ rows_out, long long cap, int k,
                                                                      unsigned long long seed, int32_t *err) {
-    __shared__ int csum[KGS_MAX_CHUNKS + 1];        // chunk sums, then their exclusive scan; [chunks] = the total
-    __shared__ int wsum[KGS_WAVES];
+    __shared__ int csum[KGS_MAX_CHUNKS + 1];
+    __shared__ int wsum[KG_SCAN_WAVES];
     const long long q = blockIdx.x;
-    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
-    const long long W = (n + 31) >> 5;
-    const int chunks = (int)((W + KGS_CHUNK_WORDS - 1) / KGS_CHUNK_WORDS);
     const long long lo = offsets[q], hi = offsets[q + 1];
     if (lo < 0 || hi < lo || hi > cap) {        // (uniform)
-        if (t == 0) flag_error(err, MPQE_FLAG_BAD_INDEX);
+        if (threadIdx.x == 0) flag_error(err, MPQE_FLAG_BAD_INDEX);
         return;
     }
-    const uint32_t *mine = bits + q * W;
-    for (int c = wave; c < chunks; c += KGS_WAVES) {
-        const long long w = (long long)c * KGS_CHUNK_WORDS + lane;
-        int pc = w < W ? __builtin_popcount(kgs_word(mine, valid, select, W, n, w)) : 0;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) pc += __shfl_xor(pc, o, 64);
-        if (lane == 0) csum[c] = pc;
-    }
-    __syncthreads();
-    // exclusive scan of csum[0 .. chunks): thread t owns the 8 entries from 8 t
-    int own[8], sum = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        own[i] = 8 * t + i < chunks ? csum[8 * t + i] : 0;
-        sum += own[i];
-    }
-    int incl = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int up = __shfl(incl, lane >= o ? lane - o : lane, 64);
-        if (lane >= o) incl += up;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int i = 0; i < KGS_WAVES; ++i) {
-        before += i < wave ? wsum[i] : 0;
-        total += wsum[i];
-    }
-    int run = before + incl - sum;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        if (8 * t + i < chunks) csum[8 * t + i] = run;
-        run += own[i];
-    }
-    if (t == 0) csum[chunks] = total;
-    __syncthreads();
-
-    const long long c = total;
-    const int m = c < k ? (int)c : k;
-    if (t == 0 && hi - lo != m) flag_error(err, MPQE_FLAG_BAD_INDEX);
-    int h = 1;
-    while (((long long)1 << (2 * h)) < c) ++h;
-    const unsigned long long key = mpqe_mix64(seed ^ mpqe_mix64((unsigned long long)q));
-    for (int j = t; j < m; j += KGS_THREADS) {
-        if (lo + j >= hi) break;                        // a segment shorter than the list: flagged above
-        int rank = (int)(c > k ? kgs_permute(key, c, h, j) : j);
-        int a = 0, b = chunks;                          // the chunk with csum[a] <= rank < csum[a + 1]
-        while (b - a > 1) {
-            const int mid = (a + b) >> 1;
-            if (csum[mid] <= rank) a = mid; else b = mid;
-        }
-        rank -= csum[a];
-        long long w = (long long)a * KGS_CHUNK_WORDS;
-        const long long w_end = w + KGS_CHUNK_WORDS < W ? w + KGS_CHUNK_WORDS : W;
-        uint32_t v = 0u;
-        for (; w < w_end; ++w) {
-            v = kgs_word(mine, valid, select, W, n, w);
-            const int pc = __builtin_popcount(v);
-            if (rank < pc) break;
-            rank -= pc;
-        }
-        if (w >= w_end) {                               // (never: the sums came from the same words)
-            flag_error(err, MPQE_FLAG_INTERNAL);
-            continue;
-        }
-        for (; rank > 0; --rank) v &= v - 1;
-        rows_out[lo + j] = w * 32 + __builtin_ctz(v);
-    }
+    const KgsSet S(bits + q * ((n + 31) >> 5), valid, select, n);
+    const int c = kgs_chunk_sums(S, csum, wsum);
+    kgs_draw(S, csum, c, kgs_draw_key(seed, q), k, lo, hi, rows_out, nullptr, nullptr, err);
 }
 
 extern "C" int mpqe_kg_sample_rows(const uint32_t *bits, int64_t num_queries, int64_t n, const uint32_t *valid, int select,
@@ -376,18 +402,16 @@ extern "C" int mpqe_kg_sample_rows(const uint32_t *bits, int64_t num_queries, in
 // mpqe_kg_sample_rows with n and valid taken per query from mode_of_query [Q] and the index's device table (kg_table.h),
 // a row stride for `bits` (the rows of mpqe_kg_answers_mixed: W of the widest mode) and q_base added to the query's
 // position in the draw key, so a batch cut into chunks draws what the whole batch draws. ids_out: the same lists as entity
-// ids, through the table's row -> id arrays. The draw is the one above, statement for statement.
-#include "kg_table.h"
-
+// ids, through the table's row -> id arrays.
 __global__ __launch_bounds__(KGS_THREADS) void kg_sample_rows_mixed_kernel(
     const char *__restrict__ table, const uint32_t *__restrict__ bits, long long stride,
     const int32_t *__restrict__ mode_of_query, long long q_base, int select, const long long *__restrict__ offsets,
     long long *__restrict__ rows_out, long long *__restrict__ ids_out, long long cap, int k, unsigned long long seed,
     int32_t *err) {
-    __shared__ int csum[KGS_MAX_CHUNKS + 1];        // chunk sums, then their exclusive scan; [chunks] = the total
-    __shared__ int wsum[KGS_WAVES];
+    __shared__ int csum[KGS_MAX_CHUNKS + 1];
+    __shared__ int wsum[KG_SCAN_WAVES];
     const long long q = blockIdx.x;
-    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    const int t = threadIdx.x;
     const KgtHead &H = *kgt_head(table);
     const long long lo = offsets[q], hi = offsets[q + 1];
     const int mode = mode_of_query[q];
@@ -400,85 +424,13 @@ __global__ __launch_bounds__(KGS_THREADS) void kg_sample_rows_mixed_kernel(
         return;
     }
     const long long n = H.mode_rows[mode];
-    const long long W = (n + 31) >> 5;
-    if (n < 1 || n > KGS_MAX_SAMPLE_ROWS || W > stride) {       // (uniform; the host checked its own copy of the modes)
+    if (n < 1 || n > KGS_MAX_SAMPLE_ROWS || ((n + 31) >> 5) > stride) {     // (uniform; the host checked its own copy of the modes)
         if (t == 0) flag_error(err, MPQE_FLAG_BAD_INDEX);
         return;
     }
-    const uint32_t *valid = H.valid[mode];
-    const long long *row_ids = H.row_ids[mode];
-    const int chunks = (int)((W + KGS_CHUNK_WORDS - 1) / KGS_CHUNK_WORDS);
-    const uint32_t *mine = bits + q * stride;
-    for (int c = wave; c < chunks; c += KGS_WAVES) {
-        const long long w = (long long)c * KGS_CHUNK_WORDS + lane;
-        int pc = w < W ? __builtin_popcount(kgs_word(mine, valid, select, W, n, w)) : 0;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) pc += __shfl_xor(pc, o, 64);
-        if (lane == 0) csum[c] = pc;
-    }
-    __syncthreads();
-    int own[8], sum = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        own[i] = 8 * t + i < chunks ? csum[8 * t + i] : 0;
-        sum += own[i];
-    }
-    int incl = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int up = __shfl(incl, lane >= o ? lane - o : lane, 64);
-        if (lane >= o) incl += up;
-    }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int i = 0; i < KGS_WAVES; ++i) {
-        before += i < wave ? wsum[i] : 0;
-        total += wsum[i];
-    }
-    int run = before + incl - sum;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        if (8 * t + i < chunks) csum[8 * t + i] = run;
-        run += own[i];
-    }
-    if (t == 0) csum[chunks] = total;
-    __syncthreads();
-
-    const long long c = total;
-    const int m = c < k ? (int)c : k;
-    if (t == 0 && hi - lo != m) flag_error(err, MPQE_FLAG_BAD_INDEX);
-    int h = 1;
-    while (((long long)1 << (2 * h)) < c) ++h;
-    const unsigned long long key = mpqe_mix64(seed ^ mpqe_mix64((unsigned long long)(q_base + q)));
-    for (int j = t; j < m; j += KGS_THREADS) {
-        if (lo + j >= hi) break;                        // a segment shorter than the list: flagged above
-        int rank = (int)(c > k ? kgs_permute(key, c, h, j) : j);
-        int a = 0, b = chunks;                          // the chunk with csum[a] <= rank < csum[a + 1]
-        while (b - a > 1) {
-            const int mid = (a + b) >> 1;
-            if (csum[mid] <= rank) a = mid; else b = mid;
-        }
-        rank -= csum[a];
-        long long w = (long long)a * KGS_CHUNK_WORDS;
-        const long long w_end = w + KGS_CHUNK_WORDS < W ? w + KGS_CHUNK_WORDS : W;
-        uint32_t v = 0u;
-        for (; w < w_end; ++w) {
-            v = kgs_word(mine, valid, select, W, n, w);
-            const int pc = __builtin_popcount(v);
-            if (rank < pc) break;
-            rank -= pc;
-        }
-        if (w >= w_end) {                               // (never: the sums came from the same words)
-            flag_error(err, MPQE_FLAG_INTERNAL);
-            continue;
-        }
-        for (; rank > 0; --rank) v &= v - 1;
-        const long long row = w * 32 + __builtin_ctz(v);
-        if (rows_out) rows_out[lo + j] = row;
-        if (ids_out) ids_out[lo + j] = row_ids ? row_ids[row] : -1;
-    }
+    const KgsSet S(bits + q * stride, H.valid[mode], select, n);
+    const int c = kgs_chunk_sums(S, csum, wsum);
+    kgs_draw(S, csum, c, kgs_draw_key(seed, q_base + q), k, lo, hi, rows_out, ids_out, H.row_ids[mode], err);
 }
 
 extern "C" int mpqe_kg_sample_rows_mixed(const void *table, const int64_t *mode_rows_host, int num_modes,
@@ -488,12 +440,8 @@ extern "C" int mpqe_kg_sample_rows_mixed(const void *table, const int64_t *mode_
                                          int32_t *err, void *stream) {
     if (num_queries < 0 || num_queries > KGS_MAX_SLOTS || q_base < 0 || rows_cap < 0 || k < 1) return MPQE_ERR_INVALID_ARG;
     if (select != MPQE_KG_ROWS_SET && select != MPQE_KG_ROWS_COMPLEMENT) return MPQE_ERR_INVALID_ARG;
-    if (!mode_rows_host || num_modes < 1 || num_modes > KGS_MAX_MODES) return MPQE_ERR_INVALID_ARG;
-    int64_t widest = 0;
-    for (int m = 0; m < num_modes; ++m) {
-        if (mode_rows_host[m] < 1) return MPQE_ERR_INVALID_ARG;
-        if (mode_rows_host[m] > widest) widest = mode_rows_host[m];
-    }
+    const int64_t widest = kgt_widest_mode(mode_rows_host, num_modes);
+    if (widest == 0) return MPQE_ERR_INVALID_ARG;
     if (k > KGS_MAX_K || widest > KGS_MAX_SAMPLE_ROWS) return MPQE_ERR_UNSUPPORTED;
     if (bits_stride < (widest + 31) / 32) return MPQE_ERR_INVALID_ARG;
     if (num_queries == 0) return MPQE_OK;

@@ -24,6 +24,18 @@ struct KgtRel {
     int reverse, pad;           // the index of reverse_relation(rel) in the same index, -1: absent
 };
 
+// The host's copy of the modes, checked as the mixed entry points take it: the widest mode's rows; 0 for no modes, more than
+// the table holds or a mode without a row. (How wide a mode may be is the caller's own limit.)
+static inline int64_t kgt_widest_mode(const int64_t *mode_rows, int num_modes) {
+    if (!mode_rows || num_modes < 1 || num_modes > KGT_MAX_MODES) return 0;
+    int64_t widest = 0;
+    for (int m = 0; m < num_modes; ++m) {
+        if (mode_rows[m] < 1) return 0;
+        if (mode_rows[m] > widest) widest = mode_rows[m];
+    }
+    return widest;
+}
+
 __device__ __forceinline__ const KgtHead *kgt_head(const char *table) { return reinterpret_cast<const KgtHead *>(table); }
 __device__ __forceinline__ const KgtRel *kgt_rels(const char *table) {
     return reinterpret_cast<const KgtRel *>(table + sizeof(KgtHead));

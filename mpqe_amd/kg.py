@@ -38,6 +38,25 @@ from .graph import Formula, Query, reverse_relation
 PROG_INTS = ops.GQE_PROG_INTS
 MAX_MODES = 16
 
+# The seven query types in query EDGES (x, rel, y), in the order of the reference's query tuple and of sample_queries' records:
+# (edges, the anchor edges -- their y is the anchor -- in anchor-slot order, the variable edges, whether Formula nests the
+# relations as (r0, (r1, r2))). Edge 0's x is the target.
+QUERY_SHAPES = {
+    '1-chain': (1, (0,), (), False),
+    '2-chain': (2, (1,), (0,), False),
+    '3-chain': (3, (2,), (0, 1), False),
+    '2-inter': (2, (0, 1), (), False),
+    '3-inter': (3, (0, 1, 2), (), False),
+    '3-inter_chain': (3, (0, 2), (1,), True),
+    '3-chain_inter': (3, (1, 2), (0,), True),
+}
+
+
+def _edge_relations(formula):
+    """the formula's relations, one per query edge in QUERY_SHAPES' edge order"""
+    rels = formula.rels
+    return [tuple(r) for r in ((rels[0],) + tuple(rels[1]) if QUERY_SHAPES[formula.query_type][3] else rels)]
+
 
 def query_hops(formula):
     """([(anchor slot, [relation of each hop])], [relations of the hops after the merge]): the walk from the anchors to the
@@ -371,19 +390,12 @@ class KGIndex(object):
         if formulas and len(set(f.query_type for f in formulas)) != 1:
             raise ValueError('KGIndex.records_of: queries of one query type')
         for i, (f, q) in enumerate(zip(formulas, queries)):
-            qt, rels = f.query_type, f.rels
-            flat = [tuple(r) for r in (rels if qt.endswith('-chain') or qt.endswith('-inter') else
-                                       (rels[0], rels[1][0], rels[1][1]))]
-            # (edge, anchor slot) of the leaf edges
-            leaves = {'1-chain': [(0, 0)], '2-chain': [(1, 0)], '3-chain': [(2, 0)], '2-inter': [(0, 0), (1, 1)],
-                      '3-inter': [(0, 0), (1, 1), (2, 2)], '3-inter_chain': [(0, 0), (2, 1)],
-                      '3-chain_inter': [(1, 0), (2, 1)]}[qt]
-            for e, r in enumerate(flat):
+            for e, r in enumerate(_edge_relations(f)):
                 if r not in self.rel_index:
                     raise KeyError('KGIndex: no adjacency for relation %r' % (r,))
                 out[i, 2 + 3 * e] = self.rel_index[r]
             anchors = q.anchor_nodes if hasattr(q, 'anchor_nodes') else q
-            for e, slot in leaves:
+            for slot, e in enumerate(QUERY_SHAPES[f.query_type][1]):
                 out[i, 3 + 3 * e] = self._rows_of(f.anchor_modes[slot], np.asarray([anchors[slot]], dtype=np.int64))[0]
             if hasattr(q, 'target_node'):
                 out[i, 1] = self._rows_of(f.target_mode, np.asarray([q.target_node], dtype=np.int64))[0]
@@ -411,8 +423,7 @@ class KGIndex(object):
         """The accepted slots of a host [Q, 10] array grouped by formula -> {Formula: (slots, target rows [B], anchor rows
         [B, A], variable rows [B, V])}; the same reading of the query tuple as graph.Query's."""
         slots = np.nonzero(records[:, 0] == 1)[0]
-        n_edges = {'1-chain': 1, '2-chain': 2, '3-chain': 3, '2-inter': 2, '3-inter': 3, '3-inter_chain': 3,
-                   '3-chain_inter': 3}[qt_name]
+        n_edges, anchor_edges, variable_edges, _ = QUERY_SHAPES[qt_name]
         e = records[slots, 1:1 + 3 * n_edges].reshape(-1, n_edges, 3)
         out = {}
         if slots.size == 0:
@@ -421,17 +432,9 @@ class KGIndex(object):
         inverse = inverse.reshape(-1)
         for g, rel_ids in enumerate(keys):
             pick = np.nonzero(inverse == g)[0]
-            rels = [self.rels[int(r)] for r in rel_ids]
             x, y = e[pick, :, 0], e[pick, :, 2]
-            if qt_name.endswith('-chain'):
-                formula, anchors, variables = Formula(qt_name, tuple(rels)), y[:, -1:], y[:, :-1]
-            elif qt_name.endswith('-inter'):
-                formula, anchors, variables = Formula(qt_name, tuple(rels)), y, y[:, :0]
-            elif qt_name == '3-inter_chain':
-                formula, anchors, variables = Formula(qt_name, (rels[0], (rels[1], rels[2]))), y[:, [0, 2]], y[:, 1:2]
-            else:
-                formula, anchors, variables = Formula(qt_name, (rels[0], (rels[1], rels[2]))), y[:, [1, 2]], y[:, 0:1]
-            out[formula] = (slots[pick], x[:, 0].copy(), np.ascontiguousarray(anchors), np.ascontiguousarray(variables))
+            out[self._formula_of(qt_name, rel_ids)] = (slots[pick], x[:, 0].copy(), np.ascontiguousarray(y[:, list(anchor_edges)]),
+                                                       np.ascontiguousarray(y[:, list(variable_edges)]))
         return out
 
     def sample_query_sets(self, query_types, per_type, seed, neg_sample_max=100, train_index=None, max_rounds=8,
@@ -503,9 +506,7 @@ class KGIndex(object):
 
     def _formula_of(self, qt_name, rel_ids):
         rels = [self.rels[int(r)] for r in rel_ids]
-        if qt_name.endswith('-chain') or qt_name.endswith('-inter'):
-            return Formula(qt_name, tuple(rels))
-        return Formula(qt_name, (rels[0], (rels[1], rels[2])))
+        return Formula(qt_name, (rels[0], (rels[1], rels[2])) if QUERY_SHAPES[qt_name][3] else tuple(rels))
 
     def _sample_query_sets_batched(self, query_types, per_type, seed, k, train_index, max_rounds, max_tries):
         dev = self.device
@@ -517,9 +518,6 @@ class KGIndex(object):
             remap_host = np.asarray([train_index.rel_index[r] if r in train_index.rel_index and
                                      reverse_relation(r) in train_index.rel_index else -1 for r in self.rels], dtype=np.int64)
             remap = torch.from_numpy(remap_host).to(dev)
-        n_edges_of = {'1-chain': 1, '2-chain': 2, '3-chain': 3, '2-inter': 2, '3-inter': 3, '3-inter_chain': 3,
-                      '3-chain_inter': 3}
-        columns = {'3-inter_chain': ([0, 2], [1]), '3-chain_inter': ([1, 2], [0])}        # (anchor edges, variable edges)
         sets = {}
         clock = [time.perf_counter()]
 
@@ -531,14 +529,9 @@ class KGIndex(object):
                 self.section_times[section] = self.section_times.get(section, 0.0) + now - clock[0]
                 clock[0] = now
         for qt_name in query_types:
-            n_e, inter = n_edges_of[qt_name], 'inter' in qt_name
+            n_e, anchor_edges, variable_edges, _ = QUERY_SHAPES[qt_name]
+            a_cols, v_cols, inter = list(anchor_edges), list(variable_edges), 'inter' in qt_name
             rel_cols = slice(2, 2 + 3 * n_e, 3)
-            if qt_name.endswith('-chain'):
-                a_cols, v_cols = [n_e - 1], list(range(n_e - 1))
-            elif qt_name.endswith('-inter'):
-                a_cols, v_cols = list(range(n_e)), []
-            else:
-                a_cols, v_cols = columns[qt_name]
             have, parts = 0, []
             type_seed = (int(seed) * 1000003 + 7919 * _capi.QUERY_TYPE_IDS[qt_name]) & (2 ** 63 - 1)
             for rnd in range(max_rounds):
@@ -961,15 +954,8 @@ class QuerySet(object):
                 offsets.append(off[1:] + base)
                 base += int(off[-1].item())
             return torch.cat([p[0] for p in pairs]), torch.cat(offsets)
-        qt, rels = formula.query_type, formula.rels
-        if qt.endswith('-chain'):
-            var_modes = [r[2] for r in rels[:-1]]
-        elif qt == '3-inter_chain':
-            var_modes = [rels[1][0][2]]
-        elif qt == '3-chain_inter':
-            var_modes = [rels[0][2]]
-        else:
-            var_modes = []
+        rels = _edge_relations(formula)
+        var_modes = [rels[e][2] for e in QUERY_SHAPES[formula.query_type][2]]        # a variable is its edge's y
         target = np.concatenate([c[0] for c in chunks])
         anchors = np.concatenate([c[1] for c in chunks])
         variables = np.concatenate([c[2] for c in chunks])

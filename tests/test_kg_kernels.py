@@ -342,6 +342,80 @@ def test_out_of_range_anchor(be):
     _answers(world, branches, tail, np.array([[64, 2, 3], [1, 2, 32]]), 42)          # the last rows: in range
 
 
+# ---------------------------------------------------------------------------------------------- a corrupt index
+CORRUPT_ROWS = [1, 33, 65]
+A0, B0, X = 10, 20, 64          # query 0's anchors (branch 0, branch 1) and the one row of mode 2 that only query 0 reaches
+
+
+def _corrupt_relations():
+    """Modes of 1, 33 and 65 rows. 0 and 3: mode 1 -> mode 2, the first hops; row X is in the lists of A0 (relation 0) and B0
+    (relation 3) only. 1, 2 and 4: mode 2 -> modes 1, 0 and 2, the hops a frontier scan walks; X's lists hold four entries."""
+    rng = np.random.RandomState(23)
+    first = lambda: {r: rng.randint(0, X, size=3).tolist() for r in range(33)}          # noqa: E731
+    scan = lambda n: {r: rng.randint(0, n, size=rng.randint(1, 5)).tolist() for r in range(65)}     # noqa: E731
+    rels = [(1, 2, first()), (2, 1, scan(33)), (2, 0, scan(1)), (1, 2, first()), (2, 2, scan(65))]
+    rels[0][2][A0] = [5, X, 9]
+    rels[3][2][B0] = [X, 3]
+    rels[1][2][X] = [32, 0, 7, 32]
+    rels[2][2][X] = [0, 0, 0, 0]
+    rels[4][2][X] = [X, 1, 0, 33]
+    return rels
+
+
+@pytest.mark.parametrize('qt', ['2-chain', '3-chain_inter'])
+@pytest.mark.parametrize('fault', ['offset', 'row to 1 row', 'row to 33 rows', 'row to 65 rows'])
+def test_corrupt_csr_is_flagged_and_the_rest_of_the_set_kept(be, fault, qt):
+    """The index lies in one place, which only query 0 of 4 meets. 'offset': offsets[A0 + 1] of the first hop's relation is
+    past `edges` -- the anchor's list is walked clamped to [offsets[A0], edges). 'row': entry 1 of row X's list in the
+    relation the frontier scan walks is the destination mode's row count (the first row outside it; its bit would lie inside
+    the mode's last word for 1 and 33 rows) -- the entry is skipped, the list's other three are followed. Either way
+    MPQE_FLAG_BAD_INDEX is set, query 0 gets what the oracle gets on the clamped / shortened list, and the other three
+    queries get the words of the clean index. Both homes of the bitmaps; guards checked by _call."""
+    rels = _corrupt_relations()
+    clean = World(be, CORRUPT_ROWS, rels)
+    bad = World(be, CORRUPT_ROWS, rels)
+    walked = [(s, d, dict(lists)) for s, d, lists in rels]             # what the kernel is to make of the corrupt index
+    if fault == 'offset':
+        scan = 1
+        edges = int(bad.edges[0])
+        flat = [x for r in range(33) for x in rels[0][2][r]]
+        lo = sum(len(rels[0][2][r]) for r in range(A0))
+        bad.keep[0][A0 + 1] = edges + 7
+        walked[0][2][A0] = flat[lo:edges]
+        walked[0][2][A0 + 1] = []                                       # (its lower end is past `edges`; nobody's anchor)
+        assert len(flat) == edges and set(rels[0][2][A0]) < set(walked[0][2][A0])
+    else:
+        scan = {'row to 1 row': 2, 'row to 33 rows': 1, 'row to 65 rows': 4}[fault]
+        n_dst = CORRUPT_ROWS[rels[scan][1]]
+        at = sum(len(rels[scan][2][r]) for r in range(X)) + 1
+        bad.keep[2 * scan + 1][at] = n_dst
+        walked[scan][2][X] = rels[scan][2][X][:1] + rels[scan][2][X][2:]
+    bad.relations = walked
+    branches, tail = ([(1, [0, scan])], []) if qt == '2-chain' else ([(1, [0]), (1, [3])], [scan])
+    anchors = np.array([[A0, 1, 2, 3], [B0, 4, 5, 6]][:len(branches)])
+    prog, target = clean.programme(branches, tail)
+    n_out = CORRUPT_ROWS[target]
+    want = bad.oracle(branches, tail, anchors)
+    assert want[1:] == clean.oracle(branches, tail, anchors)[1:]
+    if fault != 'offset':
+        assert set(walked[scan][2][X]) <= want[0][0] and n_dst not in want[0][0] | want[0][1]
+    want_a = np.stack([_bitmap(w[0], n_out) for w in want])
+    want_h = np.stack([_bitmap(w[1], n_out) for w in want])
+    want_c = np.array([[len(w[0]) for w in want], [len(w[1]) for w in want]], dtype=np.int64)
+    rng = np.random.RandomState(60)
+    for flags in (0, _capi.KG_GLOBAL_BITS):
+        what = 'bitmaps in %s' % ('the workspace' if flags else 'LDS')
+        got_a, got_h, got_c, err = _call(bad, prog, anchors, n_out, rng, flags)
+        ref_a, ref_h, ref_c, ref_err = _call(clean, prog, anchors, n_out, rng, flags)
+        assert err == BAD_INDEX and ref_err == 0, what
+        np.testing.assert_array_equal(got_a, want_a, err_msg='answers, ' + what)
+        np.testing.assert_array_equal(got_h, want_h, err_msg='hard, ' + what)
+        np.testing.assert_array_equal(got_c, want_c, err_msg='counts, ' + what)
+        np.testing.assert_array_equal(got_a[1:], ref_a[1:], err_msg='the other queries, ' + what)
+        np.testing.assert_array_equal(got_h[1:], ref_h[1:], err_msg='the other queries (hard), ' + what)
+        np.testing.assert_array_equal(got_c[:, 1:], ref_c[:, 1:], err_msg='the other queries (counts), ' + what)
+
+
 def test_same_call_twice_gives_the_same_bits(be):
     world = _seven_world(be)
     branches, tail = SEVEN['3-chain_inter']
