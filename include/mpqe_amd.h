@@ -789,6 +789,37 @@ int mpqe_gqe_embed(const int32_t *prog_host, const float *const *tables_host, co
                    const int64_t *p_ids /* [branches, p_rows], or NULL */, int64_t p_rows, float *out /* [p_rows, dim] */,
                    int32_t *err, void *stream);
 
+/* Queries of DIFFERENT formulas of one query type scored in one launch (added under ABI 7: entries only).
+ * mpqe_gqe_fwd_mixed is mpqe_gqe_fwd with save_states == 0 for num_queries queries, query q under programme
+ * formula_of[q] (int64 [num_queries] on the device) of num_formulas programmes. The programmes share what the query type
+ * fixes -- [0] form, [1] branches, [2] aggregate, [5] and every [9 + 5 b] (the products), [7] operator, [27] scoring, and
+ * whether [3] / [4] are present -- and differ in their tables, in the parameter and transposition of every site and in the
+ * pre / post matrix. prog_host of the scoring call is any ONE of them (only the shared ints are read).
+ * mpqe_gqe_mixed_desc_build checks every programme as mpqe_gqe_fwd does (progs_host [num_formulas, MPQE_GQE_PROG_INTS],
+ * tables_host / mats_host as there), refuses programmes that disagree on a shared int with MPQE_ERR_INVALID_ARG before
+ * anything is written, and writes one descriptor per formula -- table addresses and rows, the parameter address and
+ * transposition of every site -- to `desc` (device memory, 256-byte aligned, mpqe_gqe_mixed_desc_bytes(num_formulas): exact,
+ * a byte less is MPQE_ERR_WORKSPACE and nothing is written; 0: num_formulas out of range). The block depends on the
+ * programmes and the parameter ADDRESSES only: the caller keeps it between calls, and the host work of a scoring call
+ * does not grow with num_formulas. There is no other workspace.
+ * Layout of a call: as mpqe_gqe_fwd over the concatenation. Chain form: p_ids [1, n], e_ids [num_queries] the anchors,
+ * qrow [n]; intersection form: p_ids [branches, num_queries], e_ids [n], neg_off [num_queries + 1]. The P rows are cut
+ * into blocks of 16 and a block into its stretches of one formula; a workgroup owns one stretch (one launch, 16
+ * workgroups per block, the spare ones leave at once). scores [n]: every pair's score equals BIT FOR BIT what mpqe_gqe_fwd
+ * writes for it when the query's run is handed to it alone with its own programme. A formula index outside
+ * [0, num_formulas) -- chain form also a qrow outside [0, num_queries) -- ORs MPQE_FLAG_BAD_INDEX and the pairs of that
+ * query score 0; bad ids as in mpqe_gqe_fwd; the other queries' bits are unaffected and nothing is read or written out of
+ * bounds. num_queries == 0 (then n == p_rows == e_rows == 0): MPQE_OK, no launch. */
+size_t mpqe_gqe_mixed_desc_bytes(int64_t num_formulas);
+int mpqe_gqe_mixed_desc_build(const int32_t *progs_host, int64_t num_formulas, const float *const *tables_host,
+                              const int64_t *table_rows_host, int num_tables, const float *const *mats_host, int num_mats,
+                              int64_t dim, void *desc, size_t desc_bytes, void *stream);
+int mpqe_gqe_fwd_mixed(const int32_t *prog_host, int64_t num_formulas, const void *desc, size_t desc_bytes,
+                       const int64_t *node_map, int64_t node_map_len, int64_t dim, const int64_t *formula_of,
+                       int64_t num_queries, const int64_t *p_ids, int64_t p_rows, const int64_t *e_ids, int64_t e_rows,
+                       const int64_t *qrow, const int64_t *neg_off, int64_t n, float eps, float *scores, int32_t *err,
+                       void *stream);
+
 /* ---- exact answers of a conjunctive query on the knowledge graph (csrc/kg.hip) ------------------------------------
  * reference: Graph.get_metapath_neighs graph.py:459-473 (the answer set of a chain) and Graph.get_negative_samples
  * graph.py:263-314 (intersection / union of the branch sets; negatives = full set - answers, hard negatives = union -
@@ -1077,6 +1108,20 @@ int mpqe_eval_counts(const float *scores, const int64_t *neg_offsets, int64_t B,
 size_t mpqe_eval_auc_workspace_bytes(int64_t n_pos, int64_t n_neg);
 int mpqe_eval_auc(const float *pos, int64_t n_pos, const float *neg, int64_t n_neg, uint64_t *u2, void *workspace,
                   size_t workspace_bytes, void *stream);
+
+/* mpqe_eval_auc_segments: mpqe_eval_auc's statistic of S = num_segments slices in one call, without a host read (the
+ * per-formula AUCs of an evaluation; added under ABI 7: entries only). pos_off / neg_off [S + 1] int64 on the device, CSR:
+ * u2[s] is exactly what mpqe_eval_auc gives for pos[pos_off[s] .. pos_off[s + 1]) against neg[neg_off[s] .. neg_off[s + 1])
+ * -- the same reading of NaN, -0.0 and +-inf --, and 0 where either slice is empty (n_pos == 0 or n_neg == 0 included).
+ * The negatives' keys carry their segment above the 32-bit score key and are sorted once; a positive searches inside its
+ * own segment's bounds, so equal scores of neighbouring segments are never counted. A segment whose offsets are out of
+ * order or outside the arrays stays 0; nothing is read or written out of bounds. n_pos, n_neg, S < 2^31. u2 [S]: 8-byte
+ * aligned; workspace: 8-byte aligned, mpqe_eval_auc_segments_workspace_bytes (exact: a byte less is MPQE_ERR_WORKSPACE and
+ * nothing is written; 0: arguments out of range). */
+size_t mpqe_eval_auc_segments_workspace_bytes(int64_t n_pos, int64_t n_neg, int64_t num_segments);
+int mpqe_eval_auc_segments(const float *pos, int64_t n_pos, const float *neg, int64_t n_neg, const int64_t *pos_off,
+                           const int64_t *neg_off, int64_t num_segments, uint64_t *u2 /*[num_segments]*/, void *workspace,
+                           size_t workspace_bytes, void *stream);
 
 /* Diagnostics, not part of the data path: while `device_buffer` (8 int64 per workgroup, num_blocks
  * workgroups) is set, every chain-kernel launch with at most num_blocks workgroups writes per workgroup the

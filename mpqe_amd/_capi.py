@@ -111,6 +111,10 @@ PROTOTYPES = {
     'mpqe_gqe_fwd': (I, [P, P, P, I, P, L, P, I, L, P, L, P, L, P, P, L, F, I, P, P, Z, P, P]),
     'mpqe_gqe_bwd': (I, [P, P, P, I, P, L, P, I, L, P, L, P, L, P, P, L, F, P, P, P, P, Z, P, P]),
     'mpqe_gqe_embed': (I, [P, P, P, I, P, L, P, I, L, P, L, P, P, P]),
+    # queries of different formulas of one query type in one launch (added under ABI 7: entries only)
+    'mpqe_gqe_mixed_desc_bytes': (Z, [L]),
+    'mpqe_gqe_mixed_desc_build': (I, [P, L, P, P, I, P, I, L, P, Z, P]),
+    'mpqe_gqe_fwd_mixed': (I, [P, L, P, Z, P, L, L, P, L, P, L, P, L, P, P, L, F, P, P, P]),
     'mpqe_kg_workspace_bytes': (Z, [P, L, P, I, I]),
     'mpqe_kg_answers': (I, [P, P, P, P, I, P, I, P, L, P, P, P, I, P, Z, P, P]),
     'mpqe_kg_rows': (I, [P, L, L, P, I, P, P, L, P, P]),
@@ -130,6 +134,8 @@ PROTOTYPES = {
     'mpqe_eval_counts': (I, [P, P, L, L, P, P, P]),
     'mpqe_eval_auc_workspace_bytes': (Z, [L, L]),
     'mpqe_eval_auc': (I, [P, L, P, L, P, P, Z, P]),
+    'mpqe_eval_auc_segments_workspace_bytes': (Z, [L, L, L]),
+    'mpqe_eval_auc_segments': (I, [P, L, P, L, P, P, L, P, P, Z, P]),
     'mpqe_branch_agg_fwd': (I, [P, P, P, L, I, P, P]),
     'mpqe_branch_agg_bwd': (I, [P, P, P, L, I, P, P, P, P, P]),
     'mpqe_debug_chain_stamps': (None, [P, Z]),

@@ -191,3 +191,97 @@ extern "C" int mpqe_eval_auc(const float *pos, int64_t n_pos, const float *neg, 
                        (const unsigned *)sorted, (long long)n_neg, reinterpret_cast<unsigned long long *>(u2));
     return mpqe_launch_status();
 }
+
+// ------------------------------------------------------------------------------------------- ROC-AUC of S segments at once
+// mpqe_eval_auc_segments: u2[s] = mpqe_eval_auc's statistic of (pos[pos_off[s] .. pos_off[s + 1]), neg[neg_off[s] ..
+// neg_off[s + 1])) for every s, in one call with no host read. A negative becomes the 64-bit key (segment << 32 | ev_key);
+// one sort of those keys (radix_sort.h is templated on the key) leaves every segment where it was, its keys in order, so a
+// positive searches its own segment's bounds only: an equal score on the other side of a boundary has another key and is
+// outside them. The terms are added to u2[s] with 64-bit integer atomics; an empty side gives 0. A segment whose offsets
+// are out of order or outside the arrays is left at 0.
+
+// the segment of item i: the last s in [0, S) with off[s] <= i (empty segments have no items)
+__device__ __forceinline__ long long ev_segment_of(const long long *__restrict__ off, long long S, long long i) {
+    long long a = 0, b = S;
+    while (b - a > 1) {
+        const long long mid = (a + b) >> 1;
+        if (off[mid] <= i) a = mid; else b = mid;
+    }
+    return a;
+}
+
+__global__ __launch_bounds__(EV_THREADS) void eval_seg_keys_kernel(const float *__restrict__ neg, long long n,
+                                                                   const long long *__restrict__ neg_off, long long S,
+                                                                   unsigned long long *__restrict__ keys) {
+    const long long i = (long long)blockIdx.x * EV_THREADS + threadIdx.x;
+    if (i < n) keys[i] = ((unsigned long long)ev_segment_of(neg_off, S, i) << 32) | ev_key(neg[i]);
+}
+
+__global__ __launch_bounds__(EV_THREADS) void eval_seg_search_kernel(const float *__restrict__ pos, long long n_pos,
+                                                                     const long long *__restrict__ pos_off,
+                                                                     const unsigned long long *__restrict__ keys,
+                                                                     long long n_neg, const long long *__restrict__ neg_off,
+                                                                     long long S, unsigned long long *__restrict__ out) {
+    const long long i = (long long)blockIdx.x * EV_THREADS + threadIdx.x;
+    if (i >= n_pos) return;
+    const long long s = ev_segment_of(pos_off, S, i);
+    long long plo, phi, lo, hi;
+    if (!ev_segment(pos_off, s, n_pos, &plo, &phi) || i < plo || i >= phi) return;
+    if (!ev_segment(neg_off, s, n_neg, &lo, &hi)) return;
+    const unsigned long long k = ((unsigned long long)s << 32) | ev_key(pos[i]);
+    long long a = lo, b = hi;                       // the first index of the segment whose key is >= k
+    while (a < b) {
+        const long long mid = (a + b) >> 1;
+        if (keys[mid] < k) a = mid + 1; else b = mid;
+    }
+    const long long below = a;
+    b = hi;                                         // the first whose key is > k
+    while (a < b) {
+        const long long mid = (a + b) >> 1;
+        if (keys[mid] <= k) a = mid + 1; else b = mid;
+    }
+    const unsigned long long term = (unsigned long long)((below - lo) + (a - lo));
+    if (term) atomicAdd(out + s, term);
+}
+
+// workspace: keys [n_neg] u64 | sorted keys [n_neg] u64 | the sort's item numbers [n_neg] (unused) | the sort's scratch
+static inline size_t ev_seg_keys_bytes(int64_t n_neg) { return align_up((size_t)(n_neg > 0 ? n_neg : 1) * 8, 256); }
+
+extern "C" size_t mpqe_eval_auc_segments_workspace_bytes(int64_t n_pos, int64_t n_neg, int64_t num_segments) {
+    if (n_pos < 0 || n_neg < 0 || num_segments < 1) return 0;
+    if (n_pos >= ((int64_t)1 << 31) || n_neg >= ((int64_t)1 << 31) || num_segments >= ((int64_t)1 << 31)) return 0;
+    return 2 * ev_seg_keys_bytes(n_neg) + ev_keys_bytes(n_neg > 0 ? n_neg : 1) +
+           radix_sort_tmp_bytes<unsigned long long>((long long)n_neg);
+}
+
+extern "C" int mpqe_eval_auc_segments(const float *pos, int64_t n_pos, const float *neg, int64_t n_neg,
+                                      const int64_t *pos_off, const int64_t *neg_off, int64_t num_segments, uint64_t *u2,
+                                      void *workspace, size_t workspace_bytes, void *stream) {
+    if (n_pos < 0 || n_neg < 0 || num_segments < 1 || !pos_off || !neg_off || !u2) return MPQE_ERR_INVALID_ARG;
+    if ((n_pos > 0 && !pos) || (n_neg > 0 && !neg)) return MPQE_ERR_INVALID_ARG;
+    if (n_pos >= ((int64_t)1 << 31) || n_neg >= ((int64_t)1 << 31) || num_segments >= ((int64_t)1 << 31))
+        return MPQE_ERR_UNSUPPORTED;
+    if (!workspace || ((uintptr_t)workspace & 7) || ((uintptr_t)u2 & 7)) return MPQE_ERR_INVALID_ARG;
+    if (workspace_bytes < mpqe_eval_auc_segments_workspace_bytes(n_pos, n_neg, num_segments)) return MPQE_ERR_WORKSPACE;
+    hipStream_t s = as_stream(stream);
+    if (hipMemsetAsync(u2, 0, (size_t)num_segments * sizeof(uint64_t), s) != hipSuccess) return MPQE_ERR_LAUNCH;
+    if (n_pos == 0 || n_neg == 0) return MPQE_OK;
+    char *wb = reinterpret_cast<char *>(workspace);
+    const size_t kb = ev_seg_keys_bytes(n_neg);
+    unsigned long long *keys = reinterpret_cast<unsigned long long *>(wb);
+    unsigned long long *sorted = reinterpret_cast<unsigned long long *>(wb + kb);
+    int *perm = reinterpret_cast<int *>(wb + 2 * kb);
+    const long long *noff = reinterpret_cast<const long long *>(neg_off);
+    hipLaunchKernelGGL(eval_seg_keys_kernel, dim3((unsigned)((n_neg + EV_THREADS - 1) / EV_THREADS)), dim3(EV_THREADS), 0, s,
+                       neg, (long long)n_neg, noff, (long long)num_segments, keys);
+    int seg_bits = 0;
+    while (((int64_t)1 << seg_bits) < num_segments) ++seg_bits;
+    const int st = radix_sort_pairs_own<unsigned long long>(wb + 2 * kb + ev_keys_bytes(n_neg), (const unsigned long long *)keys,
+                                                            sorted, nullptr, perm, (long long)n_neg, 32 + seg_bits, s);
+    if (st != MPQE_OK) return st;
+    hipLaunchKernelGGL(eval_seg_search_kernel, dim3((unsigned)((n_pos + EV_THREADS - 1) / EV_THREADS)), dim3(EV_THREADS), 0, s,
+                       pos, (long long)n_pos, reinterpret_cast<const long long *>(pos_off),
+                       (const unsigned long long *)sorted, (long long)n_neg, noff, (long long)num_segments,
+                       reinterpret_cast<unsigned long long *>(u2));
+    return mpqe_launch_status();
+}

@@ -41,6 +41,8 @@
 // them --, so leaving them out of the sum is a rule, not a correction.)
 #include <string.h>
 
+#include <new>
+
 #include "gemm_core.h"
 
 #define GQ_ROWS 16
@@ -830,6 +832,272 @@ extern "C" int mpqe_gqe_embed(const int32_t *prog_host, const float *const *tabl
     if ((uintptr_t)out % 16 != 0) return MPQE_ERR_INVALID_ARG;
     if (!p_ids && (H.G.nb != 1 || p_rows > H.G.tab_rows[0])) return MPQE_ERR_INVALID_ARG;
     hipLaunchKernelGGL((gqe_fwd_kernel<1, 0>), dim3((unsigned)(H.G.Rp16 / GQ_ROWS)), dim3(256), 0, as_stream(stream), H.G, out);
+    return mpqe_launch_status();
+}
+
+// ------------------------------------------------------------------------------- queries of different formulas at once
+// mpqe_gqe_fwd_mixed: the forward without states for B queries of ONE query type, query q under programme formula_of[q]
+// of F. The programmes share what the query type fixes (form, branches, products per branch and after the merge, operator,
+// scoring, aggregate, pre / post presence); a formula's own part -- its tables, the parameter and transposition of every
+// site -- is one GqeMixDesc in device memory (mpqe_gqe_mixed_desc_build; it depends on the programmes and the parameter
+// addresses only, so the caller keeps the block between calls).
+// Tiles without a tile table: the P rows (intersection form: the B queries; chain form: the n pair rows, row r belonging
+// to query qrow[r]) are cut into blocks of 16, and a block into its maximal stretches of rows with one formula; workgroup
+// 16 k + j owns the j-th stretch of block k and leaves at once when the block has fewer. Every workgroup reads the block's
+// (at most 16) formula indices with uniform loads, so there is no pre-pass, no workspace and one launch. A stretch is a
+// tile of gqe_fwd_kernel with fewer rows: the shared helpers run on a GqeDev put together from the shared record and the
+// stretch's descriptor, every output element's sum over k has gq_mm's fixed order whichever tile row it sits in, and the
+// scores are mpqe_gqe_fwd's to the bit. A formula index outside [0, F) (chain form also: a qrow outside [0, B)) flags
+// MPQE_FLAG_BAD_INDEX and its rows score 0.
+struct GqeMixDesc {
+    const float *tab[4];
+    long long tab_rows[4];
+    const float *w[GQ_SITES];
+    int T[GQ_SITES];
+};
+
+// the formula of P row r, -1 for an index out of range
+__device__ __forceinline__ long long gq_mix_formula(const GqeDev &G, const long long *__restrict__ fo, long long B, int F,
+                                                    long long r) {
+    long long q = r;
+    if (G.form == 0) {
+        q = G.qrow[r];
+        if (q < 0 || q >= B) return -1;
+    }
+    const long long f = fo[q];
+    return f < 0 || f >= F ? -1 : f;
+}
+
+template <int DOT>
+__global__ __launch_bounds__(256) void gqe_fwd_mixed_kernel(GqeDev G, const GqeMixDesc *__restrict__ desc,
+                                                            const long long *__restrict__ fo, long long B, int F,
+                                                            float *__restrict__ scores) {
+    __shared__ __attribute__((aligned(16))) float lds[3 * GQ_ROWS * GQ_LDXMAX];
+    const int D = G.D, LDX = D + 4, per = D / 4;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long base = (long long)(blockIdx.x >> 4) * GQ_ROWS;
+    const int want = blockIdx.x & 15;
+    // the want-th stretch [first, end) of this block (uniform: block index and scalar loads only)
+    int cnt = -1, fi = -1;
+    long long first = base, end = base, prev = -2;
+    for (int i = 0; i < GQ_ROWS; ++i) {
+        const long long r = base + i;
+        if (r >= G.Rp) break;
+        const long long k = gq_mix_formula(G, fo, B, F, r);
+        if (k != prev) {
+            if (cnt == want) break;
+            ++cnt;
+            first = r;
+            fi = (int)k;
+            prev = k;
+        }
+        end = r + 1;
+    }
+    if (cnt != want) return;
+    fi = __builtin_amdgcn_readfirstlane(fi);
+    if (fi < 0) {
+        if (threadIdx.x == 0) flag_error(G.err, MPQE_FLAG_BAD_INDEX);
+        for (int i = wave; i < GQ_ROWS; i += 4) {
+            const long long q = first + i;
+            if (q >= end) continue;
+            if (lane == 0) scores[q] = 0.f;
+            if (G.form == 0) continue;
+            long long lo, hi;
+            gq_neg_range(G, q, lane, lo, hi);
+            for (long long r = lo + lane; r < hi; r += 64) scores[r] = 0.f;
+        }
+        return;
+    }
+    const GqeMixDesc &M = desc[fi];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        G.tab[t] = M.tab[t];
+        G.tab_rows[t] = M.tab_rows[t];
+    }
+    float *cur = lds, *nxt = lds + GQ_ROWS * LDX, *agg = lds + 2 * GQ_ROWS * LDX;
+
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+        if (b >= G.nb) break;
+        gq_gather(G, cur, LDX, G.p_ids + (long long)b * G.Rp, b, first, end);
+        __syncthreads();
+        for (int s = 0; s < G.bn[b]; ++s) {
+            const int site = 3 * b + s;
+            if (G.op) {
+                gq_vec(cur, LDX, M.w[site], D, G.op, nullptr, first);
+                __syncthreads();
+                continue;
+            }
+            gq_mm(cur, nxt, M.w[site], D, LDX, M.T[site], 0);
+            __syncthreads();
+            float *t = cur; cur = nxt; nxt = t;
+        }
+        if (G.nb < 2) break;
+        if (G.has_pre) {
+            gq_mm(cur, nxt, M.w[GQ_SITE_PRE + b], D, LDX, 1, 1);
+            __syncthreads();
+            float *t = cur; cur = nxt; nxt = t;
+        }
+        for (int e = threadIdx.x; e < GQ_ROWS * per; e += 256) {
+            const int o = (e / per) * LDX + (e % per) * 4;
+            f32x4 v = *reinterpret_cast<const f32x4 *>(cur + o);
+            if (b > 0) {
+                const f32x4 a = *reinterpret_cast<const f32x4 *>(agg + o);
+#pragma unroll
+                for (int u = 0; u < 4; ++u) v[u] = G.agg ? (v[u] < a[u] ? v[u] : a[u]) : a[u] + v[u];
+            }
+            if (!G.agg && b == G.nb - 1) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) v[u] /= (float)G.nb;
+            }
+            *reinterpret_cast<f32x4 *>(agg + o) = v;
+        }
+        __syncthreads();
+    }
+    if (G.nb >= 2) {
+        float *t = cur; cur = agg; agg = t;
+        if (G.has_post) {
+            gq_mm(cur, nxt, M.w[GQ_SITE_POST], D, LDX, 1, 0);
+            __syncthreads();
+            t = cur; cur = nxt; nxt = t;
+        }
+    }
+    for (int s = 0; s < G.ntail; ++s) {
+        const int site = GQ_SITE_TAIL + s;
+        if (G.op) {
+            gq_vec(cur, LDX, M.w[site], D, G.op, nullptr, first);
+            __syncthreads();
+            continue;
+        }
+        gq_mm(cur, nxt, M.w[site], D, LDX, M.T[site], 0);
+        __syncthreads();
+        float *t = cur; cur = nxt; nxt = t;
+    }
+
+    for (int i = wave; i < GQ_ROWS; i += 4) {
+        const long long q = first + i;
+        if (q >= end) continue;
+        f32x4 p = {0.f, 0.f, 0.f, 0.f};
+        if (lane * 4 < D) p = *reinterpret_cast<const f32x4 *>(cur + i * LDX + lane * 4);
+        if (G.form == 0) {
+            const float s = gq_score<DOT>(G, p, gq_e_row(G, q, lane), nullptr, nullptr, nullptr);
+            if (lane == 0) scores[q] = s;
+        } else {
+            long long lo, hi;
+            gq_neg_range(G, q, lane, lo, hi);
+            for (long long r = q;;) {
+                const float s = gq_score<DOT>(G, p, gq_e_row(G, r, lane), nullptr, nullptr, nullptr);
+                if (lane == 0) scores[r] = s;
+                r = r == q ? lo : r + 1;
+                if (r >= hi) break;
+            }
+        }
+    }
+}
+
+static inline size_t gqe_mixed_desc_size(int64_t F) { return align_up((size_t)F * sizeof(GqeMixDesc), 256); }
+
+extern "C" size_t mpqe_gqe_mixed_desc_bytes(int64_t num_formulas) {
+    if (num_formulas < 1 || num_formulas >= ((int64_t)1 << 24)) return 0;
+    return gqe_mixed_desc_size(num_formulas);
+}
+
+// the ints of a programme that the query type fixes: everything but the tables, the codes and the pre / post indices
+static bool gqe_mixed_same_shape(const int32_t *a, const int32_t *b) {
+    if (a[0] != b[0] || a[1] != b[1] || a[2] != b[2] || a[5] != b[5] || a[7] != b[7]) return false;
+    if ((a[27] == 1) != (b[27] == 1) || (a[3] >= 0) != (b[3] >= 0) || (a[4] >= 0) != (b[4] >= 0)) return false;
+    for (int k = 0; k < a[1] && k < 3; ++k)
+        if (a[9 + 5 * k] != b[9 + 5 * k]) return false;
+    return true;
+}
+
+extern "C" int mpqe_gqe_mixed_desc_build(const int32_t *progs_host, int64_t num_formulas, const float *const *tables_host,
+                                         const int64_t *table_rows_host, int num_tables, const float *const *mats_host,
+                                         int num_mats, int64_t dim, void *desc, size_t desc_bytes, void *stream) {
+    if (!progs_host || num_tables < 1 || num_mats < 0 || !desc) return MPQE_ERR_INVALID_ARG;
+    if (num_formulas < 1 || num_formulas >= ((int64_t)1 << 24)) return MPQE_ERR_INVALID_ARG;
+    if ((uintptr_t)desc % 256 != 0) return MPQE_ERR_INVALID_ARG;
+    GqeMixDesc *image = new (std::nothrow) GqeMixDesc[(size_t)num_formulas];
+    if (!image) return MPQE_ERR_INVALID_ARG;
+    memset(image, 0, (size_t)num_formulas * sizeof(GqeMixDesc));
+    int st = MPQE_OK;
+    for (int64_t f = 0; f < num_formulas && st == MPQE_OK; ++f) {
+        const int32_t *prog = progs_host + f * MPQE_GQE_PROG_INTS;
+        GqeHost H;
+        // (the sizes of a call are not known here: one row stands for them; the form decides which of them must agree)
+        st = gqe_plan(prog, num_tables, num_mats, dim, 1, 1, 1, &H);
+        if (st != MPQE_OK) break;
+        if (!gqe_mixed_same_shape(progs_host, prog)) {
+            st = MPQE_ERR_INVALID_ARG;
+            break;
+        }
+        st = gqe_bind(&H, tables_host, table_rows_host, nullptr, 0, mats_host, nullptr, nullptr, nullptr, nullptr, 0.f, nullptr,
+                      nullptr, true);
+        if (st != MPQE_OK) break;
+        // (p_only leaves the E side's table out)
+        H.G.tab[3] = tables_host[H.G.tmode[3]];
+        H.G.tab_rows[3] = table_rows_host[H.G.tmode[3]];
+        if (!H.G.tab[3] || H.G.tab_rows[3] < 0 || (uintptr_t)H.G.tab[3] % 16 != 0) {
+            st = MPQE_ERR_INVALID_ARG;
+            break;
+        }
+        GqeMixDesc &M = image[f];
+        for (int t = 0; t < 4; ++t) {
+            M.tab[t] = H.G.tab[t];
+            M.tab_rows[t] = H.G.tab_rows[t];
+        }
+        for (int s = 0; s < GQ_SITES; ++s) {
+            M.w[s] = H.G.w[s];
+            M.T[s] = H.site_mat[s] < 0 ? 0 : H.site_T[s];
+        }
+    }
+    if (st == MPQE_OK && desc_bytes < gqe_mixed_desc_size(num_formulas)) st = MPQE_ERR_WORKSPACE;
+    if (st == MPQE_OK &&
+        hipMemcpyAsync(desc, image, (size_t)num_formulas * sizeof(GqeMixDesc), hipMemcpyHostToDevice, as_stream(stream)) !=
+            hipSuccess)
+        st = MPQE_ERR_LAUNCH;
+    // (the copy reads pageable memory: it has left `image` when the call returns)
+    delete[] image;
+    return st;
+}
+
+extern "C" int mpqe_gqe_fwd_mixed(const int32_t *prog_host, int64_t num_formulas, const void *desc, size_t desc_bytes,
+                                  const int64_t *node_map, int64_t node_map_len, int64_t dim, const int64_t *formula_of,
+                                  int64_t num_queries, const int64_t *p_ids, int64_t p_rows, const int64_t *e_ids,
+                                  int64_t e_rows, const int64_t *qrow, const int64_t *neg_off, int64_t n, float eps,
+                                  float *scores, int32_t *err, void *stream) {
+    if (!prog_host || num_queries < 0 || node_map_len < 0) return MPQE_ERR_INVALID_ARG;
+    if (num_formulas < 1 || num_formulas >= ((int64_t)1 << 24)) return MPQE_ERR_INVALID_ARG;
+    if (!desc || (uintptr_t)desc % 256 != 0) return MPQE_ERR_INVALID_ARG;
+    if (desc_bytes < gqe_mixed_desc_size(num_formulas)) return MPQE_ERR_WORKSPACE;
+    if (num_queries == 0) return n == 0 && p_rows == 0 && e_rows == 0 ? MPQE_OK : MPQE_ERR_INVALID_ARG;
+    if (!scores || !formula_of || !p_ids || !e_ids) return MPQE_ERR_INVALID_ARG;
+    GqeHost H;
+    const int st = gqe_plan(prog_host, -1, -1, dim, p_rows, e_rows, n, &H);
+    if (st != MPQE_OK) return st;
+    GqeDev &G = H.G;
+    // chain form: one anchor per query; intersection form: one P row per query
+    if (G.form == 0 ? e_rows != num_queries : p_rows != num_queries) return MPQE_ERR_INVALID_ARG;
+    if (G.form == 0 && !qrow) return MPQE_ERR_INVALID_ARG;
+    if (G.form == 1 && G.n > G.Rp && !neg_off) return MPQE_ERR_INVALID_ARG;
+    if (G.Rp16 / GQ_ROWS >= (1ll << 27)) return MPQE_ERR_UNSUPPORTED;
+    G.node_map = (const long long *)node_map;
+    G.map_len = node_map_len;
+    G.p_ids = (const long long *)p_ids;
+    G.e_ids = (const long long *)e_ids;
+    G.qrow = (const long long *)qrow;
+    G.neg_off = (const long long *)neg_off;
+    G.eps = eps;
+    G.err = err;
+    const dim3 grid((unsigned)(G.Rp16 / GQ_ROWS * 16));
+    const GqeMixDesc *M = reinterpret_cast<const GqeMixDesc *>(desc);
+    const long long *fo = reinterpret_cast<const long long *>(formula_of);
+    if (G.dot)
+        hipLaunchKernelGGL(gqe_fwd_mixed_kernel<1>, grid, dim3(256), 0, as_stream(stream), G, M, fo, (long long)num_queries,
+                           (int)num_formulas, scores);
+    else
+        hipLaunchKernelGGL(gqe_fwd_mixed_kernel<0>, grid, dim3(256), 0, as_stream(stream), G, M, fo, (long long)num_queries,
+                           (int)num_formulas, scores);
     return mpqe_launch_status();
 }
 

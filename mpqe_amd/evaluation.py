@@ -58,12 +58,16 @@ def _batches(formula_queries, batch_size):
 
 
 def _on_device(test_queries):
-    """whether the formulas' values are kg.QuerySets (the device route) rather than lists of Query"""
-    from .kg import QuerySet
-    kinds = {isinstance(v, QuerySet) for v in test_queries.values()}
-    if kinds == {True, False}:
-        raise TypeError('evaluation: every formula\'s queries as a kg.QuerySet, or every one as a list of Query')
-    return kinds == {True}
+    """How the dict's values hold the queries: 'sets' -- kg.QuerySets by formula --, 'mixed' -- kg.MixedQuerySets by query
+    type (both the device route) -- or False for lists of Query. One kind per dict."""
+    from .kg import MixedQuerySet, QuerySet
+    kinds = {'mixed' if isinstance(v, MixedQuerySet) else 'sets' if isinstance(v, QuerySet) else 'lists'
+             for v in test_queries.values()}
+    if len(kinds) > 1:
+        raise TypeError('evaluation: every formula\'s queries as a kg.QuerySet, every query type\'s as a kg.MixedQuerySet, '
+                        'or every formula\'s as a list of Query')
+    kind = kinds.pop() if kinds else 'lists'
+    return False if kind == 'lists' else kind
 
 
 def auc_batch_seed(seed, formula_position, batch_position):
@@ -141,6 +145,100 @@ def _eval_perc_sets(test_sets, enc_dec, batch_size, hard_negatives, lib):
     return np.float64(mean.item())
 
 
+def auc_window_seed(seed, type_position, window_position):
+    """The seed of the negatives' draw for one window of eval_auc_queries over MixedQuerySets: seed * 2^40 + type position
+    * 2^20 + window position (mod 2^64) -- the query type's position in the dict's iteration order, the window's among the
+    type's windows [lo, lo + batch_size) over its concatenation. Distinct for distinct (type, window), both below 2^20.
+    auc_batch_seed's form with the type in the formula's place: the windows differ from the QuerySet route's, and so do
+    the draws."""
+    if not (0 <= type_position < 2 ** 20 and 0 <= window_position < 2 ** 20):
+        raise ValueError('eval_auc_queries: at most 2^20 query types and 2^20 windows a type')
+    return (int(seed) * 2 ** 40 + type_position * 2 ** 20 + window_position) & (2 ** 64 - 1)
+
+
+def _score_window(enc_dec, ms, lo, hi, neg, offsets_host):
+    """the scores of queries [lo, hi) of a MixedQuerySet in forward()'s layout: one score_ids_mixed call over the type's
+    formulas where the model has it, the window's runs of equal formula through score_ids otherwise"""
+    if hasattr(enc_dec, 'score_ids_mixed'):
+        return enc_dec.score_ids_mixed(ms.formulas, ms.formula_of[lo:hi], ms.anchors[lo:hi], ms.targets[lo:hi], neg=neg)
+    from .model import score_ids_by_runs
+    return score_ids_by_runs(enc_dec, ms.formulas, ms.formula_of_host[lo:hi], ms.anchors[lo:hi], ms.targets[lo:hi], neg,
+                             offsets_host)
+
+
+def _eval_auc_mixed(test_sets, enc_dec, batch_size, hard_negatives, seed, lib):
+    """eval_auc_queries over {query type: kg.MixedQuerySet}. Per type ONE sampler over the concatenated lists; per window
+    one draw (auc_window_seed) and one scoring call; per call one ops.eval_auc_segments over every formula of every type
+    (one copy of [S] integers gives the {formula: AUC} dict) and one ops.eval_auc for the overall figure."""
+    import torch
+
+    from . import ops
+    from .sampling import NegativeSampler
+    all_pos, all_neg, errs, formulas, bounds, base = [], [], {}, [], [np.zeros(1, dtype=np.int64)], 0
+    for t, (qt, ms) in enumerate(test_sets.items()):
+        Q, dev = len(ms), ms.index.device
+        if hard_negatives and ms.hard is None:
+            raise Exception("Hard negative examples can only be used with "
+                            "intersection queries")                   # reference model.py:467-469
+        sampler = NegativeSampler.from_csr(ms.neg, ms.hard, dev, lib=lib)
+        sampler.err = errs.setdefault(dev, sampler.err)         # one error word for all types: read once, below
+        pos = torch.empty(Q, dtype=torch.float32, device=dev)
+        neg = torch.empty(Q, dtype=torch.float32, device=dev)
+        unit = np.arange(min(batch_size, Q) + 1, dtype=np.int64)
+        for w, (lo, hi) in enumerate(_batches(ms.targets, batch_size)):
+            window = torch.arange(lo, hi, dtype=torch.long, device=dev)
+            negatives = sampler.sample(window, auc_window_seed(seed, t, w), hard_negatives)
+            offsets = torch.arange(hi - lo + 1, dtype=torch.long, device=dev)
+            scores = _score_window(enc_dec, ms, lo, hi, (negatives, offsets), unit[:hi - lo + 1])
+            pos[lo:hi] = scores[:hi - lo].to(dev)
+            neg[lo:hi] = scores[hi - lo:].to(dev)
+        all_pos.append(pos)
+        all_neg.append(neg)
+        formulas += list(ms.formulas)
+        bounds.append(ms.bounds[1:] + base)
+        base += Q
+    for err in errs.values():
+        ops.raise_on_flags(err)         # (an empty list: IndexError, the reference's random.choice([]))
+    pos, neg = torch.cat(all_pos), torch.cat(all_neg)
+    bounds = np.concatenate(bounds)
+    sizes = np.diff(bounds)
+    if (sizes == 0).any():
+        raise ValueError('Only one class present in y_true. ROC AUC score is not defined in that case.')
+    off = torch.from_numpy(bounds).to(pos.device)
+    u2 = ops.eval_auc_segments(pos, neg, off, off, lib=lib).cpu().tolist()
+    formula_aucs = {f: ops.auc_from_statistic(u & (2 ** 64 - 1), int(n), int(n)) for f, u, n in zip(formulas, u2, sizes)}
+    return ops.auc_from_statistic(ops.eval_auc(pos, neg, lib=lib), pos.shape[0], neg.shape[0]), formula_aucs
+
+
+def _eval_perc_mixed(test_sets, enc_dec, batch_size, hard_negatives, lib):
+    """eval_perc_queries over {query type: kg.MixedQuerySet}: _eval_perc_sets' windows over a type's concatenation"""
+    import torch
+
+    from . import ops
+    percentiles, errs = [], {}
+    for qt, ms in test_sets.items():
+        dev = ms.index.device
+        if hard_negatives and ms.hard is None:
+            raise Exception("Hard negative examples can only be used with "
+                            "intersection queries")
+        pair, host = (ms.hard, ms.offsets_host(True)) if hard_negatives else (ms.neg, ms.offsets_host(False))
+        if dev not in errs:
+            errs[dev] = ops.new_error_word(dev)         # one error word for all windows: read once, below
+        err = errs[dev]
+        for lo, hi in _batches(ms.targets, batch_size):
+            a, b = int(host[lo]), int(host[hi])
+            offsets = pair[1][lo:hi + 1] - a
+            scores = _score_window(enc_dec, ms, lo, hi, (pair[0][a:b], offsets), host[lo:hi + 1] - a)
+            counts = ops.eval_counts(scores.to(dev), offsets, hi - lo, lib=lib, err=err)
+            percentiles.append(ops.eval_percentiles(counts, offsets))
+    if not percentiles:
+        return np.mean([])
+    mean = torch.cat(percentiles).mean()
+    for err in errs.values():
+        ops.raise_on_flags(err)
+    return np.float64(mean.item())
+
+
 def eval_auc_queries(test_queries, enc_dec, batch_size=128, hard_negatives=False, seed=0, lib=None):
     """-> (overall AUC, {formula: AUC}). One negative per query, drawn with random.choice after
     random.seed(seed) (reference utils.py:34-69).
@@ -150,8 +248,17 @@ def eval_auc_queries(test_queries, enc_dec, batch_size=128, hard_negatives=False
     list and no score on the host; enc_dec scores through score_ids(formula, anchors, targets, neg). The one negative per
     query comes from the library's counter stream (mpqe_sample_negatives, seeded per batch by auc_batch_seed), NOT from
     Python's Mersenne Twister: for a given `seed` the draws differ from the list path's -- the same distribution, other
-    numbers; the deviation sampling.py states. lib: the stand-in library of the sets' index (kg.KGIndex(lib=...)), if any."""
-    if _on_device(test_queries):
+    numbers; the deviation sampling.py states. lib: the stand-in library of the sets' index (kg.KGIndex(lib=...)), if any.
+
+    {query type: kg.MixedQuerySet} (MixedQuerySet.from_sets) is the device route over queries of DIFFERENT formulas at once:
+    the windows are [lo, lo + batch_size) over a type's concatenation, each one sampler draw (auc_window_seed's seed: for a
+    given `seed` other negatives than the QuerySet route's -- the same deviation) and one scoring call --
+    enc_dec.score_ids_mixed where the model has it (ONE launch), the runs of a window through score_ids otherwise; the
+    {formula: AUC} dict comes from ONE ops.eval_auc_segments and one copy of its integers."""
+    kind = _on_device(test_queries)
+    if kind == 'mixed':
+        return _eval_auc_mixed(test_queries, enc_dec, batch_size, hard_negatives, seed, lib)
+    if kind:
         return _eval_auc_sets(test_queries, enc_dec, batch_size, hard_negatives, seed, lib)
     predictions, labels, formula_aucs = [], [], {}
     random.seed(seed)
@@ -178,8 +285,13 @@ def eval_perc_queries(test_queries, enc_dec, batch_size=128, hard_negatives=Fals
 
     {formula: kg.QuerySet} takes the device route (see eval_auc_queries): ops.eval_counts per window, the per-query
     percentiles -- percentile_of_score's to the bit -- and their mean in float64 on the device. The mean may differ from
-    np.mean's by the order of the additions: at most Q * 2^-52 relative over Q non-negative terms."""
-    if _on_device(test_queries):
+    np.mean's by the order of the additions: at most Q * 2^-52 relative over Q non-negative terms.
+    {query type: kg.MixedQuerySet}: the same per-query percentiles from windows over a type's concatenation, one scoring
+    call and one ops.eval_counts a window (see eval_auc_queries)."""
+    kind = _on_device(test_queries)
+    if kind == 'mixed':
+        return _eval_perc_mixed(test_queries, enc_dec, batch_size, hard_negatives, lib)
+    if kind:
         return _eval_perc_sets(test_queries, enc_dec, batch_size, hard_negatives, lib)
     perc_scores = []
     for formula in test_queries:

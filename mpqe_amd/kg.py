@@ -1014,3 +1014,60 @@ class QuerySet(object):
         hard, hard_off = (None, None) if self.hard is None else (self.hard[0].cpu().tolist(), self.hard[1].cpu().tolist())
         return [Query(query_graph_tuple(self.formula, t[i], a[i], v[i]), neg[neg_off[i]:neg_off[i + 1]],
                       None if hard is None else hard[hard_off[i]:hard_off[i + 1]], keep_graph=True) for i in range(len(t))]
+
+
+class MixedQuerySet(object):
+    """The QuerySets of ONE query type concatenated in their dict's order (evaluation.eval_*_queries over queries of
+    different formulas at once; QueryEncoderDecoder.score_ids_mixed): formulas (a tuple of Formula), formula_of [Q] int64
+    every query's position in it, targets [Q], anchors [Q, A], neg / hard = (ids, offsets [Q + 1]) CSR over the whole
+    (hard None for the chain types) -- all on the device --, and on the host the mirrors that size a window without a
+    synchronisation: formula_of_host [Q], bounds [F + 1] (formula f's queries are [bounds[f], bounds[f + 1])) and
+    offsets_host()."""
+
+    def __init__(self, index, query_type, formulas, formula_of, targets, anchors, neg, hard, bounds, formula_of_host,
+                 offsets_host):
+        self.index, self.query_type, self.formulas = index, query_type, tuple(formulas)
+        self.formula_of, self.targets, self.anchors, self.neg, self.hard = formula_of, targets, anchors, neg, hard
+        self.bounds, self.formula_of_host = bounds, formula_of_host
+        self._offsets_host = offsets_host
+
+    def __len__(self):
+        return int(self.targets.shape[0])
+
+    def offsets_host(self, hard=False):
+        """the host mirror of the negatives' (hard: the hard negatives') offsets, int64 [Q + 1], or None"""
+        return self._offsets_host[bool(hard)]
+
+    @classmethod
+    def from_sets(cls, sets):
+        """{Formula: QuerySet} -> {query type: MixedQuerySet}, types and formulas in the dict's order. Tensor concatenations
+        and the sets' own host mirrors of their offsets (QuerySet.offsets_host: lengths only, copied once per set): no
+        per-query host work, no id on the host."""
+        by_type = {}
+        for formula, qs in sets.items():
+            if not isinstance(qs, QuerySet) or qs.formula != formula:
+                raise TypeError('MixedQuerySet.from_sets: {formula: kg.QuerySet of that formula}')
+            by_type.setdefault(formula.query_type, []).append(qs)
+        out = {}
+        for qt, group in by_type.items():
+            index, dev = group[0].index, group[0].index.device
+            lens = np.array([len(qs) for qs in group], dtype=np.int64)
+            bounds = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+            fo_host = np.repeat(np.arange(len(group), dtype=np.int64), lens)
+
+            def csr(hard):
+                pairs = [qs.hard if hard else qs.neg for qs in group]
+                if any(p is None for p in pairs):
+                    return None, None
+                hosts = [qs.offsets_host(hard) for qs in group]
+                base = np.concatenate([[0], np.cumsum([int(h[-1]) for h in hosts])]).astype(np.int64)
+                host = np.concatenate([np.zeros(1, dtype=np.int64)] + [h[1:] + base[k] for k, h in enumerate(hosts)])
+                offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev)] +
+                                    [p[1][1:] + int(base[k]) for k, p in enumerate(pairs)])
+                return (torch.cat([p[0] for p in pairs]), offsets), host
+            neg, neg_host = csr(False)
+            hard, hard_host = csr(True)
+            out[qt] = cls(index, qt, [qs.formula for qs in group], torch.from_numpy(fo_host).to(dev),
+                          torch.cat([qs.targets for qs in group]), torch.cat([qs.anchors for qs in group]), neg, hard, bounds,
+                          fo_host, {False: neg_host, True: hard_host})
+        return out

@@ -594,6 +594,43 @@ def _device_ids(anchors, targets, neg, device, num_anchors):
     return anchors, targets, neg_ids, q_row
 
 
+def formula_runs(formula_of):
+    """[(formula index, lo, hi)] of the maximal stretches of equal entries of a host int vector"""
+    fo = np.asarray(formula_of, dtype=np.int64)
+    if fo.shape[0] == 0:
+        return []
+    cuts = np.concatenate([[0], np.nonzero(fo[1:] != fo[:-1])[0] + 1, [fo.shape[0]]])
+    return [(int(fo[lo]), int(lo), int(hi)) for lo, hi in zip(cuts[:-1], cuts[1:])]
+
+
+def score_ids_by_runs(model, formulas, formula_of_host, anchors, targets, neg=None, offsets_host=None):
+    """model.score_ids over every run of equal formula of a concatenation, the scores put back in forward()'s layout of the
+    whole: [B] targets, then the negatives in CSR order. For a model without a mixed launch (RGCNEncoderDecoder) and for
+    the formulas the fused GQE kernel does not cover. offsets_host: the host mirror of neg[1] (read from the device
+    otherwise)."""
+    B = int(targets.shape[0])
+    if neg is not None and offsets_host is None:
+        offsets_host = neg[1].cpu().numpy()
+    total = 0 if neg is None else int(neg[0].shape[0])
+    out = None
+    for f, lo, hi in formula_runs(formula_of_host):
+        if not 0 <= f < len(formulas):
+            raise IndexError('formula index %d outside the %d formulas' % (f, len(formulas)))
+        sub = None
+        if neg is not None:
+            a, b = int(offsets_host[lo]), int(offsets_host[hi])
+            sub = (neg[0][a:b], neg[1][lo:hi + 1] - a)
+        s = model.score_ids(formulas[f], anchors[lo:hi], targets[lo:hi], neg=sub)
+        if out is None:
+            out = torch.empty(B + total, dtype=torch.float32, device=s.device)
+        out[lo:hi] = s[:hi - lo]
+        if neg is not None:
+            out[B + a:B + b] = s[hi - lo:]
+    if out is None:
+        out = torch.empty(0, dtype=torch.float32, device=targets.device)
+    return out
+
+
 def gqe_plan(formula):
     """(form, [(anchor slot or None = the target side, mode, [(relation, transposed)])], intersection mode or None,
     [(relation, transposed)] after the intersection, mode of the other side): model.py:78-116 as data."""
@@ -641,6 +678,8 @@ class QueryEncoderDecoder(nn.Module, _EntityRanking):
     train() mode it is always recomputed. Code that writes parameters through raw pointers (no version bump) must switch
     to train() or set model.__dict__['_cand'] = None."""
 
+    MIXED_KEPT = 16         # score_ids_mixed: descriptor blocks kept, one per `formulas` sequence
+
     def __init__(self, graph, enc, path_dec, inter_dec):
         super(QueryEncoderDecoder, self).__init__()
         self.enc = enc
@@ -658,6 +697,7 @@ class QueryEncoderDecoder(nn.Module, _EntityRanking):
         state['_row_ids'] = None        # (what answer() caches on the device: the row -> id maps, a chain's projected candidates)
         state['_maps_np'] = None
         state['_cand'] = None
+        state['_mixed'] = None          # (score_ids_mixed's descriptor block: device addresses)
         return state
 
     def _apply(self, fn, *args, **kwargs):
@@ -666,6 +706,7 @@ class QueryEncoderDecoder(nn.Module, _EntityRanking):
         self.__dict__['_row_ids'] = None
         self.__dict__['_maps_np'] = None
         self.__dict__['_cand'] = None
+        self.__dict__['_mixed'] = None
         return out
 
     # ------------------------------------------------------------------ helpers
@@ -726,12 +767,14 @@ class QueryEncoderDecoder(nn.Module, _EntityRanking):
         return (ops.gqe_supported(D) and all(tuple(p.shape) == want for p in used)
                 and all(tuple(m.shape) == (D, D) for m in mats))
 
-    def _programme(self, plan):
-        """(programme of mpqe_gqe_fwd / mpqe_gqe_embed, the modes of its tables, its matrices / vectors) of one plan."""
+    def _programme(self, plan, shared=None):
+        """(programme of mpqe_gqe_fwd / mpqe_gqe_embed, the modes of its tables, its matrices / vectors) of one plan.
+        shared: (modes, mats, {id(parameter): index}) that several programmes number their tables and parameters in
+        (score_ids_mixed); they grow in place."""
         from .decoders import SetIntersection
         form, branches, imode, tail, emode = plan
         op, path, _ = self._path_kind()
-        modes, mats, mat_ids = [], [], {}
+        modes, mats, mat_ids = ([], [], {}) if shared is None else shared
 
         def table_of(mode):
             if mode not in modes:
@@ -818,6 +861,76 @@ class QueryEncoderDecoder(nn.Module, _EntityRanking):
                 scores = self._composed_ids(formula, anchors, tnodes, q_row, plan)
             self._check()
         return scores
+
+    def _mixed_descriptors(self, formulas):
+        """(the kept ops.GqeMixedDescriptors of `formulas`, or None where the fused kernel does not cover every formula;
+        the first formula's plan). Kept in self.__dict__['_mixed'] (copies and pickles drop it), one entry per `formulas`
+        sequence -- an evaluation walks the seven query types in turn --, at most MIXED_KEPT of them, the oldest leaving
+        first. An entry is keyed on the identity of `formulas`, `fused` and data_ptr() of every parameter (the tables among
+        them): the block holds addresses, not values, so an optimizer step keeps it, and a call that finds it does no work
+        per formula."""
+        key = (len(formulas), bool(self.fused), tuple(p.data_ptr() for p in self.parameters()))
+        kept = self.__dict__.get('_mixed')
+        if kept is None:
+            kept = self.__dict__['_mixed'] = {}
+        entry = kept.get(id(formulas))
+        if entry is not None and entry[0] == key and entry[1] is formulas:
+            return entry[2], entry[3]
+        if len(formulas) == 0 or len({f.query_type for f in formulas}) != 1:
+            raise ValueError('score_ids_mixed: formulas of one query type')
+        plans = [self._plan(f) for f in formulas]
+        desc = None
+        same = len({(plan[0], len(plan[1]), tuple(len(steps) for _, _, steps in plan[1]), len(plan[3]), plan[2] is None)
+                    for plan in plans}) == 1
+        if same and all(self._fused_ok(plan) for plan in plans):
+            shared = ([], [], {})
+            progs = np.stack([self._programme(plan, shared)[0] for plan in plans])
+            desc = ops.GqeMixedDescriptors(progs, [self.enc.table(m) for m in shared[0]], shared[1])
+        kept.pop(id(formulas), None)
+        while len(kept) >= self.MIXED_KEPT:
+            kept.pop(next(iter(kept)))
+        kept[id(formulas)] = (key, formulas, desc, plans[0])
+        return desc, plans[0]
+
+    def score_ids_mixed(self, formulas, formula_of, anchors, targets, neg=None):
+        """score_ids for queries of DIFFERENT formulas of one query type (kg.MixedQuerySet): `formulas` a sequence of
+        Formula of that type, formula_of [B] int64 every query's position in it, the rest as in score_ids over the
+        concatenation. -> fp32 [B + total] in forward()'s layout, under no_grad, bit for bit the scores score_ids gives
+        run by run. Where the fused kernel covers every formula this is ONE ops.gqe_scores_mixed launch, and the
+        descriptor block of `formulas` is kept for the next call (_mixed_descriptors: pass the SAME sequence object);
+        otherwise the runs of equal formula are walked through score_ids (one read of formula_of and the offsets)."""
+        if not torch.is_tensor(formula_of) or formula_of.dtype != torch.long or formula_of.dim() != 1:
+            raise TypeError('score_ids_mixed: formula_of must be an int64 vector')
+        with torch.no_grad():
+            desc, (form, branches, imode, tail, emode) = self._mixed_descriptors(formulas)
+            device = self._device()
+            anchors, targets, neg_ids, q_row = _device_ids(anchors, targets, neg, device, len(formulas[0].anchor_modes))
+            B = int(targets.shape[0])
+            if formula_of.shape[0] != B:
+                raise ValueError('score_ids_mixed: formula_of [B]')
+            if desc is None:
+                return self._mixed_by_runs(formulas, formula_of, anchors, targets, neg)
+            formula_of = formula_of.to(device).contiguous()
+            tnodes = targets if neg_ids is None else torch.cat([targets, neg_ids])
+            n = int(tnodes.shape[0])
+            qrow = neg_off = None
+            if form == 0:
+                p_ids, e_ids = tnodes.reshape(1, n), anchors[:, 0].contiguous()
+                qrow = q_row if q_row is not None else torch.arange(B, dtype=torch.long, device=device)
+            else:
+                slots = [slot for slot, _, _ in branches if slot is not None]
+                p_ids, e_ids = anchors[:, slots].t().contiguous(), tnodes
+                if n > B:
+                    neg_off = neg[1].to(device).contiguous()
+            scores = ops.gqe_scores_mixed(desc, self.enc.node_maps, formula_of, p_ids, e_ids, qrow, neg_off, n,
+                                          self._error_word(device))
+            self._check()
+        return scores
+
+    def _mixed_by_runs(self, formulas, formula_of, anchors, targets, neg):
+        """score_ids_mixed without the mixed launch: every run of equal formula through score_ids, put back in forward()'s
+        layout of the whole"""
+        return score_ids_by_runs(self, formulas, formula_of.cpu().numpy(), anchors, targets, neg)
 
     def _composed_ids(self, formula, anchors, tnodes, q_row, plan):
         """_composed_scores on id tensors (enc(ids, mode) takes them)"""

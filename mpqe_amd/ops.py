@@ -886,6 +886,63 @@ def gqe_embed(prog, tables, mats, node_map, p_ids, p_rows, err=None):
     return out
 
 
+class GqeMixedDescriptors(object):
+    """The device block of mpqe_gqe_mixed_desc_build (include/mpqe_amd.h) for F programmes of one query type over one list
+    of tables and one list of parameters: what a formula alone decides -- its tables, the parameter and transposition of
+    every site. It depends on the programmes and on the ADDRESSES of the tables and parameters only, so it is built once
+    and kept (the tensors are held here, which keeps the addresses theirs)."""
+
+    def __init__(self, progs, tables, mats):
+        import ctypes
+        progs = np.ascontiguousarray(progs, dtype=np.int32)
+        if progs.ndim != 2 or progs.shape[0] < 1 or progs.shape[1] != GQE_PROG_INTS:
+            raise ValueError('gqe_scores_mixed: programmes [F >= 1, %d]' % GQE_PROG_INTS)
+        tables = [_f(t.detach(), 'embedding table') for t in tables]
+        mats = [_f(m.detach(), 'matrix') for m in mats]
+        D = tables[0].shape[1]
+        if any(t.dim() != 2 or t.shape[1] != D for t in tables) or any(tuple(m.shape) not in ((D, D), (D,)) for m in mats):
+            raise ValueError('gqe_scores_mixed: every table [rows, D] and every parameter [D, D] or [D] with one D')
+        for prog in progs:
+            _gqe_check_params(prog, mats, D, 'gqe_scores_mixed')
+        self.progs, self.tables, self.mats, self.dim = progs, tables, mats, int(D)
+        self.num_formulas = int(progs.shape[0])
+        dev = tables[0].device
+        L = lib()
+        self.nbytes = L.mpqe_gqe_mixed_desc_bytes(self.num_formulas)
+        if self.nbytes == 0:
+            raise ValueError('gqe_scores_mixed: more formulas than the kernel covers')
+        self.buffer = torch.empty(self.nbytes + 256, dtype=torch.uint8, device=dev)
+        self.ptr = _capi._align256(self.buffer.data_ptr())
+        tab_arr = (ctypes.c_void_p * len(tables))(*[_p(t) for t in tables])
+        rows_arr = (ctypes.c_int64 * len(tables))(*[t.shape[0] for t in tables])
+        mat_arr = (ctypes.c_void_p * max(len(mats), 1))(*[_p(m) for m in mats])
+        with torch.cuda.device(dev):
+            _ck(L.mpqe_gqe_mixed_desc_build(progs.ctypes.data, self.num_formulas, tab_arr, rows_arr, len(tables), mat_arr,
+                                            len(mats), D, self.ptr, self.nbytes, _stream()), 'mpqe_gqe_mixed_desc_build')
+
+
+def gqe_scores_mixed(desc, node_map, formula_of, p_ids, e_ids, qrow, neg_off, n, err=None, eps=1e-8):
+    """The GQE scores of queries of DIFFERENT formulas of one query type in one launch (mpqe_gqe_fwd_mixed,
+    include/mpqe_amd.h): gqe_scores' operands over the concatenation, formula_of [B] int64 on the device naming every
+    query's programme in `desc` (a GqeMixedDescriptors, kept by the caller). -> fp32 [n], bit for bit what gqe_scores
+    gives run by run. Inference only: nothing here is differentiated."""
+    formula_of, p_ids, e_ids = _i(formula_of, 'formula_of'), _i(p_ids, 'p_ids'), _i(e_ids, 'e_ids')
+    node_map = None if node_map is None else _i(node_map, 'node_map')
+    qrow = None if qrow is None else _i(qrow, 'qrow')
+    neg_off = None if neg_off is None else _i(neg_off, 'neg_off')
+    n, B = int(n), int(formula_of.shape[0])
+    if formula_of.dim() != 1 or p_ids.dim() != 2 or e_ids.dim() != 1:
+        raise ValueError('gqe_scores_mixed: formula_of [B], p_ids [branches, p_rows], e_ids [e_rows]')
+    dev = desc.tables[0].device
+    scores = torch.empty((n,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _ck(lib().mpqe_gqe_fwd_mixed(desc.progs.ctypes.data, desc.num_formulas, desc.ptr, desc.nbytes, _p(node_map),
+                                     0 if node_map is None else node_map.shape[0], desc.dim, _p(formula_of), B, _p(p_ids),
+                                     int(p_ids.shape[1]), _p(e_ids), int(e_ids.shape[0]), _p(qrow), _p(neg_off), n,
+                                     float(eps), _p(scores), _p(err), _stream()), 'mpqe_gqe_fwd_mixed')
+    return scores
+
+
 # --------------------------------------------------------------------------------------------- neighbourhood encoder
 SAGE_MAX_DIM, SAGE_MAX_KEEP, SAGE_MAX_RELS = 256, _capi.SAGE_MAX_KEEP, _capi.SAGE_MAX_RELS
 
@@ -1052,3 +1109,27 @@ def eval_auc(pos, neg, lib=None):
 def auc_from_statistic(u2, n_pos, n_neg):
     """ROC-AUC from eval_auc's integer: one float64 division (what evaluation.roc_auc rounds to as well, n below 2^26)"""
     return u2 / (2 * n_pos * n_neg)
+
+
+def eval_auc_segments(pos, neg, pos_off, neg_off, lib=None):
+    """int64 [S] on the scores' device: eval_auc's integer U2 of every segment s -- pos[pos_off[s]:pos_off[s + 1]] against
+    neg[neg_off[s]:neg_off[s + 1]] -- in one call with no host read (mpqe_eval_auc_segments, include/mpqe_amd.h); 0 where a
+    side is empty. pos, neg: fp32 vectors, pos_off / neg_off: int64 [S + 1], all on the device. The caller copies the S
+    integers once and divides (auc_from_statistic); a statistic is below 2^63 (2 n_pos n_neg < 2^63), so int64 holds it."""
+    pos, neg = _eval_operand(pos, torch.float32, 'pos', lib), _eval_operand(neg, torch.float32, 'neg', lib)
+    pos_off, neg_off = _eval_operand(pos_off, torch.int64, 'pos_off', lib), _eval_operand(neg_off, torch.int64, 'neg_off', lib)
+    if pos.dim() != 1 or neg.dim() != 1 or pos_off.dim() != 1 or neg_off.dim() != 1 or pos_off.shape != neg_off.shape \
+            or pos_off.shape[0] < 2:
+        raise ValueError('eval_auc_segments: two score vectors and two offset vectors [S + 1], S >= 1')
+    n_pos, n_neg, S = int(pos.shape[0]), int(neg.shape[0]), int(pos_off.shape[0]) - 1
+    dev = pos.device
+    out = torch.empty(S, dtype=torch.int64, device=dev)
+    with (torch.cuda.device(dev) if lib is None else contextlib.nullcontext()):
+        L, stream = _eval_lib(dev, lib)
+        need = L.mpqe_eval_auc_segments_workspace_bytes(n_pos, n_neg, S)
+        if need == 0:
+            raise ValueError('eval_auc_segments: more scores or segments than the kernel covers (2^31)')
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        _capi.check(L, L.mpqe_eval_auc_segments(_p(pos), n_pos, _p(neg), n_neg, _p(pos_off), _p(neg_off), S, _p(out), _p(ws),
+                                                need, stream), 'mpqe_eval_auc_segments')
+    return out

@@ -5,9 +5,12 @@ a query's negatives; evaluation.eval_auc_queries / eval_perc_queries) over test 
          per batch Python id lists into forward(), the scores back through .cpu().tolist(), the metrics in Python
   sets   the QuerySets themselves: score_ids on device ids, the negatives drawn by the library's sampler, the metrics by
          mpqe_eval_auc / mpqe_eval_counts (csrc/eval.hip); one 8-byte read per AUC, one for the mean percentile
+  mixed  kg.MixedQuerySet.from_sets(sets), built once outside the rounds (its time is reported as from_sets_ms): windows
+         over a query type's concatenation, queries of different formulas in one scoring call (score_ids_mixed: one launch
+         for gqe; rgcn walks a window's runs), one sampler a type, the per-formula AUCs from one mpqe_eval_auc_segments
 
 on the `small` (480 entities) and `aifb` (2 601 entities) synthetic shapes, for both models (rgcn: RGCNEncoderDecoder, mp
-readout; gqe: QueryEncoderDecoder, bilinear paths + mean intersection). Both sides run in the same process in alternating
+readout; gqe: QueryEncoderDecoder, bilinear paths + mean intersection). The sides run in the same process in alternating
 rounds after --warmup rounds of each; a round's time is the host clock around the calls, ending in a device synchronise.
 Medians of --rounds rounds, min and max beside them. The two sides score the same queries and negatives; the sampled
 negative of the AUC comes from Python's stream on the list side and from the library's on the other, so the AUCs differ
@@ -80,6 +83,12 @@ def run(kg, which, args, device, emit):
     base = dict(kg=kg, model=which, min_per_formula=args.min_per_formula, queries=Q, formulas=len(sets), negatives=negatives,
                 batch_size=args.batch_size, embed_dim=args.embed_dim)
     last = {}
+    from mpqe_amd.kg import MixedQuerySet
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    mixed = MixedQuerySet.from_sets(sets)
+    torch.cuda.synchronize()
+    base['from_sets_ms'] = 1e3 * (time.perf_counter() - t0)
 
     def list_side():
         t0 = time.perf_counter()
@@ -105,15 +114,40 @@ def run(kg, which, args, device, emit):
         last['sets'] = (float(auc), float(perc))
         return [1e3 * (t2 - t0), 0.0, 1e3 * (t1 - t0), 1e3 * (t2 - t1)]
 
+    def mixed_side():
+        t0 = time.perf_counter()
+        auc, _ = evaluation.eval_auc_queries(mixed, model, batch_size=args.batch_size, seed=0)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        perc = evaluation.eval_perc_queries(mixed, model, batch_size=args.batch_size)
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        last['mixed'] = (float(auc), float(perc))
+        return [1e3 * (t2 - t0), 0.0, 1e3 * (t1 - t0), 1e3 * (t2 - t1)]
+
+    sides = {'list': list_side, 'sets': sets_side, 'mixed': mixed_side}
+    if args.profile:
+        import cProfile
+        import pstats
+        with torch.no_grad():
+            for _ in range(args.warmup):
+                sides[args.profile]()
+            prof = cProfile.Profile()
+            prof.enable()
+            sides[args.profile]()
+            prof.disable()
+        print('cProfile of one %s round, %s / %s' % (args.profile, kg, which))
+        pstats.Stats(prof).sort_stats('cumulative').print_stats(25)
+        return
     with torch.no_grad():
         for _ in range(args.warmup):
-            list_side()
-            sets_side()
-        times = {'list': [], 'sets': []}
-        for _ in range(args.rounds):                    # alternating: both sides see the same machine
-            times['list'].append(list_side())
-            times['sets'].append(sets_side())
-    for side in ('list', 'sets'):
+            for side in sides.values():
+                side()
+        times = {side: [] for side in sides}
+        for _ in range(args.rounds):                    # alternating: the sides see the same machine
+            for name, side in sides.items():
+                times[name].append(side())
+    for side in sides:
         t = np.asarray(times[side])
         emit(dict(base, row=side, ms=stats(t[:, 0]), queries_ms=stats(t[:, 1]), auc_ms=stats(t[:, 2]), perc_ms=stats(t[:, 3]),
                   auc=last[side][0], percentile=last[side][1]))
@@ -147,6 +181,8 @@ def main(argv=None):
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--rounds', type=int, default=7)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--profile', choices=['list', 'sets', 'mixed'], default=None,
+                    help='cProfile of one round of that side per (kg, model) instead of the timing')
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit('eval_sets_bench: needs the GPU (a CPU timing says nothing about it)')
@@ -159,17 +195,22 @@ def main(argv=None):
     for kg in args.kgs:
         for which in args.models:
             run(kg, which, args, device, emit)
-    print('| kg | model | queries | negatives | list ms (queries() + AUC + percentile) | sets ms (AUC + percentile) | list / sets | '
-          'eval_auc ms | eval_counts ms |')
-    print('|---|---|---:|---:|---:|---:|---:|---:|---:|')
+    if args.profile:
+        return rows
+    print('| kg | model | queries | formulas | list ms (queries() + AUC + percentile) | sets ms (AUC + percentile) | '
+          'mixed ms (AUC + percentile) [min .. max] | list / mixed | sets / mixed | eval_auc ms | eval_counts ms |')
+    print('|---|---|---:|---:|---:|---:|---:|---:|---:|---:|---:|')
     keyed = {}
     for r in rows:
         keyed.setdefault((r['kg'], r['model']), {})[r['row']] = r
     for (kg, which), d in keyed.items():
-        li, se, ke = d['list'], d['sets'], d['kernels']
-        print('| %s | %s | %d | %d | %.1f (%.1f + %.1f + %.1f) | %.1f (%.1f + %.1f) | %.1fx | %.3f | %.3f |'
-              % (kg, which, li['queries'], li['negatives'], li['ms'][0], li['queries_ms'][0], li['auc_ms'][0], li['perc_ms'][0],
-                 se['ms'][0], se['auc_ms'][0], se['perc_ms'][0], li['ms'][0] / se['ms'][0], ke['auc_ms'][0], ke['counts_ms'][0]))
+        li, se, mi, ke = d['list'], d['sets'], d['mixed'], d['kernels']
+        print('| %s | %s | %d | %d | %.1f (%.1f + %.1f + %.1f) [%.1f .. %.1f] | %.1f (%.1f + %.1f) [%.1f .. %.1f] | '
+              '%.1f (%.1f + %.1f) [%.1f .. %.1f] | %.1fx | %.1fx | %.3f | %.3f |'
+              % (kg, which, li['queries'], li['formulas'], li['ms'][0], li['queries_ms'][0], li['auc_ms'][0], li['perc_ms'][0],
+                 li['ms'][1], li['ms'][2], se['ms'][0], se['auc_ms'][0], se['perc_ms'][0], se['ms'][1], se['ms'][2],
+                 mi['ms'][0], mi['auc_ms'][0], mi['perc_ms'][0], mi['ms'][1], mi['ms'][2], li['ms'][0] / mi['ms'][0],
+                 se['ms'][0] / mi['ms'][0], ke['auc_ms'][0], ke['counts_ms'][0]))
     if args.out:
         with open(args.out, 'w') as f:
             json.dump(dict(args=vars(args), rows=rows), f, indent=1)

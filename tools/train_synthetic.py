@@ -13,6 +13,7 @@ type), loss.backward(), Adam; evaluation by ROC-AUC with one sampled negative pe
     python tools/train_synthetic.py --model gqe --kg small --steps 300 --kg-index    # its filtered metrics through kg.KGIndex
     python tools/train_synthetic.py --model gqe --kg small --steps 300 --device-queries   # queries sampled on the device index
     python tools/train_synthetic.py --model gqe --kg small --steps 300 --device-queries --device-eval   # ... and scored there
+    python tools/train_synthetic.py --model gqe --kg small --steps 300 --device-queries --device-eval --mixed-eval   # ... by query type
     python tools/train_synthetic.py --model gqe --kg small --steps 100 --depth 1 --kg-index    # the neighbourhood encoder, on the index
     python tools/train_synthetic.py --kg small --steps 100 --depth 2 --kg-index                 # ... two layers, under the R-GCN model
 
@@ -136,7 +137,17 @@ def test_dict(test):
 def model_queries(args, tq):
     """What the model's evaluation takes: the test QuerySets themselves under --device-eval (evaluation.eval_*_queries then
     score and rank on the device: no Query object, no id list, no score on the host), else the lists of Query."""
-    return args.test_sets if getattr(args, 'device_eval', False) else tq
+    return eval_sets(args) if getattr(args, 'device_eval', False) else tq
+
+
+def eval_sets(args):
+    """the test QuerySets, or under --mixed-eval the same sets grouped by query type (kg.MixedQuerySet.from_sets, once)"""
+    if not getattr(args, 'mixed_eval', False):
+        return args.test_sets
+    if getattr(args, 'test_mixed', None) is None:
+        from mpqe_amd.kg import MixedQuerySet
+        args.test_mixed = MixedQuerySet.from_sets(args.test_sets)
+    return args.test_mixed
 
 
 def main(argv=None):
@@ -177,6 +188,9 @@ def main(argv=None):
                     help='with --device-queries: evaluate the model on the test QuerySets themselves (AUC and percentile rank '
                          'computed on the device, evaluation.eval_auc_queries / eval_perc_queries over kg.QuerySet); the '
                          'sampled negatives then come from the library\'s stream, not Python\'s')
+    ap.add_argument('--mixed-eval', action='store_true',
+                    help='with --device-eval: group the test sets by query type (kg.MixedQuerySet) and score queries of '
+                         'different formulas per call -- one launch a window under --model gqe; other sampled negatives')
     ap.add_argument('--depth', type=int, default=0, choices=[0, 1, 2],
                     help='entity encoder (the reference\'s --depth): 0 the embedding lookup (everything above), 1 / 2 the '
                          'neighbourhood-aggregating Encoder of utils.get_encoder under either --model, trained through '
@@ -186,6 +200,8 @@ def main(argv=None):
         ap.error('--batched-queries needs --device-queries')
     if args.device_eval and (not args.device_queries or args.depth):
         ap.error('--device-eval needs --device-queries and the embedding-lookup encoder (--depth 0)')
+    if args.mixed_eval and not args.device_eval:
+        ap.error('--mixed-eval needs --device-eval')
     if args.depth:
         out = run_depth(args)
     elif args.model == 'gqe':
@@ -255,7 +271,7 @@ def run(args):
                auc_after=float(auc1), auc_curve=aucs, loss_curve=[float(v) for v in losses[:, 0]])
     if getattr(args, 'device_eval', False):
         with torch.no_grad():
-            out['perc_after'] = float(evaluation.eval_perc_queries(args.test_sets, model, batch_size=128))
+            out['perc_after'] = float(evaluation.eval_perc_queries(eval_sets(args), model, batch_size=128))
     if args.oracle:
         out.update(run_oracle(args, graph, node_maps, model, cpu_state, train, tq, steps, negs_used, anchors, targets))
     return out
@@ -492,7 +508,7 @@ def run_gqe(args):
                loss_curve=losses)
     if getattr(args, 'device_eval', False):
         with torch.no_grad():
-            out['perc_after'] = float(evaluation.eval_perc_queries(args.test_sets, model, batch_size=128))
+            out['perc_after'] = float(evaluation.eval_perc_queries(eval_sets(args), model, batch_size=128))
     return out
 
 
