@@ -820,6 +820,62 @@ int mpqe_gqe_fwd_mixed(const int32_t *prog_host, int64_t num_formulas, const voi
                        const int64_t *qrow, const int64_t *neg_off, int64_t n, float eps, float *scores, int32_t *err,
                        void *stream);
 
+/* R-GCN queries of DIFFERENT formulas of one query type scored in two launches, forward only (csrc/rgcn_mixed.hip; added
+ * under ABI 7: entries only). The formulas of a query type share the template, the pass count, the layers and the readout;
+ * a formula's own part is one record of MPQE_RGCN_MIX_REC_INTS int32:
+ *   [0..2] the relation id of every template edge (mpqe_template_info's edge order, as edge_type_host of
+ *          mpqe_rgcn_template_fwd), [3..5] the table index of every anchor slot, [6..8] the mode-embedding row of every
+ *          variable slot, [9] the target mode's table index. Entries past the template's edges / anchors / variables
+ *          are not read.
+ * mpqe_rgcn_mixed_desc_build range-checks every field read (relation >= 0, table index in [0, num_tables), row in
+ * [0, mode_emb_rows); tables non-NULL with table_rows >= 0: MPQE_ERR_INVALID_ARG; a table that is not 16-byte aligned:
+ * MPQE_ERR_UNSUPPORTED) before anything is written, and writes one descriptor per formula to `desc` (device memory,
+ * 256-byte aligned, mpqe_rgcn_mixed_desc_bytes(num_formulas): exact, a byte less is MPQE_ERR_WORKSPACE and nothing is
+ * written; 0: num_formulas out of range). The block holds ADDRESSES and indices only: the caller keeps it between calls
+ * and rebuilds it when a table has moved; a scoring call does no host work per formula.
+ *
+ * Operands of a scoring call: node_map / node_map_len as in mpqe_embed_l2norm_fwd; mode_emb the mode embeddings (at least
+ * the mode_emb_rows of the build); basis_host / root_host / bias_host HOST arrays of `passes` device pointers -- entry p
+ * is the layer pass p runs (basis [num_relations, dim, dim], root [dim, dim], bias [dim] or NULL; bias_host itself may be
+ * NULL); ReLU after every pass but the last; readout MPQE_READOUT_TM / _SUM / _MAX; formula_of [num_queries] int64 and
+ * anchors [num_queries, A] int64 on the device. The queries are cut into blocks of 64 and a block into its stretches of
+ * one formula; a workgroup owns one stretch and runs its whole programme (64 workgroups per block, the spare ones leave at
+ * once; no pre-pass). workspace: mpqe_rgcn_mixed_workspace_bytes(query_type, num_queries, dim) -- exact: two node-state
+ * buffers and the query embeddings; 0: arguments out of range --, 16-byte aligned. mpqe_rgcn_embed_mixed runs the encode
+ * launch alone and writes the query embeddings to q_out [num_queries, dim]; mpqe_rgcn_fwd_mixed runs both launches:
+ * ids [n] / qrow [n] in the layout of forward() (row i is the pair of query qrow[i] and entity ids[i] of that query's
+ * target mode), scores [n].
+ *   bits       every score (every q_out element) equals BIT FOR BIT what the module path writes for it when the query's
+ *              run is handed to it alone: mpqe_embed_l2norm_fwd + mpqe_var_rows_fwd -> mpqe_rgcn_template_fwd per pass ->
+ *              mpqe_readout_fwd -> mpqe_embed_l2norm_fwd + mpqe_cosine_fwd.
+ *   shapes     dim % 4 == 0, mode_emb, every matrix and the workspace 16-byte aligned, 1 <= passes <= 4, readout one of
+ *              the three, num_queries < 2^25, n < 2^32: MPQE_ERR_UNSUPPORTED otherwise, before any launch.
+ *   bad index  a formula_of[q] outside [0, num_formulas) or a qrow[i] outside [0, num_queries) ORs MPQE_FLAG_BAD_INDEX
+ *              and the pairs concerned score 0 (the query's q_out row is zeros). A descriptor's relation outside
+ *              [0, num_relations) ORs MPQE_FLAG_BAD_RELATION with the same result.
+ *   bad ids    MPQE_FLAG_BAD_NODE_ID, the looked-up row becomes zeros, as on the module path.
+ *   The other queries' bits are unaffected and nothing is read or written out of bounds. num_queries == 0 (then n == 0):
+ *   MPQE_OK, no launch. Arguments are checked before any launch; a short descriptor block or workspace:
+ *   MPQE_ERR_WORKSPACE. The result does not depend on what the workspace held. */
+#define MPQE_RGCN_MIX_REC_INTS 10
+size_t mpqe_rgcn_mixed_desc_bytes(int64_t num_formulas);
+int mpqe_rgcn_mixed_desc_build(int query_type, const int32_t *recs_host, int64_t num_formulas,
+                               const float *const *tables_host, const int64_t *table_rows_host, int num_tables,
+                               int64_t mode_emb_rows, void *desc, size_t desc_bytes, void *stream);
+size_t mpqe_rgcn_mixed_workspace_bytes(int query_type, int64_t num_queries, int64_t dim);
+int mpqe_rgcn_embed_mixed(int query_type, int64_t num_formulas, const void *desc, size_t desc_bytes,
+                          const int64_t *node_map, int64_t node_map_len, const float *mode_emb,
+                          const float *const *basis_host, const float *const *root_host, const float *const *bias_host,
+                          int64_t num_relations, int passes, int readout, int64_t dim, const int64_t *formula_of,
+                          const int64_t *anchors, int64_t num_queries, void *workspace, size_t workspace_bytes,
+                          float *q_out /* [num_queries, dim] */, int32_t *err, void *stream);
+int mpqe_rgcn_fwd_mixed(int query_type, int64_t num_formulas, const void *desc, size_t desc_bytes, const int64_t *node_map,
+                        int64_t node_map_len, const float *mode_emb, const float *const *basis_host,
+                        const float *const *root_host, const float *const *bias_host, int64_t num_relations, int passes,
+                        int readout, int64_t dim, const int64_t *formula_of, const int64_t *anchors, int64_t num_queries,
+                        const int64_t *ids, const int64_t *qrow, int64_t n, float eps, void *workspace,
+                        size_t workspace_bytes, float *scores, int32_t *err, void *stream);
+
 /* ---- exact answers of a conjunctive query on the knowledge graph (csrc/kg.hip) ------------------------------------
  * reference: Graph.get_metapath_neighs graph.py:459-473 (the answer set of a chain) and Graph.get_negative_samples
  * graph.py:263-314 (intersection / union of the branch sets; negatives = full set - answers, hard negatives = union -

@@ -115,6 +115,12 @@ PROTOTYPES = {
     'mpqe_gqe_mixed_desc_bytes': (Z, [L]),
     'mpqe_gqe_mixed_desc_build': (I, [P, L, P, P, I, P, I, L, P, Z, P]),
     'mpqe_gqe_fwd_mixed': (I, [P, L, P, Z, P, L, L, P, L, P, L, P, L, P, P, L, F, P, P, P]),
+    # R-GCN queries of different formulas of one query type in two launches (added under ABI 7: entries only)
+    'mpqe_rgcn_mixed_desc_bytes': (Z, [L]),
+    'mpqe_rgcn_mixed_desc_build': (I, [I, P, L, P, P, I, L, P, Z, P]),
+    'mpqe_rgcn_mixed_workspace_bytes': (Z, [I, L, L]),
+    'mpqe_rgcn_embed_mixed': (I, [I, L, P, Z, P, L, P, P, P, P, L, I, I, L, P, P, L, P, Z, P, P, P]),
+    'mpqe_rgcn_fwd_mixed': (I, [I, L, P, Z, P, L, P, P, P, P, L, I, I, L, P, P, L, P, P, L, F, P, Z, P, P, P]),
     'mpqe_kg_workspace_bytes': (Z, [P, L, P, I, I]),
     'mpqe_kg_answers': (I, [P, P, P, P, I, P, I, P, L, P, P, P, I, P, Z, P, P]),
     'mpqe_kg_rows': (I, [P, L, L, P, I, P, P, L, P, P]),
@@ -203,6 +209,7 @@ KG_ROWS_SET, KG_ROWS_COMPLEMENT, KG_ROWS_WITH_HOLES = 0, 1, 2       # mpqe_kg_ro
 KG_QUERY_INTS = 10                                   # mpqe_kg_sample_queries: ints of one record
 KG_SAMPLE_MAX_K, KG_SAMPLE_MAX_ROWS = 1024, 1 << 22  # mpqe_kg_sample_rows
 SAGE_MAX_KEEP, SAGE_MAX_RELS = 32, 64                # mpqe_kg_sample_neighbours, mpqe_sage_fwd
+RGCN_MIX_REC_INTS, RGCN_MIX_MAX_PASSES = 10, 4       # mpqe_rgcn_mixed_desc_build: ints of one record; mpqe_rgcn_fwd_mixed
 
 
 def bind(cdll):

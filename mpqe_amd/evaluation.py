@@ -253,7 +253,9 @@ def eval_auc_queries(test_queries, enc_dec, batch_size=128, hard_negatives=False
     {query type: kg.MixedQuerySet} (MixedQuerySet.from_sets) is the device route over queries of DIFFERENT formulas at once:
     the windows are [lo, lo + batch_size) over a type's concatenation, each one sampler draw (auc_window_seed's seed: for a
     given `seed` other negatives than the QuerySet route's -- the same deviation) and one scoring call --
-    enc_dec.score_ids_mixed where the model has it (ONE launch), the runs of a window through score_ids otherwise; the
+    enc_dec.score_ids_mixed where the model has it (QueryEncoderDecoder: ONE launch; RGCNEncoderDecoder: two, whatever the
+    number of formulas; either walks the runs itself where its launch does not cover the model), the runs of a window
+    through score_ids otherwise; the
     {formula: AUC} dict comes from ONE ops.eval_auc_segments and one copy of its integers."""
     kind = _on_device(test_queries)
     if kind == 'mixed':

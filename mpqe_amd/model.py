@@ -9,8 +9,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import _capi, ops
 from .data_utils import RGCNQueryDataset
+from .graph import reverse_relation
 from .ops import scatter_add, scatter_max, scatter_mean  # noqa: F401  (re-exported like the reference)
 
 
@@ -371,6 +372,7 @@ class RGCNEncoderDecoder(nn.Module, _EntityRanking):
         state['_err'] = None
         state['_row_ids'] = None        # (the row -> id maps answer() caches on the device)
         state['_maps_np'] = None
+        state['_mixed'] = None          # (score_ids_mixed's descriptor blocks: device addresses)
         return state
 
     def __setstate__(self, state):
@@ -384,6 +386,7 @@ class RGCNEncoderDecoder(nn.Module, _EntityRanking):
         self.__dict__['_dropin_checked'] = False
         self.__dict__['_row_ids'] = None
         self.__dict__['_maps_np'] = None
+        self.__dict__['_mixed'] = None
         return out
 
     def dropin(self):
@@ -448,6 +451,112 @@ class RGCNEncoderDecoder(nn.Module, _EntityRanking):
             out = self.encode(formula, None, anchors, var_ids, q_graphs)
             ids = targets if neg_ids is None else torch.cat([targets, neg_ids])
             scores = ops.cosine(out, self._target_embeds(ids, formula.target_mode, device), q_row=q_row)
+            self._check()
+        return scores
+
+    # ------------------------------------------------------------------ queries of different formulas at once
+    MIXED_KEPT = 16         # score_ids_mixed: descriptor blocks kept, one per `formulas` sequence
+
+    def _mixed_passes(self, query_type):
+        """encode()'s pass count and the layer of every pass: layer i for pass i, the LAST layer for the last pass"""
+        if self.adaptive:
+            passes = RGCNQueryDataset.query_diameters[query_type]
+            if passes > len(self.layers):
+                raise ValueError(f'RGCN is adaptive with {len(self.layers)} layers, but query requires {passes}.')
+        else:
+            passes = self.num_layers
+        return passes, [self.layers[i] for i in range(passes - 1)] + [self.layers[-1]]
+
+    def _mixed_ok(self, formulas, passes):
+        """Whether ops.rgcn_scores_mixed covers this model and these formulas: the module path's own configuration
+        (`fused`, which also stands for "the library's launches, not a caller's"), a DirectEncoder-style `enc` with `table`
+        and `node_maps`, a readout without parameters, at most RGCN_MIX_MAX_PASSES passes, the model on the GPU and the
+        library's shape conditions. Everything else is walked run by run (score_ids_by_runs): the same layout, the same
+        bits."""
+        enc = self.enc
+        if not self.fused or self.encode_twice:
+            return False
+        if not (hasattr(enc, 'table') and getattr(enc, 'node_maps', None) is not None):
+            return False
+        if self.readout_str not in ('mp', 'sum', 'max') or self._device().type != 'cuda':
+            return False
+        modes = {m for f in formulas for m in tuple(f.anchor_modes) + (f.target_mode,)}
+        if any(enc.table(m).shape[1] != self.emb_dim or enc.table(m).dtype != torch.float32 for m in modes):
+            return False
+        return ops.rgcn_mixed_supported(self.emb_dim, passes, self.readout_str)
+
+    def _mixed_descriptors(self, formulas):
+        """(the kept ops.RgcnMixedDescriptors of `formulas`, or None where the mixed launch does not cover the model; the
+        layers of every pass). Kept in self.__dict__['_mixed'] (copies and pickles drop it, _apply resets it), one entry per
+        `formulas` sequence, at most MIXED_KEPT of them, the oldest leaving first. An entry is keyed on the identity of
+        `formulas`, on what _mixed_ok reads and on data_ptr() of every tensor the block points at -- the block holds
+        addresses, not values: an optimizer step keeps it, .to() or a FlatOptimizer that re-homes the parameters makes the
+        next call rebuild it."""
+        if len(formulas) == 0 or len({f.query_type for f in formulas}) != 1:
+            raise ValueError('score_ids_mixed: formulas of one query type')
+        passes, layers = self._mixed_passes(formulas[0].query_type)
+        kept = self.__dict__.get('_mixed')
+        if kept is None:
+            kept = self.__dict__['_mixed'] = {}
+        entry = kept.get(id(formulas))
+        state = (len(formulas), bool(self.fused), bool(self.encode_twice), self.readout_str, passes)
+        if entry is not None and entry[1] is formulas and entry[0] == state and (
+                entry[2] is None or entry[2].ptrs == tuple(self.enc.table(m).data_ptr() for m in entry[3])):
+            return entry[2], layers
+        desc, modes = None, []
+        if self._mixed_ok(formulas, passes):
+            info = ops.template_info(formulas[0].query_type)
+            A, V, E = info.num_anchors, info.num_vars, info.num_edges
+
+            def table_of(mode):
+                if mode not in modes:
+                    modes.append(mode)
+                return modes.index(mode)
+
+            recs = np.zeros((len(formulas), _capi.RGCN_MIX_REC_INTS), dtype=np.int32)
+            for k, f in enumerate(formulas):
+                if len(f.anchor_modes) != A:
+                    raise ValueError('formula %s has %d anchor modes, template expects %d' % (f, len(f.anchor_modes), A))
+                nodes, rels = f.get_nodes(), f.get_rels()
+                recs[k, 0:E] = [self.rel_ids[reverse_relation(rels[info.rel_label[e]])] for e in range(E)]
+                recs[k, 3:3 + A] = [table_of(m) for m in f.anchor_modes]
+                recs[k, 6:6 + V] = [self.mode_ids[nodes[info.var_node[v]]] for v in range(V)]
+                recs[k, 9] = table_of(f.target_mode)
+            desc = ops.RgcnMixedDescriptors(formulas[0].query_type, recs, [self.enc.table(m) for m in modes],
+                                            self.mode_embeddings.weight.shape[0])
+        kept.pop(id(formulas), None)
+        while len(kept) >= self.MIXED_KEPT:
+            kept.pop(next(iter(kept)))
+        kept[id(formulas)] = (state, formulas, desc, modes)
+        return desc, layers
+
+    def score_ids_mixed(self, formulas, formula_of, anchors, targets, neg=None):
+        """score_ids for queries of DIFFERENT formulas of one query type (kg.MixedQuerySet): `formulas` a sequence of
+        Formula of that type, formula_of [B] int64 every query's position in it, the rest as in score_ids over the
+        concatenation. -> fp32 [B + total] in forward()'s layout, under no_grad, bit for bit the scores score_ids gives
+        run by run. Where the mixed launch covers the model (_mixed_ok) this is ONE ops.rgcn_scores_mixed call -- two
+        launches whatever the number of formulas -- and the descriptor block of `formulas` is kept for the next call
+        (_mixed_descriptors: pass the SAME sequence object); otherwise the runs of equal formula are walked through
+        score_ids (one read of formula_of and the offsets)."""
+        if not torch.is_tensor(formula_of) or formula_of.dtype != torch.long or formula_of.dim() != 1:
+            raise TypeError('score_ids_mixed: formula_of must be an int64 vector')
+        with torch.no_grad():
+            desc, layers = self._mixed_descriptors(formulas)
+            device = self._device()
+            anchors, targets, neg_ids, q_row = _device_ids(anchors, targets, neg, device, len(formulas[0].anchor_modes))
+            B = int(targets.shape[0])
+            if formula_of.shape[0] != B:
+                raise ValueError('score_ids_mixed: formula_of [B]')
+            if desc is None:
+                return score_ids_by_runs(self, formulas, formula_of.cpu().numpy(), anchors, targets, neg)
+            if B == 0:
+                return torch.empty(0, dtype=torch.float32, device=device)
+            ids = targets if neg_ids is None else torch.cat([targets, neg_ids])
+            if q_row is None:
+                q_row = torch.arange(B, dtype=torch.long, device=device)
+            scores = ops.rgcn_scores_mixed(desc, self.enc.node_maps, self.mode_embeddings.weight,
+                                           [(l.basis, l.root, l.bias) for l in layers], self.readout_str,
+                                           formula_of.to(device), anchors, ids, q_row, self._error_word(device))
             self._check()
         return scores
 

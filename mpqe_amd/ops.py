@@ -943,6 +943,119 @@ def gqe_scores_mixed(desc, node_map, formula_of, p_ids, e_ids, qrow, neg_off, n,
     return scores
 
 
+# --------------------------------------------------------------------------------------------- R-GCN, mixed formulas
+RGCN_MIX_MAX_PASSES = _capi.RGCN_MIX_MAX_PASSES
+
+
+def rgcn_mixed_supported(dim, passes, readout):
+    """The shapes mpqe_rgcn_fwd_mixed covers (include/mpqe_amd.h)."""
+    return dim % 4 == 0 and 1 <= passes <= RGCN_MIX_MAX_PASSES and readout in READOUT_IDS
+
+
+class RgcnMixedDescriptors(object):
+    """The device block of mpqe_rgcn_mixed_desc_build (include/mpqe_amd.h) for F formulas of one query type over one list of
+    entity tables: what a formula alone decides -- the relation of every template edge, the table of every anchor slot, the
+    mode-embedding row of every variable slot, the target mode's table. recs [F, RGCN_MIX_REC_INTS] int32. It depends on the
+    records and on the ADDRESSES of the tables only, so it is built once and kept (the tensors are held here, which keeps
+    the addresses theirs); `ptrs` are those addresses, for a keeper that wants to know whether a tensor has moved."""
+
+    def __init__(self, query_type, recs, tables, mode_emb_rows):
+        import ctypes
+        recs = np.ascontiguousarray(recs, dtype=np.int32)
+        if recs.ndim != 2 or recs.shape[0] < 1 or recs.shape[1] != _capi.RGCN_MIX_REC_INTS:
+            raise ValueError('rgcn_scores_mixed: records [F >= 1, %d]' % _capi.RGCN_MIX_REC_INTS)
+        tables = [_f(t.detach(), 'embedding table') for t in tables]
+        D = tables[0].shape[1]
+        if any(t.dim() != 2 or t.shape[1] != D for t in tables):
+            raise ValueError('rgcn_scores_mixed: every table [rows, D] with one D')
+        self.query_type, self.qid = query_type, QUERY_TYPE_IDS[query_type]
+        self.recs, self.tables, self.dim = recs, tables, int(D)
+        self.num_formulas = int(recs.shape[0])
+        self.ptrs = tuple(_p(t) for t in tables)
+        dev = tables[0].device
+        L = lib()
+        self.nbytes = L.mpqe_rgcn_mixed_desc_bytes(self.num_formulas)
+        if self.nbytes == 0:
+            raise ValueError('rgcn_scores_mixed: more formulas than the kernel covers')
+        self.buffer = torch.empty(self.nbytes + 256, dtype=torch.uint8, device=dev)
+        self.ptr = _capi._align256(self.buffer.data_ptr())
+        tab_arr = (ctypes.c_void_p * len(tables))(*self.ptrs)
+        rows_arr = (ctypes.c_int64 * len(tables))(*[t.shape[0] for t in tables])
+        with torch.cuda.device(dev):
+            _ck(L.mpqe_rgcn_mixed_desc_build(self.qid, recs.ctypes.data, self.num_formulas, tab_arr, rows_arr, len(tables),
+                                             int(mode_emb_rows), self.ptr, self.nbytes, _stream()),
+                'mpqe_rgcn_mixed_desc_build')
+
+
+_RGCN_MIX_WS = {}        # device -> the mixed launches' workspace, grown in place (every call runs on the current stream)
+
+
+def _rgcn_mixed_ws(nbytes, device):
+    ws = _RGCN_MIX_WS.get(device)
+    if ws is None or ws.shape[0] < nbytes + 256:
+        ws = _RGCN_MIX_WS[device] = torch.empty(max(int(nbytes), 256) + 256, dtype=torch.uint8, device=device)
+    return _capi._align256(ws.data_ptr())
+
+
+def _rgcn_mixed_head(desc, node_map, mode_emb, layers, readout, formula_of, anchors):
+    """the operands mpqe_rgcn_embed_mixed and mpqe_rgcn_fwd_mixed share, checked -> (argument tuple, tensors to keep alive)"""
+    import ctypes
+    formula_of, anchors = _i(formula_of, 'formula_of'), _i(anchors, 'anchors')
+    node_map = None if node_map is None else _i(node_map, 'node_map')
+    mode_emb = _f(mode_emb.detach(), 'mode_embeddings.weight')
+    Q, D, passes = int(formula_of.shape[0]), desc.dim, len(layers)
+    if formula_of.dim() != 1 or anchors.dim() != 2 or anchors.shape[0] != Q:
+        raise ValueError('rgcn_scores_mixed: formula_of [B] and anchors [B, A]')
+    if mode_emb.dim() != 2 or mode_emb.shape[1] != D or not rgcn_mixed_supported(D, passes, readout):
+        raise ValueError('rgcn_scores_mixed: a shape the mixed launch does not cover')
+    mats = []
+    for basis, root, bias in layers:
+        basis, root = _f(basis.detach(), 'basis'), _f(root.detach(), 'root')
+        bias = None if bias is None else _f(bias.detach(), 'bias')
+        if basis.dim() != 3 or tuple(basis.shape[1:]) != (D, D) or tuple(root.shape) != (D, D) or \
+                basis.shape[0] != layers[0][0].shape[0]:
+            raise ValueError('rgcn_scores_mixed: basis [R, D, D] and root [D, D] with one R and the tables\' D')
+        mats.append((basis, root, bias))
+    arr = [(ctypes.c_void_p * passes)(*[_p(m[k]) for m in mats]) for k in range(3)]
+    wb = lib().mpqe_rgcn_mixed_workspace_bytes(desc.qid, Q, D)
+    head = (desc.qid, desc.num_formulas, desc.ptr, desc.nbytes, _p(node_map), 0 if node_map is None else node_map.shape[0],
+            _p(mode_emb), arr[0], arr[1], arr[2], int(mats[0][0].shape[0]), passes, READOUT_IDS[readout], D, _p(formula_of),
+            _p(anchors), Q)
+    return head, wb, (formula_of, anchors, node_map, mode_emb, mats, arr)
+
+
+def rgcn_embed_mixed(desc, node_map, mode_emb, layers, readout, formula_of, anchors, err=None):
+    """The R-GCN query embeddings [B, D] of queries of DIFFERENT formulas of one query type in one launch
+    (mpqe_rgcn_embed_mixed): rgcn_scores_mixed's encode launch alone."""
+    with torch.no_grad():
+        head, wb, keep = _rgcn_mixed_head(desc, node_map, mode_emb, layers, readout, formula_of, anchors)
+        dev = desc.tables[0].device
+        q_out = torch.empty((head[-1], desc.dim), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _ck(lib().mpqe_rgcn_embed_mixed(*head, _rgcn_mixed_ws(wb, dev), wb, _p(q_out), _p(err), _stream()),
+                'mpqe_rgcn_embed_mixed')
+    return q_out
+
+
+def rgcn_scores_mixed(desc, node_map, mode_emb, layers, readout, formula_of, anchors, ids, qrow, err=None, eps=1e-8):
+    """The R-GCN model's scores of queries of DIFFERENT formulas of one query type in two launches (mpqe_rgcn_fwd_mixed,
+    include/mpqe_amd.h). desc: an RgcnMixedDescriptors, kept by the caller; layers: [(basis, root, bias or None)], entry p
+    what pass p runs; formula_of [B] and anchors [B, A] int64 on the device; ids [n] / qrow [n] the pairs in forward()'s
+    layout. -> fp32 [n], bit for bit what the module path gives run by run. Inference only, under no_grad."""
+    with torch.no_grad():
+        head, wb, keep = _rgcn_mixed_head(desc, node_map, mode_emb, layers, readout, formula_of, anchors)
+        ids, qrow = _i(ids, 'ids'), _i(qrow, 'qrow')
+        n = int(ids.shape[0])
+        if ids.dim() != 1 or qrow.dim() != 1 or qrow.shape[0] != n:
+            raise ValueError('rgcn_scores_mixed: ids [n] and qrow [n]')
+        dev = desc.tables[0].device
+        scores = torch.empty((n,), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _ck(lib().mpqe_rgcn_fwd_mixed(*head, _p(ids), _p(qrow), n, float(eps), _rgcn_mixed_ws(wb, dev), wb, _p(scores),
+                                          _p(err), _stream()), 'mpqe_rgcn_fwd_mixed')
+    return scores
+
+
 # --------------------------------------------------------------------------------------------- neighbourhood encoder
 SAGE_MAX_DIM, SAGE_MAX_KEEP, SAGE_MAX_RELS = 256, _capi.SAGE_MAX_KEEP, _capi.SAGE_MAX_RELS
 

@@ -7,7 +7,7 @@ a query's negatives; evaluation.eval_auc_queries / eval_perc_queries) over test 
          mpqe_eval_auc / mpqe_eval_counts (csrc/eval.hip); one 8-byte read per AUC, one for the mean percentile
   mixed  kg.MixedQuerySet.from_sets(sets), built once outside the rounds (its time is reported as from_sets_ms): windows
          over a query type's concatenation, queries of different formulas in one scoring call (score_ids_mixed: one launch
-         for gqe; rgcn walks a window's runs), one sampler a type, the per-formula AUCs from one mpqe_eval_auc_segments
+         for gqe, two for rgcn), one sampler a type, the per-formula AUCs from one mpqe_eval_auc_segments
 
 on the `small` (480 entities) and `aifb` (2 601 entities) synthetic shapes, for both models (rgcn: RGCNEncoderDecoder, mp
 readout; gqe: QueryEncoderDecoder, bilinear paths + mean intersection). The sides run in the same process in alternating
