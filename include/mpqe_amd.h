@@ -820,6 +820,51 @@ int mpqe_gqe_fwd_mixed(const int32_t *prog_host, int64_t num_formulas, const voi
                        const int64_t *qrow, const int64_t *neg_off, int64_t n, float eps, float *scores, int32_t *err,
                        void *stream);
 
+/* Training on GQE queries of DIFFERENT formulas of one query type (csrc/gqe_mixed_train.h; added under ABI 7: entries
+ * only): the mixed forward with states and a mixed backward over the layout of mpqe_gqe_fwd_mixed.
+ *
+ * mpqe_gqe_mixed_index_build writes a second block beside the descriptor block: per formula the table INDEX of the four
+ * slots and the parameter INDEX of every site (`index`: device memory, 256-byte aligned, mpqe_gqe_mixed_index_bytes:
+ * exact, a byte less is MPQE_ERR_WORKSPACE and nothing is written; programmes that disagree on a shared int are refused
+ * before anything is written). It depends on the programmes only: the caller keeps it for the life of the formula list.
+ *
+ * mpqe_gqe_fwd_mixed_save is mpqe_gqe_fwd_mixed (every score the same BITS) and keeps in `workspace` (256-byte aligned,
+ * mpqe_gqe_mixed_train_workspace_bytes: exact, 0 for arguments out of range) what mpqe_gqe_fwd(save_states = 1) keeps,
+ * indexed by P row of the concatenation; a stretch writes its own rows only. num_tables / num_mats: the lengths of the
+ * lists the blocks were built on (they size the workspace).
+ *
+ * mpqe_gqe_bwd_mixed (the forward's operands and workspace): grad_tables_host [num_tables] / grad_mats_host [num_mats]
+ * are host arrays of device pointers, NULL = neither computed nor written; gradients are ADDED. State gradients in one
+ * launch: every dY and GE row is bit for bit what mpqe_gqe_bwd computes when the query's run is handed to it alone (a
+ * row's arithmetic depends neither on its tile row nor on its tile's other rows). Parameter gradients: the contributions
+ * (site in site order, P row) of the queries with a valid formula index are sorted stably by parameter index and summed
+ * in chunks of MPQE_GQE_MIX_GRAD_CHUNK consecutive contributions in list order (v_mfma_f32_16x16x4_f32), the chunk sums
+ * in chunk order, then added to the buffer; table rows: per (table index << 40 | row) the entries (branch sources in
+ * branch order, then the E row of every pair) in entry order, one writer per row. No float atomics: the order of every
+ * addition is a function of (formula_of, programmes) alone, the bits are the same every run and do not depend on what
+ * the workspace held. A formula index outside [0, num_formulas) -- chain form also a qrow outside [0, num_queries) --
+ * ORs MPQE_FLAG_BAD_INDEX and the query contributes no gradient anywhere; a bad id's row is zeros and gets no table
+ * gradient. num_queries == 0: MPQE_OK, no launch. Arguments are checked before any launch; a short workspace or block is
+ * MPQE_ERR_WORKSPACE and nothing is written. */
+#define MPQE_GQE_MIX_GRAD_CHUNK 64
+size_t mpqe_gqe_mixed_index_bytes(int64_t num_formulas);
+int mpqe_gqe_mixed_index_build(const int32_t *progs_host, int64_t num_formulas, int num_tables, int num_mats, int64_t dim,
+                               void *index, size_t index_bytes, void *stream);
+size_t mpqe_gqe_mixed_train_workspace_bytes(const int32_t *prog_host, int64_t num_formulas, int num_tables, int num_mats,
+                                            int64_t p_rows, int64_t n, int64_t dim);
+int mpqe_gqe_fwd_mixed_save(const int32_t *prog_host, int64_t num_formulas, const void *desc, size_t desc_bytes,
+                            int num_tables, int num_mats, const int64_t *node_map, int64_t node_map_len, int64_t dim,
+                            const int64_t *formula_of, int64_t num_queries, const int64_t *p_ids, int64_t p_rows,
+                            const int64_t *e_ids, int64_t e_rows, const int64_t *qrow, const int64_t *neg_off, int64_t n,
+                            float eps, float *scores, void *workspace, size_t workspace_bytes, int32_t *err, void *stream);
+int mpqe_gqe_bwd_mixed(const int32_t *prog_host, int64_t num_formulas, const void *desc, size_t desc_bytes,
+                       const void *index, size_t index_bytes, int num_tables, int num_mats, const int64_t *node_map,
+                       int64_t node_map_len, int64_t dim, const int64_t *formula_of, int64_t num_queries,
+                       const int64_t *p_ids, int64_t p_rows, const int64_t *e_ids, int64_t e_rows, const int64_t *qrow,
+                       const int64_t *neg_off, int64_t n, float eps, const float *grad_scores,
+                       float *const *grad_tables_host, float *const *grad_mats_host, void *workspace,
+                       size_t workspace_bytes, int32_t *err, void *stream);
+
 /* R-GCN queries of DIFFERENT formulas of one query type scored in two launches, forward only (csrc/rgcn_mixed.hip; added
  * under ABI 7: entries only). The formulas of a query type share the template, the pass count, the layers and the readout;
  * a formula's own part is one record of MPQE_RGCN_MIX_REC_INTS int32:

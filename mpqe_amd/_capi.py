@@ -115,6 +115,12 @@ PROTOTYPES = {
     'mpqe_gqe_mixed_desc_bytes': (Z, [L]),
     'mpqe_gqe_mixed_desc_build': (I, [P, L, P, P, I, P, I, L, P, Z, P]),
     'mpqe_gqe_fwd_mixed': (I, [P, L, P, Z, P, L, L, P, L, P, L, P, L, P, P, L, F, P, P, P]),
+    # training on them: the forward with states and the mixed backward (added under ABI 7: entries only)
+    'mpqe_gqe_mixed_index_bytes': (Z, [L]),
+    'mpqe_gqe_mixed_index_build': (I, [P, L, I, I, L, P, Z, P]),
+    'mpqe_gqe_mixed_train_workspace_bytes': (Z, [P, L, I, I, L, L, L]),
+    'mpqe_gqe_fwd_mixed_save': (I, [P, L, P, Z, I, I, P, L, L, P, L, P, L, P, L, P, P, L, F, P, P, Z, P, P]),
+    'mpqe_gqe_bwd_mixed': (I, [P, L, P, Z, P, Z, I, I, P, L, L, P, L, P, L, P, L, P, P, L, F, P, P, P, P, Z, P, P]),
     # R-GCN queries of different formulas of one query type in two launches (added under ABI 7: entries only)
     'mpqe_rgcn_mixed_desc_bytes': (Z, [L]),
     'mpqe_rgcn_mixed_desc_build': (I, [I, P, L, P, P, I, L, P, Z, P]),
@@ -210,6 +216,7 @@ KG_QUERY_INTS = 10                                   # mpqe_kg_sample_queries: i
 KG_SAMPLE_MAX_K, KG_SAMPLE_MAX_ROWS = 1024, 1 << 22  # mpqe_kg_sample_rows
 SAGE_MAX_KEEP, SAGE_MAX_RELS = 32, 64                # mpqe_kg_sample_neighbours, mpqe_sage_fwd
 RGCN_MIX_REC_INTS, RGCN_MIX_MAX_PASSES = 10, 4       # mpqe_rgcn_mixed_desc_build: ints of one record; mpqe_rgcn_fwd_mixed
+GQE_MIX_GRAD_CHUNK = 64                              # mpqe_gqe_bwd_mixed: contributions per chunk (MPQE_GQE_MIX_GRAD_CHUNK)
 
 
 def bind(cdll):

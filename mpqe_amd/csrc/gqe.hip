@@ -868,7 +868,31 @@ __device__ __forceinline__ long long gq_mix_formula(const GqeDev &G, const long 
     return f < 0 || f >= F ? -1 : f;
 }
 
-template <int DOT>
+// rows [0, cnt) of a tile -> rows [first, first + cnt) of a [Rp16, D] state: a stretch's own rows (the zero rows that pad
+// its tile belong to a neighbouring stretch's state)
+__device__ __forceinline__ void gq_store_rows(const float *tile, int LDX, float *g, long long first, int cnt, int D) {
+    const int per = D / 4;
+    for (int e = threadIdx.x; e < cnt * per; e += 256) {
+        const int i = e / per, c = (e % per) * 4;
+        *reinterpret_cast<f32x4 *>(g + (first + i) * D + c) = *reinterpret_cast<const f32x4 *>(tile + i * LDX + c);
+    }
+}
+
+// The training states of the mixed calls (gqe_mixed_train.h) by arithmetic, not through GqeDev's offset arrays (the mixed
+// kernels write their formula's tables into their copy of the record; an array of it indexed by a loop variable would then
+// live in scratch): G.save holds the mask of the sites the query type uses, slot k is the k-th of them, X[k] sits at
+// 2 k blk, dY[k] at (2 k + 1) blk and T[b] at (2 slots + b) blk, blk = Rp16 * D floats.
+__device__ __forceinline__ long long gq_mix_x_off(const GqeDev &G, int site) {
+    return 2ll * __builtin_popcount((unsigned)G.save & ((1u << site) - 1u)) * (G.Rp16 * G.D);
+}
+__device__ __forceinline__ long long gq_mix_dy_off(const GqeDev &G, int site) { return gq_mix_x_off(G, site) + G.Rp16 * G.D; }
+__device__ __forceinline__ long long gq_mix_t_off(const GqeDev &G, int b) {
+    return (2ll * __builtin_popcount((unsigned)G.save) + b) * (G.Rp16 * G.D);
+}
+
+// SAVE = 1 (mpqe_gqe_fwd_mixed_save): the states of mpqe_gqe_fwd(save_states = 1), by P row of the concatenation; the
+// arithmetic, and so every score's bits, is that of SAVE = 0.
+template <int DOT, int SAVE>
 __global__ __launch_bounds__(256) void gqe_fwd_mixed_kernel(GqeDev G, const GqeMixDesc *__restrict__ desc,
                                                             const long long *__restrict__ fo, long long B, int F,
                                                             float *__restrict__ scores) {
@@ -915,6 +939,7 @@ __global__ __launch_bounds__(256) void gqe_fwd_mixed_kernel(GqeDev G, const GqeM
         G.tab_rows[t] = M.tab_rows[t];
     }
     float *cur = lds, *nxt = lds + GQ_ROWS * LDX, *agg = lds + 2 * GQ_ROWS * LDX;
+    const int nrow = (int)(end - first);      // (SAVE: the stretch's own rows)
 
 #pragma unroll
     for (int b = 0; b < 3; ++b) {
@@ -924,20 +949,27 @@ __global__ __launch_bounds__(256) void gqe_fwd_mixed_kernel(GqeDev G, const GqeM
         for (int s = 0; s < G.bn[b]; ++s) {
             const int site = 3 * b + s;
             if (G.op) {
+                if (SAVE && G.op == 2) {
+                    gq_store_rows(cur, LDX, G.ws + gq_mix_x_off(G, site), first, nrow, D);
+                    __syncthreads();
+                }
                 gq_vec(cur, LDX, M.w[site], D, G.op, nullptr, first);
                 __syncthreads();
                 continue;
             }
+            if (SAVE) gq_store_rows(cur, LDX, G.ws + gq_mix_x_off(G, site), first, nrow, D);
             gq_mm(cur, nxt, M.w[site], D, LDX, M.T[site], 0);
             __syncthreads();
             float *t = cur; cur = nxt; nxt = t;
         }
         if (G.nb < 2) break;
         if (G.has_pre) {
+            if (SAVE) gq_store_rows(cur, LDX, G.ws + gq_mix_x_off(G, GQ_SITE_PRE + b), first, nrow, D);
             gq_mm(cur, nxt, M.w[GQ_SITE_PRE + b], D, LDX, 1, 1);
             __syncthreads();
             float *t = cur; cur = nxt; nxt = t;
         }
+        if (SAVE) gq_store_rows(cur, LDX, G.ws + gq_mix_t_off(G, b), first, nrow, D);
         for (int e = threadIdx.x; e < GQ_ROWS * per; e += 256) {
             const int o = (e / per) * LDX + (e % per) * 4;
             f32x4 v = *reinterpret_cast<const f32x4 *>(cur + o);
@@ -957,6 +989,7 @@ __global__ __launch_bounds__(256) void gqe_fwd_mixed_kernel(GqeDev G, const GqeM
     if (G.nb >= 2) {
         float *t = cur; cur = agg; agg = t;
         if (G.has_post) {
+            if (SAVE) gq_store_rows(cur, LDX, G.ws + gq_mix_x_off(G, GQ_SITE_POST), first, nrow, D);
             gq_mm(cur, nxt, M.w[GQ_SITE_POST], D, LDX, 1, 0);
             __syncthreads();
             t = cur; cur = nxt; nxt = t;
@@ -965,14 +998,20 @@ __global__ __launch_bounds__(256) void gqe_fwd_mixed_kernel(GqeDev G, const GqeM
     for (int s = 0; s < G.ntail; ++s) {
         const int site = GQ_SITE_TAIL + s;
         if (G.op) {
+            if (SAVE && G.op == 2) {
+                gq_store_rows(cur, LDX, G.ws + gq_mix_x_off(G, site), first, nrow, D);
+                __syncthreads();
+            }
             gq_vec(cur, LDX, M.w[site], D, G.op, nullptr, first);
             __syncthreads();
             continue;
         }
+        if (SAVE) gq_store_rows(cur, LDX, G.ws + gq_mix_x_off(G, site), first, nrow, D);
         gq_mm(cur, nxt, M.w[site], D, LDX, M.T[site], 0);
         __syncthreads();
         float *t = cur; cur = nxt; nxt = t;
     }
+    if (SAVE) gq_store_rows(cur, LDX, G.ws + G.pfin_off, first, nrow, D);
 
     for (int i = wave; i < GQ_ROWS; i += 4) {
         const long long q = first + i;
@@ -1061,45 +1100,8 @@ extern "C" int mpqe_gqe_mixed_desc_build(const int32_t *progs_host, int64_t num_
     return st;
 }
 
-extern "C" int mpqe_gqe_fwd_mixed(const int32_t *prog_host, int64_t num_formulas, const void *desc, size_t desc_bytes,
-                                  const int64_t *node_map, int64_t node_map_len, int64_t dim, const int64_t *formula_of,
-                                  int64_t num_queries, const int64_t *p_ids, int64_t p_rows, const int64_t *e_ids,
-                                  int64_t e_rows, const int64_t *qrow, const int64_t *neg_off, int64_t n, float eps,
-                                  float *scores, int32_t *err, void *stream) {
-    if (!prog_host || num_queries < 0 || node_map_len < 0) return MPQE_ERR_INVALID_ARG;
-    if (num_formulas < 1 || num_formulas >= ((int64_t)1 << 24)) return MPQE_ERR_INVALID_ARG;
-    if (!desc || (uintptr_t)desc % 256 != 0) return MPQE_ERR_INVALID_ARG;
-    if (desc_bytes < gqe_mixed_desc_size(num_formulas)) return MPQE_ERR_WORKSPACE;
-    if (num_queries == 0) return n == 0 && p_rows == 0 && e_rows == 0 ? MPQE_OK : MPQE_ERR_INVALID_ARG;
-    if (!scores || !formula_of || !p_ids || !e_ids) return MPQE_ERR_INVALID_ARG;
-    GqeHost H;
-    const int st = gqe_plan(prog_host, -1, -1, dim, p_rows, e_rows, n, &H);
-    if (st != MPQE_OK) return st;
-    GqeDev &G = H.G;
-    // chain form: one anchor per query; intersection form: one P row per query
-    if (G.form == 0 ? e_rows != num_queries : p_rows != num_queries) return MPQE_ERR_INVALID_ARG;
-    if (G.form == 0 && !qrow) return MPQE_ERR_INVALID_ARG;
-    if (G.form == 1 && G.n > G.Rp && !neg_off) return MPQE_ERR_INVALID_ARG;
-    if (G.Rp16 / GQ_ROWS >= (1ll << 27)) return MPQE_ERR_UNSUPPORTED;
-    G.node_map = (const long long *)node_map;
-    G.map_len = node_map_len;
-    G.p_ids = (const long long *)p_ids;
-    G.e_ids = (const long long *)e_ids;
-    G.qrow = (const long long *)qrow;
-    G.neg_off = (const long long *)neg_off;
-    G.eps = eps;
-    G.err = err;
-    const dim3 grid((unsigned)(G.Rp16 / GQ_ROWS * 16));
-    const GqeMixDesc *M = reinterpret_cast<const GqeMixDesc *>(desc);
-    const long long *fo = reinterpret_cast<const long long *>(formula_of);
-    if (G.dot)
-        hipLaunchKernelGGL(gqe_fwd_mixed_kernel<1>, grid, dim3(256), 0, as_stream(stream), G, M, fo, (long long)num_queries,
-                           (int)num_formulas, scores);
-    else
-        hipLaunchKernelGGL(gqe_fwd_mixed_kernel<0>, grid, dim3(256), 0, as_stream(stream), G, M, fo, (long long)num_queries,
-                           (int)num_formulas, scores);
-    return mpqe_launch_status();
-}
+// the mixed entry points: mpqe_gqe_fwd_mixed, and training on such windows (index block, forward with states, backward)
+#include "gqe_mixed_train.h"
 
 extern "C" int mpqe_gqe_bwd(const int32_t *prog_host, const float *const *tables_host, const int64_t *table_rows_host,
                             int num_tables, const int64_t *node_map, int64_t node_map_len, const float *const *mats_host,

@@ -1038,6 +1038,24 @@ class MixedQuerySet(object):
         """the host mirror of the negatives' (hard: the hard negatives') offsets, int64 [Q + 1], or None"""
         return self._offsets_host[bool(hard)]
 
+    def negative_sampler(self):
+        """NegativeSampler over the concatenation's sampled lists (sampler.sample(positions, seed, hard_negatives)). Unlike
+        QuerySet.negative_sampler() a mixed 1-chain window draws from each query's SAMPLED negatives, not from the whole
+        target mode: the target modes differ from query to query here, so there is no one list to share."""
+        from .sampling import NegativeSampler
+        if self.neg is None:
+            raise ValueError('MixedQuerySet.negative_sampler: the sets hold no sampled negatives')
+        return NegativeSampler.from_csr(self.neg, self.hard, self.index.device)
+
+    def take(self, idx):
+        """(formula_of, anchors, targets) of the positions idx (int64 on the device), by tensor indexing: no host work per
+        query. Sorted positions put equal formulas next to each other (the set is concatenated by formula): longer
+        stretches for the mixed kernels."""
+        if not torch.is_tensor(idx) or idx.dtype != torch.long or idx.dim() != 1:
+            raise TypeError('MixedQuerySet.take: idx must be an int64 vector')
+        idx = idx.to(self.formula_of.device)
+        return self.formula_of[idx], self.anchors[idx], self.targets[idx]
+
     @classmethod
     def from_sets(cls, sets):
         """{Formula: QuerySet} -> {query type: MixedQuerySet}, types and formulas in the dict's order. Tensor concatenations

@@ -740,6 +740,27 @@ def score_ids_by_runs(model, formulas, formula_of_host, anchors, targets, neg=No
     return out
 
 
+def margin_loss_ids_by_runs(model, formulas, formula_of, anchors, targets, neg_ids, margin=1):
+    """QueryEncoderDecoder.margin_loss_ids_mixed without the mixed launch: every run of equal formula through the
+    differentiable per-formula route (model._score_ids: ops.gqe_scores where the fused kernel covers the formula, the
+    composed ops otherwise), the scores put back in forward()'s layout of the whole, one hinge. Its fallback, its oracle
+    and the other side of tools/gqe_mixed_train_bench.py (one read of formula_of)."""
+    device = model._device()
+    B = int(targets.shape[0])
+    anchors, targets, neg_ids = anchors.to(device), targets.to(device), neg_ids.to(device).reshape(-1)
+    pos, negs = [], []
+    for f, lo, hi in formula_runs(formula_of.cpu().numpy()):
+        if not 0 <= f < len(formulas):
+            raise IndexError('formula index %d outside the %d formulas' % (f, len(formulas)))
+        off = torch.arange(hi - lo + 1, dtype=torch.long, device=device)
+        s = model._score_ids(formulas[f], anchors[lo:hi], targets[lo:hi], (neg_ids[lo:hi], off))
+        pos.append(s[:hi - lo])
+        negs.append(s[hi - lo:])
+    model._check()
+    scores = torch.cat(pos + negs)
+    return ops.hinge(scores[:B], scores[B:], margin)
+
+
 def gqe_plan(formula):
     """(form, [(anchor slot or None = the target side, mode, [(relation, transposed)])], intersection mode or None,
     [(relation, transposed)] after the intersection, mode of the other side): model.py:78-116 as data."""
@@ -945,31 +966,35 @@ class QueryEncoderDecoder(nn.Module, _EntityRanking):
         [B + total] on the device in forward()'s layout, under no_grad. The integer operands of ops.gqe_scores are put
         together with tensor ops -- the launch is _fused_scores', so the bits are forward()'s; where the fused kernel does
         not cover the model the composed path runs on the same tensors. No id and no score visits the host."""
-        plan = self._plan(formula)
-        form, branches, imode, tail, emode = plan
         with torch.no_grad():
-            device = self._device()
-            anchors, targets, neg_ids, q_row = _device_ids(anchors, targets, neg, device, len(formula.anchor_modes))
-            B = int(targets.shape[0])
-            tnodes = targets if neg_ids is None else torch.cat([targets, neg_ids])
-            n = int(tnodes.shape[0])
-            if self._fused_ok(plan):
-                prog, modes, mats = self._programme(plan)
-                qrow = neg_off = None
-                if form == 0:
-                    p_ids, e_ids = tnodes.reshape(1, n), anchors[:, 0].contiguous()
-                    qrow = q_row if q_row is not None else torch.arange(B, dtype=torch.long, device=device)
-                else:
-                    slots = [slot for slot, _, _ in branches if slot is not None]
-                    p_ids, e_ids = anchors[:, slots].t().contiguous(), tnodes
-                    if n > B:
-                        neg_off = neg[1].to(device).contiguous()
-                scores = ops.gqe_scores(prog, [self.enc.table(m) for m in modes], mats, self.enc.node_maps, p_ids, e_ids,
-                                        qrow, neg_off, n, self._error_word(device))
-            else:
-                scores = self._composed_ids(formula, anchors, tnodes, q_row, plan)
+            scores = self._score_ids(formula, anchors, targets, neg)
             self._check()
         return scores
+
+    def _score_ids(self, formula, anchors, targets, neg=None):
+        """score_ids' scores without its no_grad and its check: differentiable w.r.t. the parameters (ops.gqe_scores where
+        the fused kernel covers the formula, the composed ops otherwise)"""
+        plan = self._plan(formula)
+        form, branches, imode, tail, emode = plan
+        device = self._device()
+        anchors, targets, neg_ids, q_row = _device_ids(anchors, targets, neg, device, len(formula.anchor_modes))
+        B = int(targets.shape[0])
+        tnodes = targets if neg_ids is None else torch.cat([targets, neg_ids])
+        n = int(tnodes.shape[0])
+        if not self._fused_ok(plan):
+            return self._composed_ids(formula, anchors, tnodes, q_row, plan)
+        prog, modes, mats = self._programme(plan)
+        qrow = neg_off = None
+        if form == 0:
+            p_ids, e_ids = tnodes.reshape(1, n), anchors[:, 0].contiguous()
+            qrow = q_row if q_row is not None else torch.arange(B, dtype=torch.long, device=device)
+        else:
+            slots = [slot for slot, _, _ in branches if slot is not None]
+            p_ids, e_ids = anchors[:, slots].t().contiguous(), tnodes
+            if n > B:
+                neg_off = neg[1].to(device).contiguous()
+        return ops.gqe_scores(prog, [self.enc.table(m) for m in modes], mats, self.enc.node_maps, p_ids, e_ids, qrow, neg_off,
+                              n, self._error_word(device))
 
     def _mixed_descriptors(self, formulas):
         """(the kept ops.GqeMixedDescriptors of `formulas`, or None where the fused kernel does not cover every formula;
@@ -995,6 +1020,8 @@ class QueryEncoderDecoder(nn.Module, _EntityRanking):
             shared = ([], [], {})
             progs = np.stack([self._programme(plan, shared)[0] for plan in plans])
             desc = ops.GqeMixedDescriptors(progs, [self.enc.table(m) for m in shared[0]], shared[1])
+            # (the live tensors the block's addresses are of: the differentiable inputs of margin_loss_ids_mixed)
+            desc.live = ([self.enc.table(m) for m in shared[0]], list(shared[1]))
         kept.pop(id(formulas), None)
         while len(kept) >= self.MIXED_KEPT:
             kept.pop(next(iter(kept)))
@@ -1035,6 +1062,41 @@ class QueryEncoderDecoder(nn.Module, _EntityRanking):
                                           self._error_word(device))
             self._check()
         return scores
+
+    def margin_loss_ids_mixed(self, formulas, formula_of, anchors, targets, neg_ids, margin=1):
+        """margin_loss() for B queries of DIFFERENT formulas of one query type with ids on the device (kg.MixedQuerySet.take):
+        `formulas` a sequence of Formula of that type (pass the SAME object every time: _mixed_descriptors is keyed on it),
+        formula_of [B], anchors [B, A], targets [B] and neg_ids [B] -- one negative per query, as the reference's
+        margin_loss draws -- int64. ONE differentiable mixed scoring call over targets ++ neg_ids
+        (ops.gqe_scores_mixed_grad: mpqe_gqe_fwd_mixed_save, and mpqe_gqe_bwd_mixed in backward()), then ops.hinge: the
+        scalar loss the reference's margin_loss gives for those queries and negatives. Where the fused kernel does not
+        cover every formula (fused = False, a D it does not take, foreign decoders) the runs of equal formula are walked
+        through the per-formula route (margin_loss_ids_by_runs)."""
+        if not torch.is_tensor(formula_of) or formula_of.dtype != torch.long or formula_of.dim() != 1:
+            raise TypeError('margin_loss_ids_mixed: formula_of must be an int64 vector')
+        desc, (form, branches, imode, tail, emode) = self._mixed_descriptors(formulas)
+        if desc is None:
+            return margin_loss_ids_by_runs(self, formulas, formula_of, anchors, targets, neg_ids, margin)
+        device = self._device()
+        B = int(targets.shape[0])
+        rows = torch.arange(B + 1, dtype=torch.long, device=device)
+        neg_ids = neg_ids.to(device).reshape(-1)
+        if formula_of.shape[0] != B or neg_ids.shape[0] != B:
+            raise ValueError('margin_loss_ids_mixed: formula_of [B], neg_ids [B]')
+        anchors, targets, neg_ids, _ = _device_ids(anchors, targets, (neg_ids, rows), device, len(formulas[0].anchor_modes))
+        formula_of = formula_of.to(device).contiguous()
+        tnodes = torch.cat([targets, neg_ids])
+        qrow = neg_off = None
+        if form == 0:
+            p_ids, e_ids = tnodes.reshape(1, 2 * B), anchors[:, 0].contiguous()
+            qrow = torch.cat([rows[:B], rows[:B]])
+        else:
+            slots = [slot for slot, _, _ in branches if slot is not None]
+            p_ids, e_ids, neg_off = anchors[:, slots].t().contiguous(), tnodes, rows
+        scores = ops.gqe_scores_mixed_grad(desc, desc.live[0], desc.live[1], self.enc.node_maps, formula_of, p_ids, e_ids,
+                                           qrow, neg_off, 2 * B, self._error_word(device))
+        self._check()
+        return ops.hinge(scores[:B], scores[B:], margin)
 
     def _mixed_by_runs(self, formulas, formula_of, anchors, targets, neg):
         """score_ids_mixed without the mixed launch: every run of equal formula through score_ids, put back in forward()'s

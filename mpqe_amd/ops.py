@@ -919,6 +919,14 @@ class GqeMixedDescriptors(object):
         with torch.cuda.device(dev):
             _ck(L.mpqe_gqe_mixed_desc_build(progs.ctypes.data, self.num_formulas, tab_arr, rows_arr, len(tables), mat_arr,
                                             len(mats), D, self.ptr, self.nbytes, _stream()), 'mpqe_gqe_mixed_desc_build')
+            # the index block of the mixed backward (mpqe_gqe_mixed_index_build): the table and parameter INDEX of every
+            # slot and site; it depends on the programmes alone
+            self.index_nbytes = L.mpqe_gqe_mixed_index_bytes(self.num_formulas)
+            self.index_buffer = torch.empty(self.index_nbytes + 256, dtype=torch.uint8, device=dev)
+            self.index_ptr = _capi._align256(self.index_buffer.data_ptr())
+            _ck(L.mpqe_gqe_mixed_index_build(progs.ctypes.data, self.num_formulas, len(tables), len(mats), D, self.index_ptr,
+                                             self.index_nbytes, _stream()), 'mpqe_gqe_mixed_index_build')
+        self.addresses = tuple(t.data_ptr() for t in tables + mats)
 
 
 def gqe_scores_mixed(desc, node_map, formula_of, p_ids, e_ids, qrow, neg_off, n, err=None, eps=1e-8):
@@ -941,6 +949,84 @@ def gqe_scores_mixed(desc, node_map, formula_of, p_ids, e_ids, qrow, neg_off, n,
                                      int(p_ids.shape[1]), _p(e_ids), int(e_ids.shape[0]), _p(qrow), _p(neg_off), n,
                                      float(eps), _p(scores), _p(err), _stream()), 'mpqe_gqe_fwd_mixed')
     return scores
+
+
+class _GqeScoresMixed(torch.autograd.Function):
+    """One mpqe_gqe_fwd_mixed_save (mpqe_gqe_fwd_mixed when nothing needs a gradient) per forward, one mpqe_gqe_bwd_mixed per
+    backward; the differentiable inputs are the descriptor's WHOLE table and parameter lists (`params` = tables, then
+    parameters)."""
+
+    @staticmethod
+    def forward(ctx, spec, *params):
+        desc, node_map, formula_of, p_ids, e_ids, qrow, neg_off, n, err, eps = spec
+        T, M = len(desc.tables), len(desc.mats)
+        if len(params) != T + M or tuple(_f(p, 'parameter').data_ptr() for p in params) != desc.addresses:
+            raise ValueError('gqe_scores_mixed_grad: the tables and parameters are not the ones the descriptor block was '
+                             'built on (their addresses differ): build a new GqeMixedDescriptors')
+        B = int(formula_of.shape[0])
+        dev = desc.tables[0].device
+        save = any(ctx.needs_input_grad[1:])
+        L = lib()
+        scores = torch.empty((n,), dtype=torch.float32, device=dev)
+        window = (_p(node_map), 0 if node_map is None else node_map.shape[0], desc.dim, _p(formula_of), B, _p(p_ids),
+                  int(p_ids.shape[1]), _p(e_ids), int(e_ids.shape[0]), _p(qrow), _p(neg_off), n, eps)
+        head = (desc.progs.ctypes.data, desc.num_formulas, desc.ptr, desc.nbytes)
+        ws, wp, wb = None, None, 0
+        with torch.cuda.device(dev):
+            if save and B > 0:
+                wb = L.mpqe_gqe_mixed_train_workspace_bytes(desc.progs.ctypes.data, desc.num_formulas, T, M,
+                                                            int(p_ids.shape[1]), n, desc.dim)
+                if wb == 0:
+                    raise ValueError('gqe_scores_mixed_grad: shape outside what the kernel covers')
+                ws = _ws(wb + 256, dev)
+                wp = _capi._align256(ws.data_ptr())
+                _ck(L.mpqe_gqe_fwd_mixed_save(*(head + (T, M) + window + (_p(scores), wp, wb, _p(err), _stream()))),
+                    'mpqe_gqe_fwd_mixed_save')
+            else:
+                _ck(L.mpqe_gqe_fwd_mixed(*(head + window + (_p(scores), _p(err), _stream()))), 'mpqe_gqe_fwd_mixed')
+        ctx.call = (desc, head, window, wp, wb, err, (ws, node_map, formula_of, p_ids, e_ids, qrow, neg_off))
+        ctx.shapes = [tuple(p.shape) for p in params]
+        return scores
+
+    @staticmethod
+    def backward(ctx, gs):
+        import ctypes
+        desc, head, window, wp, wb, err, _keep = ctx.call
+        T, M = len(desc.tables), len(desc.mats)
+        gs = _f(gs.contiguous(), 'grad_scores')
+        dev = gs.device
+        want = ctx.needs_input_grad[1:]
+        # one zero-filled allocation for every wanted gradient, handed out as views (16-byte aligned: every size is a
+        # multiple of D >= 16 floats)
+        sizes = [int(np.prod(sh)) if w else 0 for sh, w in zip(ctx.shapes, want)]
+        flat = torch.zeros(sum(sizes), dtype=torch.float32, device=dev)
+        grads, at = [], 0
+        for sh, w, k in zip(ctx.shapes, want, sizes):
+            grads.append(flat[at:at + k].view(sh) if w else None)
+            at += k
+        if wp is not None:
+            gt = (ctypes.c_void_p * T)(*[_p(g) for g in grads[:T]])
+            gm = (ctypes.c_void_p * max(M, 1))(*[_p(g) for g in grads[T:]])
+            with torch.cuda.device(dev):
+                _ck(lib().mpqe_gqe_bwd_mixed(*(head + (desc.index_ptr, desc.index_nbytes, T, M) + window +
+                                               (_p(gs), gt, gm, wp, wb, _p(err), _stream()))), 'mpqe_gqe_bwd_mixed')
+        return (None,) + tuple(grads)
+
+
+def gqe_scores_mixed_grad(desc, tables, mats, node_map, formula_of, p_ids, e_ids, qrow, neg_off, n, err=None, eps=1e-8):
+    """gqe_scores_mixed, differentiable w.r.t. the descriptor's WHOLE table and parameter lists (`tables`, `mats`: the
+    tensors `desc` was built on -- their data_ptr()s are checked, ValueError otherwise): mpqe_gqe_fwd_mixed_save when any
+    of them needs a gradient (mpqe_gqe_fwd_mixed otherwise) and one mpqe_gqe_bwd_mixed in the backward
+    (include/mpqe_amd.h). The scores are gqe_scores_mixed's bits. All gradients of a call are views of ONE zero-filled
+    allocation; a parameter no query of the window names gets zeros, not None."""
+    formula_of, p_ids, e_ids = _i(formula_of, 'formula_of'), _i(p_ids, 'p_ids'), _i(e_ids, 'e_ids')
+    node_map = None if node_map is None else _i(node_map, 'node_map')
+    qrow = None if qrow is None else _i(qrow, 'qrow')
+    neg_off = None if neg_off is None else _i(neg_off, 'neg_off')
+    if formula_of.dim() != 1 or p_ids.dim() != 2 or e_ids.dim() != 1:
+        raise ValueError('gqe_scores_mixed_grad: formula_of [B], p_ids [branches, p_rows], e_ids [e_rows]')
+    spec = (desc, node_map, formula_of, p_ids, e_ids, qrow, neg_off, int(n), err, float(eps))
+    return _GqeScoresMixed.apply(spec, *(list(tables) + list(mats)))
 
 
 # --------------------------------------------------------------------------------------------- R-GCN, mixed formulas

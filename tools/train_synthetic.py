@@ -94,6 +94,7 @@ def device_queries(args, schema, adj, node_maps, device):
     train_index.check()
     torch.cuda.synchronize()
     args.query_sets, args.sampling_seconds = {}, time.perf_counter() - t0
+    args.train_sets = train_sets
     train, test = {qt: [] for qt in types}, {qt: [] for qt in types}
     for f, qs in train_sets.items():
         args.query_sets[(f.query_type, len(train[f.query_type]))] = qs
@@ -191,6 +192,10 @@ def main(argv=None):
     ap.add_argument('--mixed-eval', action='store_true',
                     help='with --device-eval: group the test sets by query type (kg.MixedQuerySet) and score queries of '
                          'different formulas per call -- one launch a window under --model gqe; other sampled negatives')
+    ap.add_argument('--mixed-train', action='store_true',
+                    help='with --device-queries --model gqe: train on windows of one query type whatever the formulas '
+                         '(kg.MixedQuerySet.take + QueryEncoderDecoder.margin_loss_ids_mixed: one mixed forward and one mixed '
+                         'backward per window) instead of one formula per batch')
     ap.add_argument('--depth', type=int, default=0, choices=[0, 1, 2],
                     help='entity encoder (the reference\'s --depth): 0 the embedding lookup (everything above), 1 / 2 the '
                          'neighbourhood-aggregating Encoder of utils.get_encoder under either --model, trained through '
@@ -202,6 +207,8 @@ def main(argv=None):
         ap.error('--device-eval needs --device-queries and the embedding-lookup encoder (--depth 0)')
     if args.mixed_eval and not args.device_eval:
         ap.error('--mixed-eval needs --device-eval')
+    if args.mixed_train and (not args.device_queries or args.model != 'gqe' or args.depth):
+        ap.error('--mixed-train needs --device-queries --model gqe (and the embedding-lookup encoder, --depth 0)')
     if args.depth:
         out = run_depth(args)
     elif args.model == 'gqe':
@@ -486,6 +493,29 @@ def run_gqe(args):
             pos[fi] = lo + args.batch_size
             yield f, qs[lo:lo + args.batch_size]
     iterators = {qt: batches(qt) for qt in query_types}
+    margin_loss = lambda batch, hard: model.margin_loss(*batch, hard_negatives=hard)       # noqa: E731
+    if getattr(args, 'mixed_train', False):
+        # --mixed-train: a batch is batch_size positions of a query type's concatenation, whatever their formulas; sorted,
+        # so that equal formulas sit next to each other (longer stretches, fewer matrix reads)
+        from mpqe_amd.kg import MixedQuerySet
+        mixed = MixedQuerySet.from_sets(args.train_sets)
+        samplers = {qt: ms.negative_sampler() for qt, ms in mixed.items()}
+        gen = torch.Generator().manual_seed(args.seed + 13)
+        draws = [0]
+
+        def positions(qt):
+            while True:
+                idx = torch.randint(len(mixed[qt]), (args.batch_size,), generator=gen, dtype=torch.long)
+                yield qt, torch.sort(idx).values.to(device)
+
+        def margin_loss(batch, hard):
+            qt, idx = batch
+            ms = mixed[qt]
+            draws[0] += 1
+            neg = samplers[qt].sample(idx, args.seed + 100000 + draws[0], hard_negatives=hard)
+            formula_of, anchors, targets = ms.take(idx)
+            return model.margin_loss_ids_mixed(ms.formulas, formula_of, anchors, targets, neg)
+        iterators = {qt: positions(qt) for qt in query_types}
     with torch.no_grad():
         auc0, _ = evaluation.eval_auc_queries(model_queries(args, tq), model, batch_size=128, seed=0)
     rank0 = evaluation.eval_rank_queries(tq, model.eval(), batch_size=128, ks=(10,), known_answers=known)
@@ -493,8 +523,10 @@ def run_gqe(args):
     opt = optim.Adam(model.parameters(), lr=args.lr)
     random.seed(args.seed + 12)
     t0 = time.perf_counter()
-    losses = _reference_loop(model, iterators, query_types, opt, args.steps,
-                             lambda batch, hard: model.margin_loss(*batch, hard_negatives=hard))
+    losses = _reference_loop(model, iterators, query_types, opt, args.steps, margin_loss)
+    if getattr(args, 'mixed_train', False):
+        for sampler in samplers.values():
+            sampler.check()
     torch.cuda.synchronize()
     train_s = time.perf_counter() - t0
     with torch.no_grad():
@@ -509,6 +541,8 @@ def run_gqe(args):
     if getattr(args, 'device_eval', False):
         with torch.no_grad():
             out['perc_after'] = float(evaluation.eval_perc_queries(eval_sets(args), model, batch_size=128))
+    if getattr(args, 'mixed_train', False):
+        out['mixed_train'] = True
     return out
 
 
