@@ -921,6 +921,77 @@ int mpqe_rgcn_fwd_mixed(int query_type, int64_t num_formulas, const void *desc, 
                         const int64_t *ids, const int64_t *qrow, int64_t n, float eps, void *workspace,
                         size_t workspace_bytes, float *scores, int32_t *err, void *stream);
 
+/* Training on R-GCN queries of DIFFERENT formulas of one query type (csrc/rgcn_mixed_train.h; added under ABI 7: entries
+ * only): the mixed forward with states and a mixed backward. Operands as in mpqe_rgcn_fwd_mixed unless said otherwise.
+ *
+ * mpqe_rgcn_mixed_index_build writes a second block beside the descriptor block from the same records: per formula the
+ * table INDEX of every anchor slot and of the target mode, the relation of every edge and the mode-embedding row of every
+ * variable slot (`index`: device memory, 256-byte aligned, mpqe_rgcn_mixed_index_bytes: exact, 0 for num_formulas out of
+ * range, a byte less is MPQE_ERR_WORKSPACE and nothing is written; a negative field read: MPQE_ERR_INVALID_ARG). It
+ * depends on the records only: the caller keeps it for the life of the formula list.
+ *
+ * Sizes of a training call: num_tables (the table list the descriptor block was built on), mode_emb_rows, num_layers
+ * (distinct parameter sets, 1 .. 4) and n, the pairs: ids [n] = num_queries targets, then the negatives in CSR order under
+ * neg_off [num_queries + 1], n = num_queries + neg_off[num_queries] (forward()'s layout), or n = 0: nothing is scored.
+ * workspace: 256-byte aligned, mpqe_rgcn_mixed_train_workspace_bytes -- exact; 0: arguments out of range.
+ *
+ * mpqe_rgcn_fwd_mixed_save is mpqe_rgcn_fwd_mixed with the pair layout fixed so (it takes neg_off, not qrow): every score
+ * is the same BITS mpqe_rgcn_fwd_mixed writes for the equivalent qrow. It keeps in the workspace every pass's node states
+ * (passes + 1 buffers [num_queries * N, dim]) and the query embeddings; q_out, when not NULL, receives a copy of those
+ * [num_queries, dim]. Under the target-message readout the last pass still computes the target slot alone; the backward
+ * never reads the slots nobody wrote. A negative whose offsets do not name a query ORs MPQE_FLAG_BAD_INDEX and scores 0.
+ *
+ * mpqe_rgcn_bwd_mixed takes the forward's operands and workspace, plus layer_of_pass_host [passes] (which of the
+ * num_layers parameter sets a pass ran, each in [0, num_layers)), grad_scores [n] OR grad_q [num_queries, dim] -- exactly
+ * one non-NULL; with grad_q the score phase is skipped and ids / neg_off are not read -- and the gradient buffers:
+ * grad_tables_host [num_tables], grad_mode_emb [mode_emb_rows, dim], grad_basis_host / grad_root_host / grad_bias_host
+ * [num_layers] (host arrays of device pointers; the arrays themselves may be NULL). NULL = neither computed nor written;
+ * gradients are ADDED. Every buffer 16-byte aligned.
+ *   states     one launch, a workgroup per stretch of one formula, found as the forward finds it: the cosine backward of
+ *              the stretch's pairs, one wave per pair, a query's terms summed in the order target, then its negatives in
+ *              CSR order; the readout backward (max: the lowest node on ties, from the saved last state); per pass from the
+ *              last the ReLU mask from the saved state and the layer's transposed product, on the stretch alone.
+ *   parameters the contributions (pass, slot, query) -- the slots the template's edges in edge order, then the node slots
+ *              for the root term; x_p[query, src] (x) g_{p+1}[query, dst] -- carry the key layer_of_pass[p] *
+ *              (num_relations + 1) + relation (num_relations: the root); sorted stably by key, cut into chunks of
+ *              MPQE_RGCN_MIX_GRAD_CHUNK consecutive contributions, a chunk summed in list order from a zero accumulator
+ *              (v_mfma_f32_16x16x4_f32), the chunk sums added in chunk order, the total added to the buffer by the one
+ *              workgroup that owns the strip. bias: the column sums of the g rows of the layer's root contributions, mode
+ *              embeddings: of the variable slots' (slot, query) rows per row, both in the same chunked order.
+ *   table rows per (table index << 40 | row) the entries -- the anchors in (slot, query) order, then the pairs in pair
+ *              order -- summed in entry order through the l2-norm backward, one writer per row.
+ *   No float atomics: the order of every addition is a function of (formula_of, records, neg_off) alone, the bits are the
+ *   same every run and do not depend on what the workspace held beyond what the save call wrote.
+ *   bad input  a formula index outside [0, num_formulas) ORs MPQE_FLAG_BAD_INDEX, a descriptor's relation outside
+ *              [0, num_relations) MPQE_FLAG_BAD_RELATION (a stretch whose neg_off entries do not ascend inside
+ *              [0, n - num_queries]: MPQE_FLAG_BAD_INDEX): the query contributes NO gradient anywhere. A bad id's row is
+ *              zeros and gets no table gradient. The other queries' bits are unaffected.
+ *   shapes     dim a multiple of 16 in [16, 256], 1 <= passes <= 4, the three readouts, num_layers <= 4, n < 2^31:
+ *              MPQE_ERR_UNSUPPORTED otherwise, before any launch. num_queries == 0 (then n == 0): MPQE_OK, no launch.
+ *   Arguments are checked before any launch; a short block or workspace is MPQE_ERR_WORKSPACE and nothing is written. */
+#define MPQE_RGCN_MIX_GRAD_CHUNK 64
+size_t mpqe_rgcn_mixed_index_bytes(int64_t num_formulas);
+int mpqe_rgcn_mixed_index_build(int query_type, const int32_t *recs_host, int64_t num_formulas, void *index,
+                                size_t index_bytes, void *stream);
+size_t mpqe_rgcn_mixed_train_workspace_bytes(int query_type, int64_t num_queries, int64_t n, int64_t dim, int passes,
+                                             int64_t num_relations, int num_tables, int64_t mode_emb_rows, int num_layers);
+int mpqe_rgcn_fwd_mixed_save(int query_type, int64_t num_formulas, const void *desc, size_t desc_bytes,
+                             const int64_t *node_map, int64_t node_map_len, const float *mode_emb,
+                             const float *const *basis_host, const float *const *root_host, const float *const *bias_host,
+                             int64_t num_relations, int passes, int readout, int64_t dim, const int64_t *formula_of,
+                             const int64_t *anchors, int64_t num_queries, const int64_t *ids, const int64_t *neg_off,
+                             int64_t n, float eps, int num_tables, int64_t mode_emb_rows, int num_layers, void *workspace,
+                             size_t workspace_bytes, float *scores, float *q_out, int32_t *err, void *stream);
+int mpqe_rgcn_bwd_mixed(int query_type, int64_t num_formulas, const void *desc, size_t desc_bytes, const void *index,
+                        size_t index_bytes, const int64_t *node_map, int64_t node_map_len, const float *mode_emb,
+                        const float *const *basis_host, const float *const *root_host, const float *const *bias_host,
+                        int64_t num_relations, int passes, int readout, int64_t dim, const int64_t *formula_of,
+                        const int64_t *anchors, int64_t num_queries, const int64_t *ids, const int64_t *neg_off, int64_t n,
+                        float eps, int num_tables, int64_t mode_emb_rows, int num_layers, const int *layer_of_pass_host,
+                        const float *grad_scores, const float *grad_q, float *const *grad_tables_host,
+                        float *grad_mode_emb, float *const *grad_basis_host, float *const *grad_root_host,
+                        float *const *grad_bias_host, void *workspace, size_t workspace_bytes, int32_t *err, void *stream);
+
 /* ---- exact answers of a conjunctive query on the knowledge graph (csrc/kg.hip) ------------------------------------
  * reference: Graph.get_metapath_neighs graph.py:459-473 (the answer set of a chain) and Graph.get_negative_samples
  * graph.py:263-314 (intersection / union of the branch sets; negatives = full set - answers, hard negatives = union -

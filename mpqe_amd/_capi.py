@@ -127,6 +127,13 @@ PROTOTYPES = {
     'mpqe_rgcn_mixed_workspace_bytes': (Z, [I, L, L]),
     'mpqe_rgcn_embed_mixed': (I, [I, L, P, Z, P, L, P, P, P, P, L, I, I, L, P, P, L, P, Z, P, P, P]),
     'mpqe_rgcn_fwd_mixed': (I, [I, L, P, Z, P, L, P, P, P, P, L, I, I, L, P, P, L, P, P, L, F, P, Z, P, P, P]),
+    'mpqe_rgcn_mixed_index_bytes': (Z, [L]),
+    'mpqe_rgcn_mixed_index_build': (I, [I, P, L, P, Z, P]),
+    'mpqe_rgcn_mixed_train_workspace_bytes': (Z, [I, L, L, L, I, L, I, L, I]),
+    'mpqe_rgcn_fwd_mixed_save': (I, [I, L, P, Z, P, L, P, P, P, P, L, I, I, L, P, P, L, P, P, L, F, I, L, I, P, Z, P, P, P,
+                                     P]),
+    'mpqe_rgcn_bwd_mixed': (I, [I, L, P, Z, P, Z, P, L, P, P, P, P, L, I, I, L, P, P, L, P, P, L, F, I, L, I, P, P, P, P, P, P,
+                                P, P, P, Z, P, P]),
     'mpqe_kg_workspace_bytes': (Z, [P, L, P, I, I]),
     'mpqe_kg_answers': (I, [P, P, P, P, I, P, I, P, L, P, P, P, I, P, Z, P, P]),
     'mpqe_kg_rows': (I, [P, L, L, P, I, P, P, L, P, P]),
@@ -217,6 +224,7 @@ KG_SAMPLE_MAX_K, KG_SAMPLE_MAX_ROWS = 1024, 1 << 22  # mpqe_kg_sample_rows
 SAGE_MAX_KEEP, SAGE_MAX_RELS = 32, 64                # mpqe_kg_sample_neighbours, mpqe_sage_fwd
 RGCN_MIX_REC_INTS, RGCN_MIX_MAX_PASSES = 10, 4       # mpqe_rgcn_mixed_desc_build: ints of one record; mpqe_rgcn_fwd_mixed
 GQE_MIX_GRAD_CHUNK = 64                              # mpqe_gqe_bwd_mixed: contributions per chunk (MPQE_GQE_MIX_GRAD_CHUNK)
+RGCN_MIX_GRAD_CHUNK = 64                             # mpqe_rgcn_bwd_mixed: the same (MPQE_RGCN_MIX_GRAD_CHUNK)
 
 
 def bind(cdll):

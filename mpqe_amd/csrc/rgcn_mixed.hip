@@ -1,5 +1,5 @@
-// R-GCN scores of queries of DIFFERENT formulas of one query type in two launches, forward only (include/mpqe_amd.h:
-// mpqe_rgcn_embed_mixed / mpqe_rgcn_fwd_mixed). The formulas of a query type share the template (N, E, src / dst, the
+// R-GCN scores of queries of DIFFERENT formulas of one query type in two launches (include/mpqe_amd.h:
+// mpqe_rgcn_embed_mixed / mpqe_rgcn_fwd_mixed; the forward with states and the backward: rgcn_mixed_train.h). The formulas of a query type share the template (N, E, src / dst, the
 // variable slots), the pass count, the layers and the readout; a formula's own part -- the relation of every template
 // edge, the entity table of every anchor slot, the mode-embedding row of every variable slot, the target mode's table --
 // is one RgcnMixDesc in device memory (mpqe_rgcn_mixed_desc_build; addresses and indices only, kept by the caller).
@@ -70,7 +70,9 @@ __device__ __forceinline__ long long rm_lookup_row(const long long *node_map, lo
     return row;
 }
 
-template <int MODE>
+// SAVE (mpqe_rgcn_fwd_mixed_save, rgcn_mixed_train.h): every pass keeps its state -- pass p reads S[p] and writes S[p + 1],
+// S[p] = s0 + p * (s1 - s0) -- in place of the two buffers taking turns.
+template <int MODE, int SAVE = 0>
 __global__ __launch_bounds__(256) void rgcn_mixed_encode_kernel(RgcnMixArgs G, RgcnMixLayers W) {
     __shared__ __attribute__((aligned(16))) float smem[GT_SMEM_FLOATS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -151,7 +153,13 @@ __global__ __launch_bounds__(256) void rgcn_mixed_encode_kernel(RgcnMixArgs G, R
                 tmpl_fwd_tile<MODE>(tp, (long long)Bs, cur, basis, root, bias, D, D, last ? 0 : 1, nxt, n, 0ll, n0, smem);
         }
         __syncthreads();
-        float *t = cur; cur = nxt; nxt = t;
+        if (SAVE) {
+            const long long stride = G.s1 - G.s0;
+            cur = nxt;
+            nxt = nxt + stride;
+        } else {
+            float *t = cur; cur = nxt; nxt = t;
+        }
     }
 
     // readout: readout_fwd_kernel's expressions (the sum in node order)
@@ -397,3 +405,6 @@ extern "C" int mpqe_rgcn_fwd_mixed(int query_type, int64_t num_formulas, const v
                        scores);
     return mpqe_launch_status();
 }
+
+// the mixed forward with states and the mixed backward
+#include "rgcn_mixed_train.h"

@@ -445,14 +445,19 @@ class RGCNEncoderDecoder(nn.Module, _EntityRanking):
         module path's ops take the rest as tensors -- one lookup-and-normalise and one ragged cosine over targets and
         negatives together, each row computed as forward()'s module path computes it."""
         with torch.no_grad():
-            device = self._device()
-            anchors, targets, neg_ids, q_row = _device_ids(anchors, targets, neg, device, len(formula.anchor_modes))
-            var_ids, q_graphs = RGCNQueryDataset.get_query_template(formula, anchors.shape[0], self.rel_ids, self.mode_ids)
-            out = self.encode(formula, None, anchors, var_ids, q_graphs)
-            ids = targets if neg_ids is None else torch.cat([targets, neg_ids])
-            scores = ops.cosine(out, self._target_embeds(ids, formula.target_mode, device), q_row=q_row)
+            scores = self._score_ids(formula, anchors, targets, neg)
             self._check()
         return scores
+
+    def _score_ids(self, formula, anchors, targets, neg=None):
+        """score_ids' body with gradients enabled (the module path's autograd ops): the differentiable per-formula route
+        of margin_loss_ids_by_runs. The caller checks the error word."""
+        device = self._device()
+        anchors, targets, neg_ids, q_row = _device_ids(anchors, targets, neg, device, len(formula.anchor_modes))
+        var_ids, q_graphs = RGCNQueryDataset.get_query_template(formula, anchors.shape[0], self.rel_ids, self.mode_ids)
+        out = self.encode(formula, None, anchors, var_ids, q_graphs)
+        ids = targets if neg_ids is None else torch.cat([targets, neg_ids])
+        return ops.cosine(out, self._target_embeds(ids, formula.target_mode, device), q_row=q_row)
 
     # ------------------------------------------------------------------ queries of different formulas at once
     MIXED_KEPT = 16         # score_ids_mixed: descriptor blocks kept, one per `formulas` sequence
@@ -524,6 +529,8 @@ class RGCNEncoderDecoder(nn.Module, _EntityRanking):
                 recs[k, 9] = table_of(f.target_mode)
             desc = ops.RgcnMixedDescriptors(formulas[0].query_type, recs, [self.enc.table(m) for m in modes],
                                             self.mode_embeddings.weight.shape[0])
+            # (the live tensors the block's addresses are of: the differentiable inputs of margin_loss_ids_mixed)
+            desc.live = [self.enc.table(m) for m in modes]
         kept.pop(id(formulas), None)
         while len(kept) >= self.MIXED_KEPT:
             kept.pop(next(iter(kept)))
@@ -559,6 +566,48 @@ class RGCNEncoderDecoder(nn.Module, _EntityRanking):
                                            formula_of.to(device), anchors, ids, q_row, self._error_word(device))
             self._check()
         return scores
+
+    def margin_loss_ids_mixed(self, formulas, formula_of, anchors, targets, neg_ids, margin=1):
+        """margin_loss() for B queries of DIFFERENT formulas of one query type with ids on the device (kg.MixedQuerySet.take):
+        `formulas` a sequence of Formula of that type (pass the SAME object every time: _mixed_descriptors is keyed on it),
+        formula_of [B], anchors [B, A], targets [B] and neg_ids [B] -- one negative per query, as the reference's
+        margin_loss draws -- int64. ONE differentiable mixed scoring call over targets ++ neg_ids
+        (ops.rgcn_scores_mixed_grad: mpqe_rgcn_fwd_mixed_save, and mpqe_rgcn_bwd_mixed in backward()), then ops.hinge: the
+        scalar loss the reference's margin_loss gives for those queries and negatives. The gradients land in .grad of the
+        entity tables, mode_embeddings.weight and every layer's basis / root / bias. Where _mixed_ok or
+        ops.rgcn_mixed_train_supported says no (learned readouts, fused = False, encode_twice, foreign encoders, other
+        shapes) the runs of equal formula are walked through the module path (margin_loss_ids_by_runs)."""
+        if not torch.is_tensor(formula_of) or formula_of.dtype != torch.long or formula_of.dim() != 1:
+            raise TypeError('margin_loss_ids_mixed: formula_of must be an int64 vector')
+        desc, layers = self._mixed_descriptors(formulas)
+        distinct = []
+        for l in layers:
+            if not any(l is d for d in distinct):
+                distinct.append(l)
+        if desc is None or not ops.rgcn_mixed_train_supported(self.emb_dim, len(layers), self.readout_str, len(distinct)):
+            return margin_loss_ids_by_runs(self, formulas, formula_of, anchors, targets, neg_ids, margin)
+        device = self._device()
+        B = int(targets.shape[0])
+        rows = torch.arange(B + 1, dtype=torch.long, device=device)
+        neg_ids = neg_ids.to(device).reshape(-1)
+        if formula_of.shape[0] != B or neg_ids.shape[0] != B:
+            raise ValueError('margin_loss_ids_mixed: formula_of [B], neg_ids [B]')
+        anchors, targets, neg_ids, _ = _device_ids(anchors, targets, (neg_ids, rows), device, len(formulas[0].anchor_modes))
+        layer_of_pass = [[l is d for d in distinct].index(True) for l in layers]
+        # (the fused step's error word where the model has one: the word the flat optimizer's guard reads, so that the
+        # update after a flagged window is refused on the device, as after a flagged margin_loss)
+        step = self.dropin()
+        err = step.step.err if step is not None else self._error_word(device)
+        scores = ops.rgcn_scores_mixed_grad(desc, desc.live, self.mode_embeddings.weight,
+                                            [(l.basis, l.root, l.bias) for l in distinct], layer_of_pass, self.enc.node_maps,
+                                            self.readout_str, formula_of.to(device).contiguous(), anchors,
+                                            torch.cat([targets, neg_ids]), rows, err)
+        # (_check() reads self._err and the encoder's word; the call above wrote `err`, which is the step's word where there
+        # is a step and self._err otherwise -- so the step's word is read here and _check() covers the rest)
+        if self.validate and step is not None:
+            ops.raise_on_flags(err)
+        self._check()
+        return ops.hinge(scores[:B], scores[B:], margin)
 
     # ------------------------------------------------------------------ answering a query (no counterpart in the reference)
     def _query_embeddings(self, formula, queries, anchor_ids, var_ids, q_graphs):
@@ -741,10 +790,11 @@ def score_ids_by_runs(model, formulas, formula_of_host, anchors, targets, neg=No
 
 
 def margin_loss_ids_by_runs(model, formulas, formula_of, anchors, targets, neg_ids, margin=1):
-    """QueryEncoderDecoder.margin_loss_ids_mixed without the mixed launch: every run of equal formula through the
-    differentiable per-formula route (model._score_ids: ops.gqe_scores where the fused kernel covers the formula, the
-    composed ops otherwise), the scores put back in forward()'s layout of the whole, one hinge. Its fallback, its oracle
-    and the other side of tools/gqe_mixed_train_bench.py (one read of formula_of)."""
+    """margin_loss_ids_mixed of either model without the mixed launch: every run of equal formula through the
+    differentiable per-formula route (model._score_ids -- QueryEncoderDecoder: ops.gqe_scores where the fused kernel
+    covers the formula, the composed ops otherwise; RGCNEncoderDecoder: the module path's ops), the scores put back in
+    forward()'s layout of the whole, one hinge. Its fallback, its oracle and the other side of
+    tools/gqe_mixed_train_bench.py and tools/rgcn_mixed_train_bench.py (one read of formula_of)."""
     device = model._device()
     B = int(targets.shape[0])
     anchors, targets, neg_ids = anchors.to(device), targets.to(device), neg_ids.to(device).reshape(-1)

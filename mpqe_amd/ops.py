@@ -1071,6 +1071,14 @@ class RgcnMixedDescriptors(object):
             _ck(L.mpqe_rgcn_mixed_desc_build(self.qid, recs.ctypes.data, self.num_formulas, tab_arr, rows_arr, len(tables),
                                              int(mode_emb_rows), self.ptr, self.nbytes, _stream()),
                 'mpqe_rgcn_mixed_desc_build')
+            # the index block of the mixed backward (mpqe_rgcn_mixed_index_build): the table INDEX of every slot, the
+            # relations and the mode-embedding rows; it depends on the records alone
+            self.mode_emb_rows = int(mode_emb_rows)
+            self.index_nbytes = L.mpqe_rgcn_mixed_index_bytes(self.num_formulas)
+            self.index_buffer = torch.empty(self.index_nbytes + 256, dtype=torch.uint8, device=dev)
+            self.index_ptr = _capi._align256(self.index_buffer.data_ptr())
+            _ck(L.mpqe_rgcn_mixed_index_build(self.qid, recs.ctypes.data, self.num_formulas, self.index_ptr,
+                                              self.index_nbytes, _stream()), 'mpqe_rgcn_mixed_index_build')
 
 
 _RGCN_MIX_WS = {}        # device -> the mixed launches' workspace, grown in place (every call runs on the current stream)
@@ -1140,6 +1148,135 @@ def rgcn_scores_mixed(desc, node_map, mode_emb, layers, readout, formula_of, anc
             _ck(lib().mpqe_rgcn_fwd_mixed(*head, _p(ids), _p(qrow), n, float(eps), _rgcn_mixed_ws(wb, dev), wb, _p(scores),
                                           _p(err), _stream()), 'mpqe_rgcn_fwd_mixed')
     return scores
+
+
+def rgcn_mixed_train_supported(dim, passes, readout, num_layers=1):
+    """The shapes mpqe_rgcn_fwd_mixed_save / mpqe_rgcn_bwd_mixed cover (include/mpqe_amd.h)."""
+    return (dim % 16 == 0 and 16 <= dim <= 256 and 1 <= passes <= RGCN_MIX_MAX_PASSES and readout in READOUT_IDS
+            and 1 <= num_layers <= RGCN_MIX_MAX_PASSES)
+
+
+class _RgcnMixedTrain(torch.autograd.Function):
+    """One mpqe_rgcn_fwd_mixed_save per forward, one mpqe_rgcn_bwd_mixed per backward. The differentiable inputs are the
+    descriptor's WHOLE table list, the mode embeddings and every distinct layer's basis / root / bias (`params` = tables,
+    mode_emb, the bases, the roots, the biases that exist). embed: the query embeddings are returned and the backward goes
+    through grad_q; otherwise the scores of ids [n] under neg_off."""
+
+    @staticmethod
+    def forward(ctx, spec, *params):
+        import ctypes
+        desc, node_map, layer_of_pass, has_bias, readout, formula_of, anchors, ids, neg_off, err, eps, embed = spec
+        T, L, passes = len(desc.tables), len(has_bias), len(layer_of_pass)
+        params = [_f(p, 'parameter') for p in params]
+        tables, mode_emb = params[:T], params[T]
+        basis, root = params[T + 1:T + 1 + L], params[T + 1 + L:T + 1 + 2 * L]
+        biases, at = [], T + 1 + 2 * L
+        for hb in has_bias:
+            biases.append(params[at] if hb else None)
+            at += 1 if hb else 0
+        if tuple(t.data_ptr() for t in tables) != desc.ptrs:
+            raise ValueError('rgcn_scores_mixed_grad: the tables are not the ones the descriptor block was built on (their '
+                             'addresses differ): build a new RgcnMixedDescriptors')
+        D, R = desc.dim, int(basis[0].shape[0])
+        Q = int(formula_of.shape[0])
+        n = 0 if embed else int(ids.shape[0])
+        if mode_emb.dim() != 2 or mode_emb.shape[1] != D or mode_emb.shape[0] < desc.mode_emb_rows or \
+                not rgcn_mixed_train_supported(D, passes, readout, L):
+            raise ValueError('rgcn_scores_mixed_grad: a shape the mixed training launches do not cover')
+        for b, r, bi in zip(basis, root, biases):
+            if tuple(b.shape) != (R, D, D) or tuple(r.shape) != (D, D) or (bi is not None and tuple(bi.shape) != (D,)):
+                raise ValueError('rgcn_scores_mixed_grad: basis [R, D, D], root [D, D] and bias [D] with one R and the tables\' D')
+        dev = tables[0].device
+        arr = [(ctypes.c_void_p * passes)(*[_p(seq[l]) for l in layer_of_pass]) for seq in (basis, root, biases)]
+        head = (desc.qid, desc.num_formulas, desc.ptr, desc.nbytes)
+        mid = (_p(node_map), 0 if node_map is None else node_map.shape[0], _p(mode_emb), arr[0], arr[1], arr[2], R, passes,
+               READOUT_IDS[readout], D, _p(formula_of), _p(anchors), Q, _p(ids), _p(neg_off), n, eps, T,
+               int(mode_emb.shape[0]), L)
+        out = torch.empty((Q, D) if embed else (n,), dtype=torch.float32, device=dev)
+        ws, wp, wb = None, None, 0
+        if Q > 0:
+            with torch.cuda.device(dev):
+                wb = lib().mpqe_rgcn_mixed_train_workspace_bytes(desc.qid, Q, n, D, passes, R, T, int(mode_emb.shape[0]), L)
+                if wb == 0:
+                    raise ValueError('rgcn_scores_mixed_grad: shape outside what the kernels cover')
+                ws = _ws(wb + 256, dev)
+                wp = _capi._align256(ws.data_ptr())
+                _ck(lib().mpqe_rgcn_fwd_mixed_save(*(head + mid + (wp, wb, None if embed else _p(out),
+                                                                  _p(out) if embed else None, _p(err), _stream()))),
+                    'mpqe_rgcn_fwd_mixed_save')
+        ctx.call = (desc, head, mid, wp, wb, err, embed, list(layer_of_pass), has_bias,
+                    (ws, node_map, formula_of, anchors, ids, neg_off, arr, params))
+        ctx.shapes = [tuple(p.shape) for p in params]
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        import ctypes
+        desc, head, mid, wp, wb, err, embed, layer_of_pass, has_bias, _keep = ctx.call
+        T, L = len(desc.tables), len(has_bias)
+        g = _f(g.contiguous(), 'grad')
+        dev = g.device
+        want = ctx.needs_input_grad[1:]
+        # one zero-filled allocation for every wanted gradient, handed out as views (16-byte aligned: every size is a
+        # multiple of D >= 16 floats)
+        sizes = [int(np.prod(sh)) if w else 0 for sh, w in zip(ctx.shapes, want)]
+        flat = torch.zeros(sum(sizes), dtype=torch.float32, device=dev)
+        grads, at = [], 0
+        for sh, w, k in zip(ctx.shapes, want, sizes):
+            grads.append(flat[at:at + k].view(sh) if w else None)
+            at += k
+        if wp is not None:
+            gbias, at = [], T + 1 + 2 * L
+            for hb in has_bias:
+                gbias.append(grads[at] if hb else None)
+                at += 1 if hb else 0
+            gt = (ctypes.c_void_p * T)(*[_p(x) for x in grads[:T]])
+            per = [(ctypes.c_void_p * L)(*[_p(x) for x in seq])
+                   for seq in (grads[T + 1:T + 1 + L], grads[T + 1 + L:T + 1 + 2 * L], gbias)]
+            lop = (ctypes.c_int * len(layer_of_pass))(*layer_of_pass)
+            with torch.cuda.device(dev):
+                _ck(lib().mpqe_rgcn_bwd_mixed(*(head + (desc.index_ptr, desc.index_nbytes) + mid + (
+                    lop, None if embed else _p(g), _p(g) if embed else None, gt, _p(grads[T]), per[0], per[1], per[2], wp, wb,
+                    _p(err), _stream()))), 'mpqe_rgcn_bwd_mixed')
+        return (None,) + tuple(grads)
+
+
+def _rgcn_mixed_train(desc, tables, mode_emb, layers, layer_of_pass, node_map, readout, formula_of, anchors, ids, neg_off, err,
+                      eps, embed):
+    formula_of, anchors = _i(formula_of, 'formula_of'), _i(anchors, 'anchors')
+    node_map = None if node_map is None else _i(node_map, 'node_map')
+    if formula_of.dim() != 1 or anchors.dim() != 2 or anchors.shape[0] != formula_of.shape[0]:
+        raise ValueError('rgcn_scores_mixed_grad: formula_of [B] and anchors [B, A]')
+    if not embed:
+        ids, neg_off = _i(ids, 'ids'), _i(neg_off, 'neg_off')
+        if ids.dim() != 1 or neg_off.dim() != 1 or neg_off.shape[0] != formula_of.shape[0] + 1 or \
+                ids.shape[0] < formula_of.shape[0]:
+            raise ValueError('rgcn_scores_mixed_grad: ids [B + total] and neg_off [B + 1]')
+    has_bias = tuple(l[2] is not None for l in layers)
+    params = list(tables) + [mode_emb] + [l[0] for l in layers] + [l[1] for l in layers] + \
+        [l[2] for l in layers if l[2] is not None]
+    spec = (desc, node_map, tuple(int(l) for l in layer_of_pass), has_bias, readout, formula_of, anchors, ids, neg_off, err,
+            float(eps), embed)
+    return _RgcnMixedTrain.apply(spec, *params)
+
+
+def rgcn_scores_mixed_grad(desc, tables, mode_emb, layers, layer_of_pass, node_map, readout, formula_of, anchors, ids, neg_off,
+                           err=None, eps=1e-8):
+    """rgcn_scores_mixed with the pair layout fixed to forward()'s -- ids [B + total] = the B targets, then the negatives in
+    CSR order under neg_off [B + 1] --, differentiable w.r.t. `tables` (the tensors `desc` was built on: their data_ptr()s
+    are checked), `mode_emb` and every DISTINCT layer's (basis, root, bias or None) in `layers`; layer_of_pass[p]: the
+    position in `layers` of what pass p runs. One mpqe_rgcn_fwd_mixed_save in the forward, one mpqe_rgcn_bwd_mixed in the
+    backward (include/mpqe_amd.h); the scores are rgcn_scores_mixed's bits. All gradients of a call are views of ONE
+    zero-filled allocation; a parameter no query of the window names gets zeros, not None."""
+    return _rgcn_mixed_train(desc, tables, mode_emb, layers, layer_of_pass, node_map, readout, formula_of, anchors, ids,
+                             neg_off, err, eps, False)
+
+
+def rgcn_embed_mixed_grad(desc, tables, mode_emb, layers, layer_of_pass, node_map, readout, formula_of, anchors, err=None):
+    """rgcn_embed_mixed, differentiable as rgcn_scores_mixed_grad is: the query embeddings [B, D], the backward through
+    mpqe_rgcn_bwd_mixed's grad_q."""
+    return _rgcn_mixed_train(desc, tables, mode_emb, layers, layer_of_pass, node_map, readout, formula_of, anchors, None, None,
+                             err, 1e-8, True)
 
 
 # --------------------------------------------------------------------------------------------- neighbourhood encoder

@@ -193,9 +193,9 @@ def main(argv=None):
                     help='with --device-eval: group the test sets by query type (kg.MixedQuerySet) and score queries of '
                          'different formulas per call -- one launch a window under --model gqe; other sampled negatives')
     ap.add_argument('--mixed-train', action='store_true',
-                    help='with --device-queries --model gqe: train on windows of one query type whatever the formulas '
-                         '(kg.MixedQuerySet.take + QueryEncoderDecoder.margin_loss_ids_mixed: one mixed forward and one mixed '
-                         'backward per window) instead of one formula per batch')
+                    help='with --device-queries: train on windows of one query type whatever the formulas '
+                         '(kg.MixedQuerySet.take + the model\'s margin_loss_ids_mixed: one mixed forward and one mixed '
+                         'backward per window, under either --model) instead of one formula per batch')
     ap.add_argument('--depth', type=int, default=0, choices=[0, 1, 2],
                     help='entity encoder (the reference\'s --depth): 0 the embedding lookup (everything above), 1 / 2 the '
                          'neighbourhood-aggregating Encoder of utils.get_encoder under either --model, trained through '
@@ -207,12 +207,18 @@ def main(argv=None):
         ap.error('--device-eval needs --device-queries and the embedding-lookup encoder (--depth 0)')
     if args.mixed_eval and not args.device_eval:
         ap.error('--mixed-eval needs --device-eval')
-    if args.mixed_train and (not args.device_queries or args.model != 'gqe' or args.depth):
-        ap.error('--mixed-train needs --device-queries --model gqe (and the embedding-lookup encoder, --depth 0)')
+    if args.mixed_train and (not args.device_queries or args.depth or
+                             (args.model == 'rgcn' and args.readout not in ('mp', 'sum', 'max'))):
+        ap.error('--mixed-train needs --device-queries and the embedding-lookup encoder (--depth 0); under --model rgcn a '
+                 'readout without parameters (mp | sum | max)')
+    if args.mixed_train and args.dropin:
+        ap.error('--mixed-train and --dropin are two different loops: choose one')
     if args.depth:
         out = run_depth(args)
     elif args.model == 'gqe':
         out = run_gqe(args)
+    elif args.mixed_train:
+        out = run_rgcn_mixed(args)
     else:
         out = run_dropin(args) if args.dropin else run(args)
     if getattr(args, 'device_queries', False):
@@ -470,6 +476,65 @@ def kg_index(args, schema, node_maps, device):
     return KGIndex.from_edges(schema, edges, node_maps, device)
 
 
+def mixed_windows(args, model, query_types, device):
+    """--mixed-train: a batch is batch_size positions of a query type's concatenation, whatever their formulas; sorted, so
+    that equal formulas sit next to each other (longer stretches, fewer matrix reads). -> (the iterators and the
+    margin_loss of _reference_loop, the negative samplers): kg.MixedQuerySet.take + model.margin_loss_ids_mixed."""
+    from mpqe_amd.kg import MixedQuerySet
+    mixed = MixedQuerySet.from_sets(args.train_sets)
+    samplers = {qt: ms.negative_sampler() for qt, ms in mixed.items()}
+    gen = torch.Generator().manual_seed(args.seed + 13)
+    draws = [0]
+
+    def positions(qt):
+        while True:
+            idx = torch.randint(len(mixed[qt]), (args.batch_size,), generator=gen, dtype=torch.long)
+            yield qt, torch.sort(idx).values.to(device)
+
+    def margin_loss(batch, hard):
+        qt, idx = batch
+        ms = mixed[qt]
+        draws[0] += 1
+        neg = samplers[qt].sample(idx, args.seed + 100000 + draws[0], hard_negatives=hard)
+        formula_of, anchors, targets = ms.take(idx)
+        return model.margin_loss_ids_mixed(ms.formulas, formula_of, anchors, targets, neg)
+    return {qt: positions(qt) for qt in query_types}, margin_loss, samplers
+
+
+def run_rgcn_mixed(args):
+    """--mixed-train under --model rgcn: the R-GCN model (embedding-lookup encoder, a readout without parameters) through
+    the reference's loop body on mixed windows -- RGCNEncoderDecoder.margin_loss_ids_mixed: one mixed forward with states
+    and one mixed backward per window --, loss.backward(), Adam; ROC-AUC before and after."""
+    import random
+    from mpqe_amd import evaluation, optim
+    device = torch.device('cuda:0')
+    schema, graph, node_maps, model, train, test = build(args, device)
+    model = model.to(device)
+    tq = test_dict(test)
+    order = [qt for qt, _ in __import__('mpqe_amd.synthetic', fromlist=['FULL_MIX']).FULL_MIX]
+    query_types = list(dict.fromkeys(order))
+    iterators, margin_loss, samplers = mixed_windows(args, model, query_types, device)
+    with torch.no_grad():
+        auc0, _ = evaluation.eval_auc_queries(model_queries(args, tq), model, batch_size=128, seed=0)
+    opt = optim.Adam([p for p in model.parameters() if p.requires_grad], lr=args.lr)
+    random.seed(args.seed + 12)
+    t0 = time.perf_counter()
+    losses = _reference_loop(model, iterators, query_types, opt, args.steps, margin_loss)
+    for sampler in samplers.values():
+        sampler.check()
+    torch.cuda.synchronize()
+    train_s = time.perf_counter() - t0
+    with torch.no_grad():
+        auc1, _ = evaluation.eval_auc_queries(model_queries(args, tq), model, batch_size=128, seed=0)
+    out = dict(model='rgcn', kg=args.kg, embed_dim=args.embed_dim, batch_size=args.batch_size, steps=args.steps,
+               readout=args.readout, train_seconds=train_s, loss_first=losses[0], loss_last20=float(np.mean(losses[-20:])),
+               auc_before=float(auc0), auc_after=float(auc1), loss_curve=losses, mixed_train=True)
+    if getattr(args, 'device_eval', False):
+        with torch.no_grad():
+            out['perc_after'] = float(evaluation.eval_perc_queries(eval_sets(args), model, batch_size=128))
+    return out
+
+
 def run_gqe(args):
     """The GQE baseline (QueryEncoderDecoder, bilinear paths + set intersection) through the reference's loop body
     (_reference_loop): margin_loss per batch on the fused kernels, loss.backward(), Adam; ROC-AUC and the filtered ranking
@@ -495,27 +560,7 @@ def run_gqe(args):
     iterators = {qt: batches(qt) for qt in query_types}
     margin_loss = lambda batch, hard: model.margin_loss(*batch, hard_negatives=hard)       # noqa: E731
     if getattr(args, 'mixed_train', False):
-        # --mixed-train: a batch is batch_size positions of a query type's concatenation, whatever their formulas; sorted,
-        # so that equal formulas sit next to each other (longer stretches, fewer matrix reads)
-        from mpqe_amd.kg import MixedQuerySet
-        mixed = MixedQuerySet.from_sets(args.train_sets)
-        samplers = {qt: ms.negative_sampler() for qt, ms in mixed.items()}
-        gen = torch.Generator().manual_seed(args.seed + 13)
-        draws = [0]
-
-        def positions(qt):
-            while True:
-                idx = torch.randint(len(mixed[qt]), (args.batch_size,), generator=gen, dtype=torch.long)
-                yield qt, torch.sort(idx).values.to(device)
-
-        def margin_loss(batch, hard):
-            qt, idx = batch
-            ms = mixed[qt]
-            draws[0] += 1
-            neg = samplers[qt].sample(idx, args.seed + 100000 + draws[0], hard_negatives=hard)
-            formula_of, anchors, targets = ms.take(idx)
-            return model.margin_loss_ids_mixed(ms.formulas, formula_of, anchors, targets, neg)
-        iterators = {qt: positions(qt) for qt in query_types}
+        iterators, margin_loss, samplers = mixed_windows(args, model, query_types, device)
     with torch.no_grad():
         auc0, _ = evaluation.eval_auc_queries(model_queries(args, tq), model, batch_size=128, seed=0)
     rank0 = evaluation.eval_rank_queries(tq, model.eval(), batch_size=128, ks=(10,), known_answers=known)
