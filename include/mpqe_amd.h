@@ -313,6 +313,50 @@ int mpqe_rank_entities_scored(const float *q, int64_t num_queries, const float *
                               int64_t *rank, float *target_scores, void *workspace, size_t workspace_bytes, int32_t *err,
                               void *stream);
 
+/* Queries of ONE call ranked against DIFFERENT tables (csrc/rank_mixed.hip; added under ABI 7: entries only). Query i is
+ * ranked against candidate set set_of_group[group_of[i]] of num_sets sets -- in an evaluation window the group is the
+ * query's formula and the set the entities of the formula's target mode.
+ *
+ * mpqe_rank_mixed_desc_build writes the sets to `desc` (device memory, 256-byte aligned, mpqe_rank_mixed_desc_bytes: exact,
+ * a byte less is MPQE_ERR_WORKSPACE; 0: a count out of range). Host arrays, per set: tables_host the device address of raw
+ * rows [rows_host[s], dim] (16-byte aligned, MPQE_ERR_UNSUPPORTED otherwise), rows_host >= 1, kinds_host the score kind of
+ * mpqe_rank_entities_scored (0 cosine, 1 dot), valid_host (the array or an entry may be NULL: every row valid) the device
+ * address of ceil(rows / 32) uint32 words, bit r clear = row r is no entity and never eligible. set_of_group_host
+ * [num_groups] in [0, num_sets). 1 <= num_sets <= 256, 1 <= num_groups <= 2^20, the rows of all sets <= 2^30. Everything
+ * is checked before anything is written. The block holds addresses and sizes only: the caller keeps it between calls and
+ * a ranking call does no host work per set or per group.
+ *
+ * mpqe_rank_entities_mixed: num_sets, num_groups, max_rows (the widest set) and total_rows (all sets') are the block's own
+ * (a call that names other values flags MPQE_FLAG_BAD_INDEX and ranks nothing). group_of [Q] int64 on the device.
+ * target_rows [Q] or NULL: rows of the query's own set. excl_bits or NULL: [Q, excl_stride_words] int32 words, the layout
+ * of the KG index's answer bitmaps; bit r of row i set = row r is not eligible for query i; bits at or beyond the rows of
+ * the query's set, and words the stride does not cover, are not read as exclusions. topk_rows, topk_scores, rank,
+ * target_scores: the layouts and meanings of mpqe_rank_entities. Workspace: 256-byte aligned,
+ * mpqe_rank_mixed_workspace_bytes (exact; 0: out of range); its contents on entry do not matter.
+ * Rank, every top-k row and score and the target score of query i equal BIT FOR BIT what mpqe_rank_entities_scored returns
+ * when the queries of i's set are handed to it alone with the set's score kind and, as exclusion list, the set's rows
+ * whose excl_bits bit is set or whose valid bit is clear. Total order, the target never being excluded from its rank, NaN
+ * last and integer counters as there. The outputs of a query depend neither on the order of the queries (a permutation
+ * of the queries permutes the outputs) nor on how they are split over calls.
+ * Launches: a plan (stable sort of the queries by set, blocks of 64 queries of one set: at most Q / 64 + num_sets, the
+ * grids are sized to that bound on the host), then the pre-pass, the targets, the tiles and the merge of
+ * mpqe_rank_entities, each reading its queries through the permutation and its table through the block's set. Exclusion
+ * is a bit test in the tile kernel (two words per query and 64-row tile).
+ * A group_of[i] outside [0, num_groups) or a target row outside its set ORs MPQE_FLAG_BAD_INDEX: rank -1, score NaN (a bad
+ * group: also a top-k of -1 / -inf); the other queries are unaffected and nothing is read or written out of bounds.
+ * num_queries == 0: MPQE_OK, no launch. k > 128: MPQE_ERR_UNSUPPORTED. */
+size_t mpqe_rank_mixed_desc_bytes(int64_t num_sets, int64_t num_groups);
+int mpqe_rank_mixed_desc_build(const float *const *tables_host, const int64_t *rows_host, const int32_t *kinds_host,
+                               const uint32_t *const *valid_host, int64_t num_sets, const int32_t *set_of_group_host,
+                               int64_t num_groups, void *desc, size_t desc_bytes, void *stream);
+size_t mpqe_rank_mixed_workspace_bytes(int64_t num_queries, int64_t num_sets, int64_t max_rows, int64_t total_rows,
+                                       int64_t dim, int k);
+int mpqe_rank_entities_mixed(const float *q /*[Q, dim]*/, int64_t num_queries, int64_t dim, float eps, const void *desc,
+                             size_t desc_bytes, int64_t num_sets, int64_t num_groups, int64_t max_rows, int64_t total_rows,
+                             const int64_t *group_of, const int64_t *target_rows, const int32_t *excl_bits,
+                             int64_t excl_stride_words, int k, int64_t *topk_rows, float *topk_scores, int64_t *rank,
+                             float *target_scores, void *workspace, size_t workspace_bytes, int32_t *err, void *stream);
+
 /* ---- fused training step -------------------------------------------------------------------
  * Forward + backward of RGCNEncoderDecoder.margin_loss (reference model.py:464-494) for ALL the
  * formula batches of one training step (reference train_helpers.py:76-120 draws 11 after
@@ -819,6 +863,17 @@ int mpqe_gqe_fwd_mixed(const int32_t *prog_host, int64_t num_formulas, const voi
                        int64_t num_queries, const int64_t *p_ids, int64_t p_rows, const int64_t *e_ids, int64_t e_rows,
                        const int64_t *qrow, const int64_t *neg_off, int64_t n, float eps, float *scores, int32_t *err,
                        void *stream);
+
+/* mpqe_gqe_embed for queries of different formulas (added under ABI 7: an entry only): the rows mpqe_gqe_fwd_mixed would
+ * score, written to out [num_queries, dim] (16-byte aligned) in the same single launch and with the same descriptor
+ * block, for the intersection form (programme int [0] == 1; the chain form is MPQE_ERR_INVALID_ARG: its candidates are a
+ * projected table per formula, which goes by runs through mpqe_gqe_embed). p_ids [branches, num_queries]. Row q equals BIT
+ * FOR BIT mpqe_gqe_embed's row when the query's run is handed to it alone with its own programme. A formula index
+ * outside [0, num_formulas) ORs MPQE_FLAG_BAD_INDEX and its row is zeros; bad ids as in mpqe_gqe_fwd.
+ * num_queries == 0: MPQE_OK, no launch. */
+int mpqe_gqe_embed_mixed(const int32_t *prog_host, int64_t num_formulas, const void *desc, size_t desc_bytes,
+                         const int64_t *node_map, int64_t node_map_len, int64_t dim, const int64_t *formula_of,
+                         int64_t num_queries, const int64_t *p_ids, float *out, int32_t *err, void *stream);
 
 /* Training on GQE queries of DIFFERENT formulas of one query type (csrc/gqe_mixed_train.h; added under ABI 7: entries
  * only): the mixed forward with states and a mixed backward over the layout of mpqe_gqe_fwd_mixed.

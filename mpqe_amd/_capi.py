@@ -107,11 +107,16 @@ PROTOTYPES = {
     'mpqe_rank_workspace_bytes': (Z, [L, L, L, I]),
     'mpqe_rank_entities': (I, [P, L, P, L, L, F, P, P, P, L, I, P, P, P, P, P, Z, P, P]),
     'mpqe_rank_entities_scored': (I, [P, L, P, L, L, F, I, P, P, P, L, I, P, P, P, P, P, Z, P, P]),
+    'mpqe_rank_mixed_desc_bytes': (Z, [L, L]),
+    'mpqe_rank_mixed_desc_build': (I, [P, P, P, P, L, P, L, P, Z, P]),
+    'mpqe_rank_mixed_workspace_bytes': (Z, [L, L, L, L, L, I]),
+    'mpqe_rank_entities_mixed': (I, [P, L, L, F, P, Z, L, L, L, L, P, P, P, L, I, P, P, P, P, P, Z, P, P]),
     'mpqe_gqe_workspace_bytes': (Z, [P, L, L, L]),
     'mpqe_gqe_fwd': (I, [P, P, P, I, P, L, P, I, L, P, L, P, L, P, P, L, F, I, P, P, Z, P, P]),
     'mpqe_gqe_bwd': (I, [P, P, P, I, P, L, P, I, L, P, L, P, L, P, P, L, F, P, P, P, P, Z, P, P]),
     'mpqe_gqe_embed': (I, [P, P, P, I, P, L, P, I, L, P, L, P, P, P]),
     # queries of different formulas of one query type in one launch (added under ABI 7: entries only)
+    'mpqe_gqe_embed_mixed': (I, [P, L, P, Z, P, L, L, P, L, P, P, P, P]),
     'mpqe_gqe_mixed_desc_bytes': (Z, [L]),
     'mpqe_gqe_mixed_desc_build': (I, [P, L, P, P, I, P, I, L, P, Z, P]),
     'mpqe_gqe_fwd_mixed': (I, [P, L, P, Z, P, L, L, P, L, P, L, P, L, P, P, L, F, P, P, P]),

@@ -892,10 +892,14 @@ __device__ __forceinline__ long long gq_mix_t_off(const GqeDev &G, int b) {
 
 // SAVE = 1 (mpqe_gqe_fwd_mixed_save): the states of mpqe_gqe_fwd(save_states = 1), by P row of the concatenation; the
 // arithmetic, and so every score's bits, is that of SAVE = 0.
-template <int DOT, int SAVE>
+// KIND 0: SAVE = 0; 1: SAVE = 1; 2 (mpqe_gqe_embed_mixed, intersection form): SAVE = 0 and, as gqe_fwd_kernel's EMBED, the
+// rows the forward would score go to `scores` as [Rp, D] -- a stretch writes its own rows, a bad formula's rows are zeros.
+template <int DOT, int KIND>
 __global__ __launch_bounds__(256) void gqe_fwd_mixed_kernel(GqeDev G, const GqeMixDesc *__restrict__ desc,
                                                             const long long *__restrict__ fo, long long B, int F,
                                                             float *__restrict__ scores) {
+    constexpr int SAVE = KIND == 1 ? 1 : 0;
+    constexpr int EMBED = KIND == 2 ? 1 : 0;
     __shared__ __attribute__((aligned(16))) float lds[3 * GQ_ROWS * GQ_LDXMAX];
     const int D = G.D, LDX = D + 4, per = D / 4;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -921,6 +925,10 @@ __global__ __launch_bounds__(256) void gqe_fwd_mixed_kernel(GqeDev G, const GqeM
     fi = __builtin_amdgcn_readfirstlane(fi);
     if (fi < 0) {
         if (threadIdx.x == 0) flag_error(G.err, MPQE_FLAG_BAD_INDEX);
+        if (EMBED) {
+            for (long long e = threadIdx.x; e < (end - first) * D; e += 256) scores[first * D + e] = 0.f;
+            return;
+        }
         for (int i = wave; i < GQ_ROWS; i += 4) {
             const long long q = first + i;
             if (q >= end) continue;
@@ -1012,6 +1020,10 @@ __global__ __launch_bounds__(256) void gqe_fwd_mixed_kernel(GqeDev G, const GqeM
         float *t = cur; cur = nxt; nxt = t;
     }
     if (SAVE) gq_store_rows(cur, LDX, G.ws + G.pfin_off, first, nrow, D);
+    if (EMBED) {
+        gq_store_rows(cur, LDX, scores, first, nrow, D);
+        return;
+    }
 
     for (int i = wave; i < GQ_ROWS; i += 4) {
         const long long q = first + i;

@@ -608,6 +608,22 @@ extern "C" int mpqe_gqe_fwd_mixed(const int32_t *prog_host, int64_t num_formulas
     return gqe_fwd_mixed_launch<0>(H.G, desc, formula_of, num_queries, num_formulas, scores, stream);
 }
 
+// the rows the mixed forward would score, alone (intersection form): gqe_fwd_mixed_kernel's EMBED path, no E side
+extern "C" int mpqe_gqe_embed_mixed(const int32_t *prog_host, int64_t num_formulas, const void *desc, size_t desc_bytes,
+                                    const int64_t *node_map, int64_t node_map_len, int64_t dim, const int64_t *formula_of,
+                                    int64_t num_queries, const int64_t *p_ids, float *out, int32_t *err, void *stream) {
+    if (!prog_host || prog_host[0] != 1) return MPQE_ERR_INVALID_ARG;       // (chain form: by runs, mpqe_gqe_embed)
+    GqeHost H;
+    bool empty;
+    // (one P row per query and no E rows: the sizes of the E side stand at the P side's, its ids are not read)
+    const int st = gqe_mixed_call(prog_host, num_formulas, desc, desc_bytes, 0, 0, node_map, node_map_len, dim, formula_of,
+                                  num_queries, p_ids, num_queries, p_ids, num_queries, nullptr, nullptr, num_queries, 0.f,
+                                  nullptr, 0, err, &H, nullptr, &empty);
+    if (st != MPQE_OK || empty) return st;
+    if (!out || (uintptr_t)out % 16 != 0) return MPQE_ERR_INVALID_ARG;
+    return gqe_fwd_mixed_launch<2>(H.G, desc, formula_of, num_queries, num_formulas, out, stream);
+}
+
 extern "C" int mpqe_gqe_fwd_mixed_save(const int32_t *prog_host, int64_t num_formulas, const void *desc, size_t desc_bytes,
                                        int num_tables, int num_mats, const int64_t *node_map, int64_t node_map_len,
                                        int64_t dim, const int64_t *formula_of, int64_t num_queries, const int64_t *p_ids,

@@ -16,20 +16,9 @@
 //   rank_finish_kernel   merges a query's strip lists in strip order (one wave per query), writes rank and top-k
 // Total order: higher fp32 score first, the smaller row on equal scores. Counters are integers (integer atomics: the sum
 // does not depend on the order); no float atomics.
-#include <math.h>
-
-#include "gemm_core.h"
-
-#define RANK_MAX_K 128          // candidate lists: 64 queries x k x 8 B of LDS next to the tile core's 36 KB
-#define RANK_SMALL_K 16
-#define RANK_MID_K 64           // 70 KB of LDS in all: still two workgroups per CU (128: 100 KB, one)
-#define RANK_MAX_STRIPS 64      // one lane of the merging wave per strip
-#define RANK_TILE_LD 65         // score tile [64][65] (reuses the tile core's LDS)
-
-__device__ __forceinline__ float rank_score(float dot, float rinv, float qinv) {
-    const float s = (dot * rinv) * qinv;
-    return s == s ? s : -INFINITY;          // (a NaN has no place in a total order: it ranks last)
-}
+// rank_core.h holds what rank_mixed.hip (the queries of one call ranked against different tables) runs too: the score, the
+// pre-pass's per-row factors, the operand loader, the list insertion and the merge.
+#include "rank_core.h"
 
 // ---------------------------------------------------------------------------------------------- pre-pass
 __global__ __launch_bounds__(256) void rank_prep_kernel(const float *__restrict__ q, long long Q,
@@ -43,52 +32,20 @@ __global__ __launch_bounds__(256) void rank_prep_kernel(const float *__restrict_
     const int lane = threadIdx.x & 63;
     const bool is_q = i >= N;
     const float *v = is_q ? q + (i - N) * D : table + i * D;
-    float ss = 0.f;
-    if (score_kind == 0)
-        for (int c = lane; c < D; c += 64) ss += v[c] * v[c];
-    ss = wave_sum(ss);
+    const float ss = rank_sumsq(v, D, lane, score_kind);
     if (lane != 0) return;
     const float nrm = sqrtf(ss);
     if (is_q) {
         const long long j = i - N;
-        qinv[j] = score_kind ? 1.f : 1.f / fmaxf(nrm, eps);      // (dot: (dot * 1) * 1 is the dot's own bits; eps is not read)
+        qinv[j] = rank_query_inv(nrm, eps, score_kind);
         tsc[j] = -INFINITY;
         trow[j] = -1;
         cnt[j] = 0;
         cntx[j] = 0;
     } else {
-        rinv[i] = score_kind ? 1.f : (nrm > 0.f ? 1.f / nrm : 0.f);      // (a zero row has no direction: it scores 0)
+        rinv[i] = rank_row_inv(nrm, score_kind);
     }
 }
-
-// ---------------------------------------------------------------------------------------------- operands
-// Both operands are R-type (contiguous along k): A rows are query embeddings, B rows are table rows. The caller hands in
-// this thread's two row pointers per operand; a row outside the operand is !ok (LD_FAST: a clamped valid row instead).
-template <int MODE>
-struct RankLoader {
-    const float *pa0, *pa1, *pb0, *pb1, *sa, *sb;
-    bool a0, a1, b0, b1;
-    int c, K, left;
-
-    __device__ __forceinline__ void init(const float *a_safe, const float *b_safe, int K_) {
-        sa = a_safe;
-        sb = b_safe;
-        K = K_;
-        c = stage_col(false);
-        left = (K + GT_BK - 1) / GT_BK;
-    }
-    __device__ __forceinline__ f32x4 a(int slot, bool &ok) {
-        return ld4_pred<MODE>(sa, slot ? pa1 : pa0, c, K, slot ? a1 : a0, ok);
-    }
-    __device__ __forceinline__ f32x4 b(int slot, bool &ok) {
-        return ld4_pred<MODE>(sb, slot ? pb1 : pb0, c, K, slot ? b1 : b0, ok);
-    }
-    __device__ __forceinline__ void next() {
-        const bool go = left > 1;           // freeze on the last step (surplus pipeline loads)
-        left -= go ? 1 : 0;
-        c += go ? GT_BK : 0;
-    }
-};
 
 // ---------------------------------------------------------------------------------------------- listed pairs
 // The query whose CSR segment holds entry e: the last i with off[i] <= e (bounded: a garbled offset array cannot send it
@@ -304,15 +261,7 @@ __global__ __launch_bounds__(256) void rank_tile_kernel(const float *__restrict_
                         if (len >= k && !(s > S_[k - 1])) continue;
                         const long long col = c0 + quarter * 16 + j;
                         if (rank_excluded(excl, xlo, xhi, col)) continue;
-                        int p = len < k ? len : k - 1;
-                        while (p > 0 && S_[p - 1] < s) {
-                            S_[p] = S_[p - 1];
-                            R_[p] = R_[p - 1];
-                            --p;
-                        }
-                        S_[p] = s;
-                        R_[p] = (int)col;
-                        if (len < k) llen[srow] = len + 1;
+                        llen[srow] = rank_list_insert(S_, R_, len, k, s, (int)col);
                     }
                 }
                 __syncthreads();
@@ -355,38 +304,7 @@ __global__ __launch_bounds__(256) void rank_finish_kernel(long long Q, int k, in
         if (target_scores) target_scores[i] = tr >= 0 ? tsc[i] : NAN;
     }
     const long long base = live && lane < S ? (i * S + lane) * k : -1;
-    int pos = 0;
-    float hs = -INFINITY;
-    int hr = -1;
-    if (base >= 0 && k > 0) {
-        hs = cand_s[base];
-        hr = cand_r[base];
-    }
-    for (int j = 0; j < k; ++j) {
-        float bs = hs;
-        int bv = hr >= 0 ? 1 : 0, bl = lane;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const float os = __shfl_xor(bs, o, 64);
-            const int ov = __shfl_xor(bv, o, 64), ol = __shfl_xor(bl, o, 64);
-            const bool better = ov != bv ? ov > bv : (os != bs ? os > bs : ol < bl);
-            if (better) {
-                bs = os;
-                bv = ov;
-                bl = ol;
-            }
-        }
-        if (lane == bl && live) {
-            topk_rows[i * k + j] = bv ? (long long)hr : -1;
-            topk_scores[i * k + j] = bv ? hs : -INFINITY;
-            if (bv) {
-                ++pos;
-                const bool more = pos < k;
-                hs = more ? cand_s[base + pos] : -INFINITY;
-                hr = more ? cand_r[base + pos] : -1;
-            }
-        }
-    }
+    rank_merge_lists(live, lane, base, k, cand_s, cand_r, topk_rows + i * k, topk_scores + i * k);
 }
 
 // ---------------------------------------------------------------------------------------------- host

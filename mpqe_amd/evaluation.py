@@ -309,13 +309,55 @@ def eval_perc_queries(test_queries, enc_dec, batch_size=128, hard_negatives=Fals
     return np.mean(perc_scores)
 
 
+def _rank_sets(test_sets, enc_dec, batch_size, index):
+    """eval_rank_queries over {formula: kg.QuerySet}: per window the answers on the device (index.answers over the anchor
+    ids) and one enc_dec.rank_ids call; the ranks stay on the device and are copied once per set. Yields (formula, ranks)."""
+    import torch
+    for formula, qs in test_sets.items():
+        parts = []
+        for lo, hi in _batches(qs.targets, batch_size):
+            exclude = None if index is None else index.answers(formula, qs.anchors[lo:hi])
+            parts.append(enc_dec.rank_ids(formula, qs.anchors[lo:hi], qs.targets[lo:hi], exclude)[0])
+        yield formula, (torch.cat(parts).cpu().numpy() if parts else np.zeros(0, dtype=np.int64))
+
+
+def _rank_mixed_sets(test_sets, enc_dec, batch_size, index):
+    """eval_rank_queries over {query type: kg.MixedQuerySet}: per window of a type's concatenation the records from the
+    device ids (index.records_of_ids), the answers of queries of different formulas in one launch (index.answers_mixed)
+    and ONE ranking call -- enc_dec.rank_ids_mixed where the model has it, the window's runs through rank_ids otherwise;
+    the ranks stay on the device and are copied once per type. Yields (formula, ranks) from the type's bounds."""
+    import torch
+    for qt, ms in test_sets.items():
+        parts = []
+        for lo, hi in _batches(ms.targets, batch_size):
+            fo, anchors, targets = ms.formula_of[lo:hi], ms.anchors[lo:hi], ms.targets[lo:hi]
+            exclude = None
+            if index is not None:
+                exclude = index.answers_mixed(qt, index.records_of_ids(ms.formulas, fo, anchors, targets))
+            if hasattr(enc_dec, 'rank_ids_mixed'):
+                ranks = enc_dec.rank_ids_mixed(ms.formulas, fo, anchors, targets, exclude)[0]
+            else:
+                from .model import rank_ids_by_runs
+                ranks = rank_ids_by_runs(enc_dec, ms.formulas, ms.formula_of_host[lo:hi], anchors, targets, exclude)[0]
+            parts.append(ranks)
+        ranks = torch.cat(parts).cpu().numpy() if parts else np.zeros(0, dtype=np.int64)
+        for f, formula in enumerate(ms.formulas):
+            yield formula, ranks[int(ms.bounds[f]):int(ms.bounds[f + 1])]
+
+
 def eval_rank_queries(test_queries, enc_dec, batch_size=128, ks=(1, 3, 10), known_answers=None):
     """Link-prediction metrics over ALL entities of each query's target mode (no counterpart in the reference, whose
     evaluation ranks the target among the negatives stored with the query): the rank of query.target_node from
     `enc_dec.rank_targets`, filtered by `known_answers[query]` (every entity known to answer the query; the target is
     never filtered out) when given -- the standard filtered setting -- raw otherwise. known_answers may also be a
     kg.KGIndex: the answers of each batch are then computed on the device (index.answers) and never visit the host.
-    -> {'mrr', 'hits@k' for k in ks, 'num_queries', 'per_formula': {formula: {'mrr', 'hits@k', 'num_queries'}}}."""
+    -> {'mrr', 'hits@k' for k in ks, 'num_queries', 'per_formula': {formula: {'mrr', 'hits@k', 'num_queries'}}}.
+
+    {formula: kg.QuerySet} and {query type: kg.MixedQuerySet} take the device route (known_answers: a kg.KGIndex or
+    None): windows [lo, lo + batch_size), the answers from index.answers / index.answers_mixed over the device ids, one
+    enc_dec.rank_ids / rank_ids_mixed call a window -- for a MixedQuerySet one ranking call over queries of DIFFERENT
+    formulas and target modes --, the ranks copied to the host once per set or type. The same ranks as the list route
+    over QuerySet.queries(), so the same dict."""
     def summary(ranks):
         r = np.asarray(ranks, dtype=np.float64)
         out = {'mrr': float(np.mean(1.0 / r)) if r.size else float('nan')}
@@ -325,6 +367,18 @@ def eval_rank_queries(test_queries, enc_dec, batch_size=128, ks=(1, 3, 10), know
         return out
 
     from .kg import KGIndex
+    kind = _on_device(test_queries)
+    if kind:
+        if known_answers is not None and not isinstance(known_answers, KGIndex):
+            raise TypeError('eval_rank_queries: device query sets take known_answers as a kg.KGIndex (or None)')
+        ranks_of = _rank_mixed_sets if kind == 'mixed' else _rank_sets
+        all_ranks, per_formula = [], {}
+        for formula, ranks in ranks_of(test_queries, enc_dec, batch_size, known_answers):
+            per_formula[formula] = summary(ranks)
+            all_ranks.append(ranks)
+        out = summary(np.concatenate(all_ranks) if all_ranks else [])
+        out['per_formula'] = per_formula
+        return out
     all_ranks, per_formula = [], {}
     for formula in test_queries:
         formula_queries = test_queries[formula]

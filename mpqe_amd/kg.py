@@ -402,6 +402,65 @@ class KGIndex(object):
             out[i, 0] = 1
         return torch.from_numpy(out).to(self.device)
 
+    def _rows_of_modes(self, mode_index, ids):
+        """_rows_of for ids whose modes differ: mode_index [B] and ids [B] int64 on the device -> table rows [B], computed
+        there; an id that is no entity of its mode becomes that mode's row n (outside)."""
+        dev = self.device
+        if self._maps_dev is None:
+            self._maps_dev = torch.from_numpy(self.maps_host).to(dev)
+        cat = self.__dict__.get('_row_ids_cat_dev')
+        if cat is None:
+            base = np.zeros(len(self.modes), dtype=np.int64)
+            base[1:] = np.cumsum(self.mode_rows)[:-1]
+            cat = self.__dict__['_row_ids_cat_dev'] = (
+                torch.cat([self.row_ids[m] for m in self.modes]), torch.from_numpy(base).to(dev),
+                torch.from_numpy(self.mode_rows).to(dev))
+        row_ids, base, rows = cat
+        maps = self._maps_dev
+        n = rows[mode_index]
+        inside = (ids >= 0) & (ids < maps.shape[0])
+        cand = torch.where(inside, maps[ids.clamp(0, maps.shape[0] - 1)], torch.full_like(ids, -1))
+        ok = (cand >= 0) & (cand < n)
+        ok &= row_ids[base[mode_index] + torch.minimum(cand.clamp(min=0), n - 1)] == ids
+        return torch.where(ok, cand, n)
+
+    def records_of_ids(self, formulas, formula_of, anchors, targets=None):
+        """records_of for ids that are on the device already (kg.MixedQuerySet windows): formulas a sequence of Formula of
+        one query type, formula_of [Q] int64 every query's position in it, anchors [Q, A] and targets [Q] (or None: -1)
+        global ids. -> records [Q, 10] int64, equal to records_of(the queries' formulas, the queries), from tensor ops
+        alone: a per-formula template (kept per `formulas` object) gathered by formula_of, the anchors' and the target's
+        rows through the device copy of node_maps. A formula_of outside the formulas gives a record without a query."""
+        dev = self.device
+        kept = self.__dict__.setdefault('_record_templates', {})
+        hit = kept.get(id(formulas))
+        if hit is None or hit[0] is not formulas:
+            if len(formulas) == 0 or len({f.query_type for f in formulas}) != 1:
+                raise ValueError('KGIndex.records_of_ids: formulas of one query type')
+            anchor_edges = list(QUERY_SHAPES[formulas[0].query_type][1])
+            tmpl = np.full((len(formulas), _capi.KG_QUERY_INTS), -1, dtype=np.int64)
+            modes = np.zeros((len(formulas), len(anchor_edges) + 1), dtype=np.int64)
+            for k, f in enumerate(formulas):
+                for e, r in enumerate(_edge_relations(f)):
+                    if r not in self.rel_index:
+                        raise KeyError('KGIndex: no adjacency for relation %r' % (r,))
+                    tmpl[k, 2 + 3 * e] = self.rel_index[r]
+                tmpl[k, 0] = 1
+                modes[k] = [self.mode_index[m] for m in f.anchor_modes] + [self.mode_index[f.target_mode]]
+            while len(kept) >= 16:
+                kept.pop(next(iter(kept)))
+            hit = kept[id(formulas)] = (formulas, torch.from_numpy(tmpl).to(dev), torch.from_numpy(modes).to(dev), anchor_edges)
+        _, tmpl, modes, anchor_edges = hit
+        fo = formula_of.to(device=dev, dtype=torch.int64).reshape(-1)
+        anchors = anchors.to(device=dev, dtype=torch.int64).reshape(fo.shape[0], len(anchor_edges))
+        ok = (fo >= 0) & (fo < tmpl.shape[0])
+        foc = fo.clamp(0, tmpl.shape[0] - 1)
+        rec = tmpl[foc]
+        for slot, e in enumerate(anchor_edges):
+            rec[:, 3 + 3 * e] = self._rows_of_modes(modes[foc, slot], anchors[:, slot].contiguous())
+        if targets is not None:
+            rec[:, 1] = self._rows_of_modes(modes[foc, -1], targets.to(device=dev, dtype=torch.int64).reshape(-1))
+        return torch.where(ok[:, None], rec, torch.full_like(rec, -1))
+
     def answers_mixed(self, query_type, records, hard=False, probe_rows=None, bits=True, global_bits=False,
                       max_bitmap_bytes=1 << 30):
         """The exact answers of a batch of queries of one query type whose relations differ per query, one launch (per

@@ -186,6 +186,141 @@ class _EntityRanking(object):
             ids = torch.where(topr >= 0, row_ids[topr.clamp(min=0)], topr)
         return ids, tops, rank
 
+    # ------------------------------------------------------------------ ranking ids that are on the device already
+    def rank_ids(self, formula, anchors, targets, exclude=None, k=0):
+        """rank_targets / answer for ids that are on the device already (kg.QuerySet: evaluation.eval_rank_queries): anchors
+        [B, A] and targets [B] int64; exclude a kg.KGAnswers of these queries (KGIndex.answers) or None. -> (ranks [B],
+        top-k ids [B, k] or None, top-k scores), under no_grad: the per-formula route -- the model's own operands and ONE
+        ops.rank_entities -- with the targets translated on the device (an id that is no entity of the target mode becomes
+        the row past the ranked ones, so _check() raises). The by-runs fallback and the oracle of rank_ids_mixed."""
+        from .kg import KGAnswers
+        with torch.no_grad():
+            device = self._device()
+            mode = formula.target_mode
+            row_ids, holes, _ = self._mode_rows(mode, device)
+            n = row_ids.shape[0]
+            anchors, targets, _, _ = _device_ids(anchors, targets, None, device, len(formula.anchor_modes))
+            B = int(targets.shape[0])
+            maps = self.enc.node_maps
+            inside = (targets >= 0) & (targets < maps.shape[0])
+            cand = torch.where(inside, maps[targets.clamp(0, maps.shape[0] - 1)], torch.full_like(targets, -1))
+            ok = (cand >= 0) & (cand < n)
+            ok &= row_ids[cand.clamp(0, n - 1)] == targets
+            target_rows = torch.where(ok, cand, torch.full_like(cand, n))
+            csr = None
+            if isinstance(exclude, KGAnswers):
+                if exclude.mode != mode or exclude.n != n or len(exclude) != B:
+                    raise ValueError('exclude: KGAnswers of %d queries over %d rows of %r, ranking %d queries over %d rows of %r'
+                                     % (len(exclude), exclude.n, exclude.mode, B, n, mode))
+                csr = exclude.exclusion_csr()
+            elif exclude is not None:
+                raise TypeError('rank_ids: exclude is a kg.KGAnswers or None')
+            elif holes.size:
+                off = torch.arange(B + 1, dtype=torch.int64, device=device) * holes.size
+                csr = (off, torch.from_numpy(holes).to(device).repeat(B))
+            q, table, score = self._rank_operands_ids(formula, anchors, n)
+            topr, tops, rank, _ = ops.rank_entities(q, table, target_rows, csr, k, err=self._error_word(device), score=score)
+            self._check()
+            ids = None if topr is None else torch.where(topr >= 0, row_ids[topr.clamp(min=0)], topr)
+        return rank, ids, tops
+
+    def _rank_mixed_sets(self, formulas, device):
+        """The candidate sets of rank_ids_mixed for `formulas`: the distinct target modes, one ops.RankMixedDescriptors
+        over the modes' tables (valid words from a mode's holes), and what translates ids on the device. Kept beside the
+        row maps (self.__dict__['_row_ids'], reset where they are), keyed like _mixed_descriptors' entries: the identity of
+        `formulas` and data_ptr() of every table the block points at."""
+        cache = self.__dict__.get('_row_ids')
+        if cache is None:
+            cache = self.__dict__['_row_ids'] = {}
+        modes = []
+        for f in formulas:
+            if f.target_mode not in modes:
+                modes.append(f.target_mode)
+        ptrs = tuple(self.enc.table(m).data_ptr() for m in modes)
+        key = ('rank_mixed', id(formulas))
+        hit = cache.get(key)
+        if hit is not None and hit['formulas'] is formulas and hit['ptrs'] == ptrs and hit['device'] == device:
+            return hit
+        maps = [self._mode_rows(m, device) for m in modes]
+        tables, valid = [], []
+        for m, (row_ids, holes, row_ids_host) in zip(modes, maps):
+            n = row_ids.shape[0]
+            tables.append(self.enc.table(m).detach()[:n])
+            words = None
+            if holes.size:
+                words = cache.get(('valid', m))
+                if words is None or words.device != device:
+                    bits = np.zeros((n + 31) // 32 * 32, dtype=bool)
+                    bits[:n] = row_ids_host >= 0
+                    words = np.packbits(bits.reshape(-1, 32), axis=1, bitorder='little').view('<u4').reshape(-1)
+                    words = cache[('valid', m)] = torch.from_numpy(words.view(np.int32).copy()).to(device)
+            valid.append(words)
+        rows = np.asarray([t.shape[0] for t in tables], dtype=np.int64)
+        base = np.zeros(len(modes), dtype=np.int64)
+        base[1:] = np.cumsum(rows)[:-1]
+        set_of_group = np.asarray([modes.index(f.target_mode) for f in formulas], dtype=np.int32)
+        hit = {'formulas': formulas, 'ptrs': ptrs, 'device': device, 'modes': modes,
+               'desc': ops.RankMixedDescriptors(tables, set_of_group, 'cosine', valid),
+               'row_ids': torch.cat([m[0] for m in maps]), 'base': torch.from_numpy(base).to(device),
+               'rows': torch.from_numpy(rows).to(device), 'set_of_group': torch.from_numpy(set_of_group.astype(np.int64)).to(device),
+               'rows_host': [m[2] for m in maps], 'indexes': []}
+        olds = [k for k in cache if isinstance(k, tuple) and k[0] == 'rank_mixed' and k != key]
+        for old in olds[:max(0, len(olds) - (self.MIXED_KEPT - 1))]:         # (the oldest leave first)
+            cache.pop(old)
+        cache[key] = hit
+        return hit
+
+    def rank_ids_mixed(self, formulas, formula_of, anchors, targets, exclude=None, k=0):
+        """rank_ids for queries of DIFFERENT formulas of one query type (kg.MixedQuerySet): `formulas` a sequence of Formula
+        of that type (pass the SAME object every time), formula_of [B] int64 every query's position in it; exclude a
+        kg.KGAnswersMixed of these queries with its bitmaps kept (KGIndex.answers_mixed) or None. -> (ranks, top-k ids,
+        top-k scores) equal to rank_ids run by run, under no_grad. Where the model's mixed embedding covers the formulas
+        (_embed_mixed) this is one embedding call and ONE ops.rank_entities_mixed over the distinct target modes: the
+        answers' bitmaps are the exclusion words as they stand, targets and top-k rows are translated on the device.
+        Otherwise the runs of equal formula are walked through rank_ids (rank_ids_by_runs)."""
+        from .kg import KGAnswersMixed
+        if not torch.is_tensor(formula_of) or formula_of.dtype != torch.long or formula_of.dim() != 1:
+            raise TypeError('rank_ids_mixed: formula_of must be an int64 vector')
+        if exclude is not None and not isinstance(exclude, KGAnswersMixed):
+            raise TypeError('rank_ids_mixed: exclude is a kg.KGAnswersMixed or None')
+        if exclude is not None and exclude.bits is None:
+            raise ValueError('rank_ids_mixed: the answers were computed without their bitmaps (bits=False or chunked)')
+        with torch.no_grad():
+            if len(formulas) == 0 or len({f.query_type for f in formulas}) != 1:
+                raise ValueError('rank_ids_mixed: formulas of one query type')
+            device = self._device()
+            anchors, targets, _, _ = _device_ids(anchors, targets, None, device, len(formulas[0].anchor_modes))
+            B = int(targets.shape[0])
+            if formula_of.shape[0] != B or (exclude is not None and len(exclude) != B):
+                raise ValueError('rank_ids_mixed: formula_of [B], exclude of B queries')
+            formula_of = formula_of.to(device).contiguous()
+            q = self._embed_mixed(formulas, formula_of, anchors) if B and device.type == 'cuda' else None
+            if q is None:
+                return rank_ids_by_runs(self, formulas, formula_of.cpu().numpy(), anchors, targets, exclude, k)
+            sets = self._rank_mixed_sets(formulas, device)
+            if exclude is not None and not any(ix is exclude.index for ix in sets['indexes']):
+                # once per `formulas` and index: the index numbers the rows of every target mode as the model does
+                for m, host in zip(sets['modes'], sets['rows_host']):
+                    if not np.array_equal(exclude.index.row_ids_host.get(m), host):
+                        raise ValueError('rank_ids_mixed: the index\'s rows of mode %r are not the model\'s' % (m,))
+                sets['indexes'].append(exclude.index)
+            set_of = sets['set_of_group'][formula_of.clamp(0, len(formulas) - 1)]
+            n, base = sets['rows'][set_of], sets['base'][set_of]
+            maps = self.enc.node_maps
+            inside = (targets >= 0) & (targets < maps.shape[0])
+            cand = torch.where(inside, maps[targets.clamp(0, maps.shape[0] - 1)], torch.full_like(targets, -1))
+            ok = (cand >= 0) & (cand < n)
+            ok &= sets['row_ids'][base + torch.minimum(cand.clamp(min=0), n - 1)] == targets
+            target_rows = torch.where(ok, cand, n)
+            bits = None if exclude is None else exclude.bits.to(device)
+            topr, tops, rank, _ = ops.rank_entities_mixed(q, sets['desc'], formula_of, target_rows, bits, k,
+                                                          err=self._error_word(device))
+            self._check()
+            ids = None
+            if topr is not None:
+                ids = torch.where(topr >= 0, sets['row_ids'][base[:, None] + topr.clamp(min=0)], topr)
+        return rank, ids, tops
+
 
 class RGCNEncoderDecoder(nn.Module, _EntityRanking):
     """reference: RGCNEncoderDecoder, model.py:313-494."""
@@ -624,6 +759,23 @@ class RGCNEncoderDecoder(nn.Module, _EntityRanking):
             return q, self.enc.table(formula.target_mode).detach()[:n]
         return self._rank_rows(formula, queries, target_nodes, exclude, k, operands)
 
+    def _rank_operands_ids(self, formula, anchors, n):
+        """rank_ids' operands: the module path's query embeddings of device anchors (as _score_ids encodes them) and the
+        target mode's first n rows"""
+        var_ids, q_graphs = RGCNQueryDataset.get_query_template(formula, anchors.shape[0], self.rel_ids, self.mode_ids)
+        q = self.encode(formula, None, anchors, var_ids, q_graphs)
+        return q, self.enc.table(formula.target_mode).detach()[:n], 'cosine'
+
+    def _embed_mixed(self, formulas, formula_of, anchors):
+        """rank_ids_mixed's query embeddings [B, D] in one ops.rgcn_embed_mixed call, or None where _mixed_ok says the
+        mixed launch does not cover the model"""
+        desc, layers = self._mixed_descriptors(formulas)
+        if desc is None:
+            return None
+        return ops.rgcn_embed_mixed(desc, self.enc.node_maps, self.mode_embeddings.weight,
+                                    [(l.basis, l.root, l.bias) for l in layers], self.readout_str, formula_of, anchors,
+                                    self._error_word(self._device()))
+
     def answer(self, formula, queries, k=10, exclude=None, anchor_ids=None, var_ids=None, q_graphs=None):
         """The k entities of formula.target_mode the model proposes for each query, best first:
         (ids [B, k] int64 global entity ids, scores [B, k] float32), -1 / -inf past the last eligible entity. The score is
@@ -787,6 +939,34 @@ def score_ids_by_runs(model, formulas, formula_of_host, anchors, targets, neg=No
     if out is None:
         out = torch.empty(0, dtype=torch.float32, device=targets.device)
     return out
+
+
+def rank_ids_by_runs(model, formulas, formula_of_host, anchors, targets, exclude=None, k=0):
+    """model.rank_ids over every run of equal formula of a concatenation -> (ranks [B], top-k ids [B, k] or None, top-k
+    scores) of the whole. exclude: a kg.KGAnswersMixed with its bitmaps, or None; a run's answers are the rows of its
+    bitmaps cut to the target mode's words. rank_ids_mixed's fallback (learned readouts, chain types of the GQE model,
+    models without a mixed embedding) and its oracle."""
+    from .kg import KGAnswers, _words
+    B = int(targets.shape[0])
+    ranks, ids, scores = torch.empty(B, dtype=torch.int64, device=targets.device), None, None
+    for f, lo, hi in formula_runs(formula_of_host):
+        if not 0 <= f < len(formulas):
+            raise IndexError('formula index %d outside the %d formulas' % (f, len(formulas)))
+        sub = None
+        if exclude is not None:
+            index, mode = exclude.index, formulas[f].target_mode
+            n = int(index.mode_rows[index.mode_index[mode]])
+            sub = KGAnswers(index, formulas[f], mode, n, exclude.bits[lo:hi, :_words(n)].contiguous(), None,
+                            exclude.counts[:, lo:hi].contiguous())
+        r, i, s = model.rank_ids(formulas[f], anchors[lo:hi], targets[lo:hi], sub, k)
+        ranks = ranks.to(r.device)
+        ranks[lo:hi] = r
+        if i is not None:
+            if ids is None:
+                ids = torch.empty((B, k), dtype=torch.int64, device=i.device)
+                scores = torch.empty((B, k), dtype=torch.float32, device=i.device)
+            ids[lo:hi], scores[lo:hi] = i, s
+    return ranks, ids, scores
 
 
 def margin_loss_ids_by_runs(model, formulas, formula_of, anchors, targets, neg_ids, margin=1):
@@ -1199,12 +1379,13 @@ class QueryEncoderDecoder(nn.Module, _EntityRanking):
             return ops.cosine(anchors.t(), act, q_row=q_row)
         return ops.cosine(self._composed_query(queries, plan).t(), target_embeds.t(), q_row=q_row)
 
-    def _composed_query(self, queries, plan):
-        """[D, B]: an intersection formula's query embeddings from the decoders' own pieces (model.py:84-116)."""
+    def _composed_query(self, queries, plan, anchors=None):
+        """[D, B]: an intersection formula's query embeddings from the decoders' own pieces (model.py:84-116). anchors: the
+        anchor ids [B, A] on the device in place of `queries`."""
         form, branches, imode, tail, emode = plan
         embeds = []
         for slot, mode, steps in branches:
-            e = self.enc(_anchor_ids(queries, slot), mode)
+            e = self.enc(_anchor_ids(queries, slot) if anchors is None else anchors[:, slot].contiguous(), mode)
             for rel, _ in steps:
                 e = self.path_dec.project(e, rel)
             embeds.append(e)
@@ -1241,23 +1422,26 @@ class QueryEncoderDecoder(nn.Module, _EntityRanking):
             hit = self.__dict__['_cand'] = (key, project())
         return hit[1]
 
-    def _rank_operands(self, formula, queries, n):
+    def _rank_operands(self, formula, queries, n, anchors=None):
         """(q [B, D], candidates [n, D], score kind) for ops.rank_entities: that score of (q, candidate) is the one
-        forward() gives the pair."""
+        forward() gives the pair. anchors: the anchor ids [B, A] on the device in place of `queries` (rank_ids)."""
         plan = self._plan(formula)
         form, branches, imode, tail, emode = plan
         enc, device = self.enc, self._device()
         err = self._error_word(device)
-        B = len(queries)
+        B = len(queries) if anchors is None else int(anchors.shape[0])
         fused = self._fused_ok(plan)
         if form == 1:
             if fused:
                 prog, modes, mats = self._programme(plan)
-                p_ids = np.asarray([_anchor_ids(queries, slot) for slot, _, _ in branches], dtype=np.int64).reshape(-1, B)
-                q = ops.gqe_embed(prog, [enc.table(m) for m in modes], mats, enc.node_maps,
-                                  torch.from_numpy(p_ids).to(device), B, err)
+                if anchors is None:
+                    p_ids = np.asarray([_anchor_ids(queries, slot) for slot, _, _ in branches], dtype=np.int64).reshape(-1, B)
+                    p_ids = torch.from_numpy(p_ids).to(device)
+                else:
+                    p_ids = anchors[:, [slot for slot, _, _ in branches]].t().contiguous()
+                q = ops.gqe_embed(prog, [enc.table(m) for m in modes], mats, enc.node_maps, p_ids, B, err)
             else:
-                q = self._composed_query(queries, plan).t()
+                q = self._composed_query(queries, plan, anchors).t()
             return q, enc.table(formula.target_mode).detach()[:n], 'cosine'
         steps = branches[0][2]
         table = enc.table(formula.target_mode).detach()
@@ -1274,10 +1458,23 @@ class QueryEncoderDecoder(nn.Module, _EntityRanking):
                     act = ops.linear(act, self.path_dec.mats[rel].detach().t())
             return act.contiguous()
         cand = self._chain_candidates(plan, n, project)
-        return enc(_anchor_ids(queries, 0), formula.anchor_modes[0]).t(), cand, self._plan_score(plan)
+        first = _anchor_ids(queries, 0) if anchors is None else anchors[:, 0].contiguous()
+        return enc(first, formula.anchor_modes[0]).t(), cand, self._plan_score(plan)
 
     def _rank_all(self, formula, queries, target_nodes, exclude, k):
         return self._rank_rows(formula, queries, target_nodes, exclude, k, lambda n: self._rank_operands(formula, queries, n))
+
+    def _rank_operands_ids(self, formula, anchors, n):
+        return self._rank_operands(formula, None, n, anchors)
+
+    def _embed_mixed(self, formulas, formula_of, anchors):
+        """rank_ids_mixed's query embeddings [B, D] in one ops.gqe_embed_mixed launch, or None: a chain type (its candidates
+        are a projected table per formula, which goes by runs) or formulas the fused kernel does not cover"""
+        desc, (form, branches, imode, tail, emode) = self._mixed_descriptors(formulas)
+        if desc is None or form != 1:
+            return None
+        p_ids = anchors[:, [slot for slot, _, _ in branches]].t().contiguous()
+        return ops.gqe_embed_mixed(desc, self.enc.node_maps, formula_of, p_ids, self._error_word(self._device()))
 
     def answer(self, formula, queries, k=10, exclude=None):
         """The k entities of formula.target_mode the model proposes for each query, best first:

@@ -642,6 +642,107 @@ def rank_entities(q, table, target_rows=None, exclude=None, k=0, eps=1e-8, err=N
     return topr, tops, rank, tsc
 
 
+class RankMixedDescriptors(object):
+    """The device block of mpqe_rank_mixed_desc_build (include/mpqe_amd.h): the candidate sets of a mixed ranking call.
+      tables        one [rows_s, D] float32 tensor per set (raw rows, 16-byte aligned)
+      scores        one of RANK_SCORES per set, or one name for all
+      valid         None, or per set None / an int32 tensor of ceil(rows_s / 32) words (bit r clear: row r is no entity)
+      set_of_group  one set index per group (a query names its group; in evaluation the group is the formula)
+    It holds addresses and sizes only, so it is built once and kept (the tensors are held here, which keeps the
+    addresses theirs); `addresses` lets the owner see that a tensor was replaced."""
+
+    def __init__(self, tables, set_of_group, scores='cosine', valid=None):
+        import ctypes
+        tables = [_f(t.detach(), 'embedding table') for t in tables]
+        if not tables or any(t.dim() != 2 or t.shape[1] != tables[0].shape[1] or t.shape[0] < 1 for t in tables):
+            raise ValueError('rank_entities_mixed: every set a table [rows >= 1, D] with one D')
+        S = len(tables)
+        scores = [scores] * S if isinstance(scores, str) else list(scores)
+        if len(scores) != S or any(s not in RANK_SCORES for s in scores):
+            raise ValueError('rank_entities_mixed: one score of %s per set' % sorted(RANK_SCORES))
+        valid = [None] * S if valid is None else list(valid)
+        if len(valid) != S:
+            raise ValueError('rank_entities_mixed: valid must hold one entry per set')
+        for s, v in enumerate(valid):
+            if v is None:
+                continue
+            valid[s] = v = _need(v, torch.int32, 'valid words')
+            if v.dim() != 1 or v.shape[0] < (tables[s].shape[0] + 31) // 32:
+                raise ValueError('rank_entities_mixed: valid words of set %d: ceil(rows / 32) int32 words' % s)
+        sog = np.ascontiguousarray(set_of_group, dtype=np.int32).reshape(-1)
+        G = int(sog.shape[0])
+        self.tables, self.valid, self.scores = tables, valid, scores
+        self.num_sets, self.num_groups, self.dim = S, G, int(tables[0].shape[1])
+        self.rows = [int(t.shape[0]) for t in tables]
+        self.max_rows, self.total_rows = max(self.rows), sum(self.rows)
+        self.set_of_group = sog
+        dev = tables[0].device
+        L = lib()
+        self.nbytes = L.mpqe_rank_mixed_desc_bytes(S, G)
+        if self.nbytes == 0:
+            raise ValueError('rank_entities_mixed: %d sets / %d groups outside [1, 256] / [1, 2^20]' % (S, G))
+        self.buffer = torch.empty(self.nbytes + 256, dtype=torch.uint8, device=dev)
+        self.ptr = _capi._align256(self.buffer.data_ptr())
+        tab_arr = (ctypes.c_void_p * S)(*[_p(t) for t in tables])
+        val_arr = (ctypes.c_void_p * S)(*[_p(v) for v in valid])
+        rows_arr = (ctypes.c_int64 * S)(*self.rows)
+        kind_arr = (ctypes.c_int32 * S)(*[RANK_SCORES[s] for s in scores])
+        with torch.cuda.device(dev):
+            _ck(L.mpqe_rank_mixed_desc_build(tab_arr, rows_arr, kind_arr, val_arr, S, sog.ctypes.data, G, self.ptr,
+                                             self.nbytes, _stream()), 'mpqe_rank_mixed_desc_build')
+        self.addresses = tuple(t.data_ptr() for t in tables)
+
+
+def rank_entities_mixed(q, desc, group_of, target_rows=None, exclude_bits=None, k=0, eps=1e-8, err=None):
+    """Q query embeddings ranked in ONE call, query i against candidate set desc.set_of_group[group_of[i]]
+    (mpqe_rank_entities_mixed, include/mpqe_amd.h): bit for bit rank_entities over the queries of one set.
+      group_of      [Q] int64 on the device
+      target_rows   [Q] int64 rows of the query's own set, or None
+      exclude_bits  None or [Q, W] int32 words: bit r of row i set = row r is not eligible for query i
+    -> (topk_rows [Q, k], topk_scores [Q, k], rank [Q] or None, target_scores [Q] or None) as rank_entities. A group or a
+    target row out of range ORs MPQE_FLAG_BAD_INDEX into `err`. Inference only."""
+    k = int(k)
+    if k < 0 or k > RANK_MAX_K:
+        raise ValueError('rank_entities_mixed: k must be in [0, %d], got %d' % (RANK_MAX_K, k))
+    if not torch.is_tensor(q) or q.dim() != 2 or q.shape[1] != desc.dim:
+        raise ValueError('rank_entities_mixed: q must be [Q, %d]' % desc.dim)
+    q = _f(q.detach(), 'query embeddings')
+    Q, D = q.shape
+    group_of = _i(group_of, 'group_of')
+    if tuple(group_of.shape) != (Q,):
+        raise ValueError('rank_entities_mixed: group_of must hold one group per query')
+    if target_rows is not None:
+        target_rows = _i(target_rows, 'target_rows')
+        if tuple(target_rows.shape) != (Q,):
+            raise ValueError('rank_entities_mixed: target_rows must hold one row per query')
+    if k == 0 and target_rows is None:
+        raise ValueError('rank_entities_mixed: nothing to compute (k = 0 and no target_rows)')
+    W = 0
+    if exclude_bits is not None:
+        exclude_bits = _need(exclude_bits, torch.int32, 'exclude_bits')
+        if exclude_bits.dim() != 2 or exclude_bits.shape[0] != Q or exclude_bits.shape[1] < 1:
+            raise ValueError('rank_entities_mixed: exclude_bits must be [Q, W >= 1] int32 words')
+        W = int(exclude_bits.shape[1])
+    dev = q.device
+    topr = torch.empty((Q, k), dtype=torch.int64, device=dev) if k else None
+    tops = torch.empty((Q, k), dtype=torch.float32, device=dev) if k else None
+    rank = torch.empty((Q,), dtype=torch.int64, device=dev) if target_rows is not None else None
+    tsc = torch.empty((Q,), dtype=torch.float32, device=dev) if target_rows is not None else None
+    if Q == 0:
+        return topr, tops, rank, tsc
+    with torch.cuda.device(dev):
+        need = lib().mpqe_rank_mixed_workspace_bytes(Q, desc.num_sets, desc.max_rows, desc.total_rows, D, k)
+        if need == 0:
+            raise ValueError('rank_entities_mixed: shape outside what the kernel covers')
+        buf = torch.empty(need + 256, dtype=torch.uint8, device=dev)
+        ws = _capi._align256(buf.data_ptr())
+        _ck(lib().mpqe_rank_entities_mixed(_p(q), Q, D, float(eps), desc.ptr, desc.nbytes, desc.num_sets, desc.num_groups,
+                                           desc.max_rows, desc.total_rows, _p(group_of), _p(target_rows),
+                                           _p(exclude_bits), W, k, _p(topr), _p(tops), _p(rank), _p(tsc), ws, need,
+                                           _p(err), _stream()), 'mpqe_rank_entities_mixed')
+    return topr, tops, rank, tsc
+
+
 class _Hinge(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pos, neg, margin):
@@ -949,6 +1050,23 @@ def gqe_scores_mixed(desc, node_map, formula_of, p_ids, e_ids, qrow, neg_off, n,
                                      int(p_ids.shape[1]), _p(e_ids), int(e_ids.shape[0]), _p(qrow), _p(neg_off), n,
                                      float(eps), _p(scores), _p(err), _stream()), 'mpqe_gqe_fwd_mixed')
     return scores
+
+
+def gqe_embed_mixed(desc, node_map, formula_of, p_ids, err=None):
+    """The rows gqe_scores_mixed would score, [B, D] float32, for queries of DIFFERENT formulas of one intersection type
+    in one launch (mpqe_gqe_embed_mixed, include/mpqe_amd.h): bit for bit gqe_embed run by run. p_ids [branches, B]."""
+    formula_of, p_ids = _i(formula_of, 'formula_of'), _i(p_ids, 'p_ids')
+    node_map = None if node_map is None else _i(node_map, 'node_map')
+    B = int(formula_of.shape[0])
+    if formula_of.dim() != 1 or p_ids.dim() != 2 or p_ids.shape[1] != B:
+        raise ValueError('gqe_embed_mixed: formula_of [B], p_ids [branches, B]')
+    dev = desc.tables[0].device
+    out = torch.empty((B, desc.dim), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _ck(lib().mpqe_gqe_embed_mixed(desc.progs.ctypes.data, desc.num_formulas, desc.ptr, desc.nbytes, _p(node_map),
+                                       0 if node_map is None else node_map.shape[0], desc.dim, _p(formula_of), B, _p(p_ids),
+                                       _p(out), _p(err), _stream()), 'mpqe_gqe_embed_mixed')
+    return out
 
 
 class _GqeScoresMixed(torch.autograd.Function):

@@ -14,6 +14,8 @@ type), loss.backward(), Adam; evaluation by ROC-AUC with one sampled negative pe
     python tools/train_synthetic.py --model gqe --kg small --steps 300 --device-queries   # queries sampled on the device index
     python tools/train_synthetic.py --model gqe --kg small --steps 300 --device-queries --device-eval   # ... and scored there
     python tools/train_synthetic.py --model gqe --kg small --steps 300 --device-queries --device-eval --mixed-eval   # ... by query type
+    python tools/train_synthetic.py --model gqe --kg small --steps 300 --device-queries --device-rank   # filtered MRR / hits@10 on the device sets
+    python tools/train_synthetic.py --model gqe --kg small --steps 300 --device-queries --device-eval --mixed-eval --device-rank   # ... one ranking call a window
     python tools/train_synthetic.py --model gqe --kg small --steps 100 --depth 1 --kg-index    # the neighbourhood encoder, on the index
     python tools/train_synthetic.py --kg small --steps 100 --depth 2 --kg-index                 # ... two layers, under the R-GCN model
 
@@ -151,6 +153,15 @@ def eval_sets(args):
     return args.test_mixed
 
 
+def rank_queries(args, tq, known):
+    """What eval_rank_queries takes as (queries, known_answers): under --device-rank the test QuerySets (grouped by query
+    type under --mixed-eval) and the index they were sampled on -- ranked on the device, the answers computed there --, else
+    the lists of Query and the caller's known answers."""
+    if not getattr(args, 'device_rank', False):
+        return tq, known
+    return eval_sets(args), next(iter(args.test_sets.values())).index
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--kg', default='small')
@@ -192,6 +203,10 @@ def main(argv=None):
     ap.add_argument('--mixed-eval', action='store_true',
                     help='with --device-eval: group the test sets by query type (kg.MixedQuerySet) and score queries of '
                          'different formulas per call -- one launch a window under --model gqe; other sampled negatives')
+    ap.add_argument('--device-rank', action='store_true',
+                    help='with --device-queries: the filtered ranking metrics over the test QuerySets themselves '
+                         '(evaluation.eval_rank_queries on the device route, known answers from the sets\' index); with '
+                         '--mixed-eval over kg.MixedQuerySets: one ranking call a window whatever the formulas')
     ap.add_argument('--mixed-train', action='store_true',
                     help='with --device-queries: train on windows of one query type whatever the formulas '
                          '(kg.MixedQuerySet.take + the model\'s margin_loss_ids_mixed: one mixed forward and one mixed '
@@ -205,6 +220,8 @@ def main(argv=None):
         ap.error('--batched-queries needs --device-queries')
     if args.device_eval and (not args.device_queries or args.depth):
         ap.error('--device-eval needs --device-queries and the embedding-lookup encoder (--depth 0)')
+    if args.device_rank and (not args.device_queries or args.depth):
+        ap.error('--device-rank needs --device-queries and the embedding-lookup encoder (--depth 0)')
     if args.mixed_eval and not args.device_eval:
         ap.error('--mixed-eval needs --device-eval')
     if args.mixed_train and (not args.device_queries or args.depth or
@@ -563,7 +580,8 @@ def run_gqe(args):
         iterators, margin_loss, samplers = mixed_windows(args, model, query_types, device)
     with torch.no_grad():
         auc0, _ = evaluation.eval_auc_queries(model_queries(args, tq), model, batch_size=128, seed=0)
-    rank0 = evaluation.eval_rank_queries(tq, model.eval(), batch_size=128, ks=(10,), known_answers=known)
+    rq, rknown = rank_queries(args, tq, known)
+    rank0 = evaluation.eval_rank_queries(rq, model.eval(), batch_size=128, ks=(10,), known_answers=rknown)
     model.train()
     opt = optim.Adam(model.parameters(), lr=args.lr)
     random.seed(args.seed + 12)
@@ -576,12 +594,14 @@ def run_gqe(args):
     train_s = time.perf_counter() - t0
     with torch.no_grad():
         auc1, _ = evaluation.eval_auc_queries(model_queries(args, tq), model, batch_size=128, seed=0)
-    rank1 = evaluation.eval_rank_queries(tq, model.eval(), batch_size=128, ks=(10,), known_answers=known)
+    rank1 = evaluation.eval_rank_queries(rq, model.eval(), batch_size=128, ks=(10,), known_answers=rknown)
     out = dict(model='gqe', decoder=args.decoder, inter_decoder=args.inter_decoder, kg=args.kg, embed_dim=args.embed_dim,
                batch_size=args.batch_size, steps=args.steps, train_seconds=train_s, loss_first=losses[0],
                loss_last20=float(np.mean(losses[-20:])), auc_before=float(auc0), auc_after=float(auc1),
                filtered_mrr_before=rank0['mrr'], filtered_mrr_after=rank1['mrr'], filtered_hits10_before=rank0['hits@10'],
-               filtered_hits10_after=rank1['hits@10'], known_answers='kg-index' if getattr(args, 'kg_index', False) else 'host',
+               filtered_hits10_after=rank1['hits@10'],
+               known_answers='device-sets' if getattr(args, 'device_rank', False) else
+               'kg-index' if getattr(args, 'kg_index', False) else 'host',
                loss_curve=losses)
     if getattr(args, 'device_eval', False):
         with torch.no_grad():
