@@ -11,6 +11,9 @@ Tolerances: `close` of tests/test_kernels.py (forward rtol 1e-5, gradients rtol 
 assert_array_equal where the operation is exact (max, argmax, min, masks, copies, hinge gradients). Signed zeros compare by
 value (-0.0 == +0.0). Where fp32 atomics add k terms into one address in arbitrary order the bound is the worst case of a
 sequential fp32 sum, k * 2^-24 * sum|term| per address. Every float comparison prints its max abs error and max |ref|.
+
+The optimiser steps of csrc/optim.hip close the file: the grid-stride second trip past the capped grid and the scalar path
+of unaligned buffers, against torch.optim.Adam / SGD on the CPU with the tolerances of tests/test_kernels.py's optimiser tests.
 """
 import numpy as np
 import pytest
@@ -568,6 +571,22 @@ def layernorm_problem(rows, D, relu):
 def test_layernorm_relu_edges(be, D, rows, relu):
     """D = 2 (the smallest with a std), 65 (one trip + 1 lane), 260 and 300 (five trips, 4 and 44 lanes on the last);
     rows 1 / 5 / 9: block tails at 4 rows per block."""
+    check_layernorm(be, D, rows, relu)
+
+
+@pytest.mark.parametrize('relu', [0, 1])
+@pytest.mark.parametrize('D', [64, 65])
+def test_layernorm_relu_column_sums_past_128_partial_rows(be, D, relu):
+    """grad_gamma and grad_beta are column sums through csrc/bias_grad.h. rows = 4097: 129 partial rows, so
+    bias_final_kernel makes a second trip with one row on it; D = 64 takes the 16-byte partial sums (16 row groups per
+    trip, the clamped rows past each block's 32 left out), D = 65 the scalar ones with a second column block of one column."""
+    from tests.test_dense_template_edges import bias_form, bias_num_blocks
+    rows = 4097
+    assert bias_num_blocks(rows) == 129 and bias_form(D) == {64: ('v4', 16), 65: ('scalar', 0)}[D]
+    check_layernorm(be, D, rows, relu)
+
+
+def check_layernorm(be, D, rows, relu):
     x, gamma, beta, gy, y_ref, gx_ref, gg_ref, gb_ref, mean_ref, inv_ref = layernorm_problem(rows, D, relu)
     dx, dg, db, dgy = be.put(x), be.put(gamma), be.put(beta), be.put(gy)
     y, stats = be.empty((rows, D)), be.empty((rows, 2))
@@ -632,3 +651,98 @@ def test_branch_agg(be, branches, agg, count):
     equal(be.get(g1), be.get(gs[1]))
     if branches == 3:
         equal(be.get(g2), be.get(gs[2]))
+
+
+# ------------------------------------------------------------------------------------------ optimiser steps
+def optim_grid(n, per_thread):
+    """csrc/optim.hip: workgroups of 256 threads, `per_thread` elements each, at most 4096 of them"""
+    return max(min(-(-n // (256 * per_thread)), 256 * 16), 1)
+
+
+def at_offset(be, a, off):
+    """`a` on the backend, starting 4 * off bytes past a 16-byte boundary"""
+    buf = be.zeros((a.size + 8,))
+    base = (-(be.ptr(buf) // 4)) % 4 + off
+    view = buf[base:base + a.size]
+    if be.name == 'emu':
+        view[:] = a
+    else:
+        view.copy_(be.torch.from_numpy(a))
+    assert be.ptr(view) % 16 == 4 * off
+    return view
+
+
+def check_adam(be, n, wd, steps, offs, edges):
+    """mpqe_adam_step against torch.optim.Adam on the CPU with tests/test_kernels.py::test_adam_step_matches_torch's
+    tolerances (they come from the reference's arithmetic: a few ulps of p ~ 1, one rounding of an O(3) intermediate); the
+    elements at `edges` are compared one by one on top of the whole arrays. offs: floats past a 16-byte boundary of
+    (param, grad, exp_avg, exp_avg_sq)."""
+    rng = np.random.RandomState(n % 1000 + sum(offs))
+    p0 = rng.randn(n).astype(np.float32)
+    ref = torch.nn.Parameter(torch.from_numpy(p0.copy()))
+    opt = torch.optim.Adam([ref], lr=0.01, weight_decay=wd)
+    zeros = np.zeros(n, np.float32)
+    p, m, v = at_offset(be, p0, offs[0]), at_offset(be, zeros, offs[2]), at_offset(be, zeros, offs[3])
+    for t in range(1, steps + 1):
+        g = (rng.randn(n) * (0.1 if t % 2 else 3.0)).astype(np.float32)
+        ref.grad = torch.from_numpy(g.copy())
+        opt.step()
+        dg = at_offset(be, g, offs[1])
+        be.check(be.lib.mpqe_adam_step(be.ptr(p), be.ptr(dg), be.ptr(m), be.ptr(v), n, 0.01, 0.9, 0.999, 1e-8, wd, t,
+                                       be.stream), 'adam')
+    state = opt.state[ref]
+    for got, want, rtol, atol, what in ((p, ref.detach(), 2e-6, 3e-7, 'param'), (m, state['exp_avg'], 1e-6, 3e-7, 'exp_avg'),
+                                        (v, state['exp_avg_sq'], 2e-6, 1e-9, 'exp_avg_sq')):
+        got, want = be.get(got), want.numpy()
+        for i in edges:
+            np.testing.assert_allclose(got[i], want[i], rtol=rtol, atol=atol, err_msg='%s[%d]' % (what, i))
+        np.testing.assert_allclose(got, want, rtol=rtol, atol=atol, err_msg=what)
+    moved = be.get(p)[list(edges)] != p0[list(edges)]
+    assert moved.all()
+
+
+def test_adam_step_second_grid_stride_trip(be):
+    """n = 4 194 304 + 5: the grid is capped at 4096 workgroups of 1024 elements, so thread 0 makes a second trip with a
+    whole vector on it (elements n - 5 .. n - 2) and thread 1 one whose `i + 3 < n` fails: the scalar tail (element n - 1).
+    Two steps. The emulator takes 2 s: it runs there too.
+    No weight decay here (the scalar-path cases have it): among four million elements some g + wd p cancels down to the
+    size of eps = 1e-8, where the first step's m / (sqrt(v) + eps) magnifies the rounding of that sum a thousandfold. With
+    wd = 1e-3 one element did (g = -5.979811e-4, p = 0.59799045): torch's float32 result lay 7.6e-6 from the float64 one and
+    the kernel's 3.7e-6, which says nothing about either. Without weight decay the sum is g itself, exactly."""
+    n, first = 4194304 + 5, 4096 * 1024
+    assert optim_grid(n, 4) == 4096 and -(-n // 4) == 4096 * 256 + 2          # two threads' worth beyond the first trip
+    check_adam(be, n, 0.0, 2, (0, 0, 0, 0), edges=(0, first - 4, first - 1, first, first + 3, first + 4))
+
+
+ADAM_OFFSETS = {'all': (1, 1, 1, 1), 'param': (1, 0, 0, 0), 'grad': (0, 1, 0, 0), 'exp_avg': (0, 0, 1, 0),
+                'exp_avg_sq': (0, 0, 0, 1)}
+
+
+@pytest.mark.parametrize('which', list(ADAM_OFFSETS))
+def test_adam_step_scalar_path(be, which):
+    """n = 4099 with all four buffers 4 bytes past a 16-byte boundary, then each alone: every term of the host's `vec`
+    sends the call to the scalar loop, whose 5 workgroups (the grid is sized for four elements a thread) make four trips,
+    the last of 259 elements."""
+    n = 4099
+    stride = optim_grid(n, 4) * 256
+    assert stride == 1280 and -(-n // stride) == 4 and n - 3 * stride == 259
+    check_adam(be, n, 1e-3, 3, ADAM_OFFSETS[which], edges=(0, stride - 1, stride, 3 * stride - 1, 3 * stride, n - 1))
+
+
+def test_sgd_step_second_grid_stride_trip(be):
+    """n = 1 048 576 + 3: sgd_kernel's grid is capped at 4096 workgroups of 256 elements, so threads 0 .. 2 make a second
+    trip. Tolerance of tests/test_kernels.py::test_sgd_step_matches_torch. The emulator takes under 1 s: it runs there too."""
+    n, first = 1048576 + 3, 4096 * 256
+    assert optim_grid(n, 1) == 4096 and n - first == 3
+    rng = np.random.RandomState(11)
+    p0, g = rng.randn(n).astype(np.float32), rng.randn(n).astype(np.float32)
+    ref = torch.nn.Parameter(torch.from_numpy(p0.copy()))
+    ref.grad = torch.from_numpy(g.copy())
+    torch.optim.SGD([ref], lr=0.05, momentum=0, weight_decay=1e-2).step()
+    p, dg = be.put(p0), be.put(g)
+    be.check(be.lib.mpqe_sgd_step(be.ptr(p), be.ptr(dg), n, 0.05, 1e-2, be.stream), 'sgd')
+    got, want = be.get(p), ref.detach().numpy()
+    for i in (0, first - 1, first, first + 1, n - 1):
+        np.testing.assert_allclose(got[i], want[i], rtol=1e-6, atol=1e-7, err_msg='param[%d]' % i)
+        assert got[i] != p0[i]
+    np.testing.assert_allclose(got, want, rtol=1e-6, atol=1e-7)
