@@ -76,7 +76,8 @@ def test_tolerance_covers_plain_fp32():
 
 @pytest.mark.parametrize('shape', SHAPES, ids=lambda s: 'Q%d_N%d_D%d_k%d' % s)
 def test_rank_and_topk_by_dot(be, shape):
-    """(67, 700, 48, 10): eleven column tiles, several per strip; k up to 128."""
+    """(67, 700, 48, 10): eleven column tiles, one per strip (eleven strips: tests/test_operand_bounds.py and
+    tests/test_rank_exact.py have the shapes with several tiles per strip); k up to 128."""
     Q, N, D, k = shape
     _, q, table, target = make(100 + Q, Q, N, D)
     s64 = truth(q, table)

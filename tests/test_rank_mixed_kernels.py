@@ -5,13 +5,15 @@ Runs on the host fiber emulator (`emu`, no GPU needed) and on the gfx950 library
 The oracle is the library's own per-table call on the same backend: every output of query i must equal, to the bit, what
 mpqe_rank_entities_scored returns when the queries of i's set are handed to it alone, with the set's score kind and the
 exclusion list "rows of the set whose excl_bits bit is set or whose valid bit is clear". One case is also held against
-float64 with tests/test_rank.py's tolerance and checkers (imported, not copied).
+float64 with tests/test_rank.py's tolerance and checkers (imported, not copied); tests/test_rank_exact.py holds the call,
+bitmaps included, against an int64 oracle that shares nothing with the library.
 
 The main shape: five sets of 1, 63, 64, 65 and 700 rows, Q = 150 interleaved so that the sets get 0, 1, 64, 65 and 20
 queries (an empty set, a one-query block, a full block, a block and a query, a partial block). The block bound is
 150 / 64 + 5 = 7, so the strip rule of rank.hip gives S = 11 strips of one tile for the 700-row set and the narrower sets
-leave most strips empty; test_a_wide_set_several_tiles_per_strip widens a set until a strip of it holds two tiles. Operands sit between NaN fences, the descriptor block and the workspace are exactly the size the size
-functions name and hold garbage.
+leave most strips empty; test_a_wide_set_several_tiles_per_strip widens a set until a strip of it holds two tiles. Operands
+sit between NaN fences; the descriptor block and the workspace are exactly as large as the size functions say and hold
+garbage.
 """
 import ctypes
 
