@@ -45,6 +45,29 @@ __device__ __forceinline__ void flag_error(int32_t *err, int32_t bit) {
     if (err) atomicOr(err, bit);
 }
 
+// entity id -> row of its table through node_map (NULL: the identity map, ids are table rows); -1 and
+// MPQE_FLAG_BAD_NODE_ID (err may be NULL: flagged elsewhere) for an id or a row out of range
+__device__ __forceinline__ long long lookup_row(const long long *node_map, long long map_len, long long id,
+                                                long long table_rows, int32_t *err) {
+    if (!node_map) {
+        if (id < 0 || id >= table_rows) {
+            flag_error(err, MPQE_FLAG_BAD_NODE_ID);
+            return -1;
+        }
+        return id;
+    }
+    if (id < 0 || id >= map_len) {
+        flag_error(err, MPQE_FLAG_BAD_NODE_ID);
+        return -1;
+    }
+    const long long row = node_map[id];
+    if (row < 0 || row >= table_rows) {
+        flag_error(err, MPQE_FLAG_BAD_NODE_ID);
+        return -1;
+    }
+    return row;
+}
+
 // The library's counter-based random stream: splitmix64's finaliser over a counter (mpqe_sample_negatives in optim.hip, the
 // KG samplers in kg_sample.hip). Stateless, restated with Python ints by oracle/ref_cpu.py and tests/kg_sample_oracle.py.
 __host__ __device__ __forceinline__ unsigned long long mpqe_mix64(unsigned long long x) {

@@ -44,27 +44,6 @@ extern "C" int mpqe_collate_template(int query_type, int64_t B, const int64_t *e
 }
 
 // ------------------------------------------------------------------------------------ embedding
-__device__ __forceinline__ long long lookup_row(const long long *node_map, long long map_len, long long id,
-                                                long long table_rows, int32_t *err) {
-    if (!node_map) {                       // identity map: ids are table rows
-        if (id < 0 || id >= table_rows) {
-            flag_error(err, MPQE_FLAG_BAD_NODE_ID);
-            return -1;
-        }
-        return id;
-    }
-    if (id < 0 || id >= map_len) {
-        flag_error(err, MPQE_FLAG_BAD_NODE_ID);
-        return -1;
-    }
-    const long long row = node_map[id];
-    if (row < 0 || row >= table_rows) {
-        flag_error(err, MPQE_FLAG_BAD_NODE_ID);
-        return -1;
-    }
-    return row;
-}
-
 __global__ __launch_bounds__(256) void embed_l2norm_fwd_kernel(
     const float *__restrict__ table, long long table_rows, int D, const long long *__restrict__ node_map,
     long long map_len, const long long *__restrict__ ids, long long n, float *__restrict__ out,

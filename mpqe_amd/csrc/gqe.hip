@@ -43,7 +43,7 @@
 
 #include <new>
 
-#include "gemm_core.h"
+#include "mix_grad_core.h"
 
 #define GQ_ROWS 16
 #define GQ_MAXD 256
@@ -75,27 +75,6 @@ struct GqeDev {
     int32_t *err;
 };
 
-__device__ __forceinline__ long long gq_lookup(const long long *node_map, long long map_len, long long id,
-                                               long long table_rows, int32_t *err) {
-    if (!node_map) {
-        if (id < 0 || id >= table_rows) {
-            flag_error(err, MPQE_FLAG_BAD_NODE_ID);
-            return -1;
-        }
-        return id;
-    }
-    if (id < 0 || id >= map_len) {
-        flag_error(err, MPQE_FLAG_BAD_NODE_ID);
-        return -1;
-    }
-    const long long row = node_map[id];
-    if (row < 0 || row >= table_rows) {
-        flag_error(err, MPQE_FLAG_BAD_NODE_ID);
-        return -1;
-    }
-    return row;
-}
-
 // one table row, L2-normalised, 4 floats per lane (lanes with 4 * lane >= D hold zeros): the arithmetic of row_norm_store
 __device__ __forceinline__ f32x4 gq_norm_row(const float *tab, long long row, int D, int lane) {
     f32x4 q = {0.f, 0.f, 0.f, 0.f};
@@ -116,7 +95,7 @@ __device__ __forceinline__ void gq_gather(const GqeDev &G, float *tile, int LDX,
     for (int i = wave; i < GQ_ROWS; i += 4) {
         const long long r = i0 + i;
         long long row = -1;
-        if (r < R) row = ids ? gq_lookup(G.node_map, G.map_len, ids[r], G.tab_rows[slot], lane == 0 ? G.err : nullptr) : r;
+        if (r < R) row = ids ? lookup_row(G.node_map, G.map_len, ids[r], G.tab_rows[slot], lane == 0 ? G.err : nullptr) : r;
         const f32x4 q = gq_norm_row(G.tab[slot], row, G.D, lane);
         if (lane * 4 < G.D) *reinterpret_cast<f32x4 *>(tile + i * LDX + lane * 4) = q;
     }
@@ -224,7 +203,7 @@ __device__ __forceinline__ f32x4 gq_e_row(const GqeDev &G, long long r, int lane
                 e = -1;
             }
         }
-        if (e >= 0) row = gq_lookup(G.node_map, G.map_len, G.e_ids[e], G.tab_rows[3], lane == 0 ? G.err : nullptr);
+        if (e >= 0) row = lookup_row(G.node_map, G.map_len, G.e_ids[e], G.tab_rows[3], lane == 0 ? G.err : nullptr);
     }
     return gq_norm_row(G.tab[3], row, G.D, lane);
 }
@@ -537,62 +516,33 @@ __global__ __launch_bounds__(256) void gqe_keys_kernel(GqeDev G, long long n_ent
             if (ok) id = G.e_ids[q];
         } else id = G.e_ids[pos];
         if (ok) {
-            const long long row = gq_lookup(G.node_map, G.map_len, id, G.tab_rows[slot], nullptr);     // (flagged by the forward)
+            const long long row = lookup_row(G.node_map, G.map_len, id, G.tab_rows[slot], nullptr);     // (flagged by the forward)
             if (row >= 0) key = ((long long)G.tmode[slot] << 40) | row;
         }
     }
     reinterpret_cast<long long *>(G.ws + G.key_off)[e] = key;
 }
 
-// y = v / |v|: dv = (g - y (y . g)) / |v| per entry; one wave per entry, the first entry of a key sums the key's entries
-__global__ __launch_bounds__(256) void gqe_rows_kernel(GqeDev G, long long n_ent) {
-    const long long e = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (e >= n_ent) return;
-    const long long *keys = reinterpret_cast<const long long *>(G.ws + G.key_off);
-    const long long key = keys[e];
-    if (key < 0) return;
-    float earlier = 0.f;
-    for (long long j0 = 0; j0 < e; j0 += 64) {
-        const long long j = j0 + lane;
-        if (j < e && keys[j] == key) earlier = 1.f;
+// rows_reduce's entries (mix_grad_core.h): keys and GE rows in the workspace, the table and its gradient by the entry's slot
+struct GqeEntries {
+    const GqeDev &G;
+    __device__ __forceinline__ const long long *keys() const { return reinterpret_cast<const long long *>(G.ws + G.key_off); }
+    __device__ __forceinline__ void tables(long long e, long long, const float *&tab, float *&gtab) const {
+        int slot;
+        long long pos, ger;
+        gq_entry(G, e, slot, pos, ger);
+        tab = G.tab[slot];
+        gtab = G.gtab[slot];
     }
-    if (wave_sum(earlier) > 0.f) return;
-    const int D = G.D, c = lane * 4;
-    const long long row = key & ((1ll << 40) - 1);
-    int slot0;
-    long long pos0, ger0;
-    gq_entry(G, e, slot0, pos0, ger0);
-    const float *GE = G.ws + G.ge_off;
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (c < D) v = gload4(G.tab[slot0] + row * D + c);
-    const float nrm = sqrtf(wave_sum(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]));
-    const float inv = 1.f / nrm;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (long long j0 = e; j0 < n_ent; j0 += 64) {
-        const long long j = j0 + lane;
-        const float mine = (j < n_ent && keys[j] == key) ? 1.f : 0.f;
-        if (!(wave_sum(mine) > 0.f)) continue;
-        for (int l = 0; l < 64; ++l) {
-            if (!(__shfl(mine, l, 64) > 0.f)) continue;
-            int slot;
-            long long pos, ger;
-            gq_entry(G, j0 + l, slot, pos, ger);
-            f32x4 g = {0.f, 0.f, 0.f, 0.f};
-            if (c < D) g = gload4(GE + ger * D + c);
-            const float ydotg = wave_sum(v[0] * g[0] + v[1] * g[1] + v[2] * g[2] + v[3] * g[3]) * inv;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) acc[u] += (g[u] - (v[u] / nrm) * ydotg) * inv;
-        }
+    __device__ __forceinline__ const float *grad_row(long long e) const {
+        int slot;
+        long long pos, ger;
+        gq_entry(G, e, slot, pos, ger);
+        return G.ws + G.ge_off + ger * G.D;
     }
-    if (c < D) {
-        float *o = G.gtab[slot0] + row * D + c;
-        f32x4 old = *reinterpret_cast<const f32x4 *>(o);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) old[u] += acc[u];
-        *reinterpret_cast<f32x4 *>(o) = old;
-    }
-}
+};
+
+__global__ __launch_bounds__(256) void gqe_rows_kernel(GqeDev G, long long n_ent) { rows_reduce(GqeEntries{G}, n_ent, G.D); }
 
 // The vector gradients from the workgroups' partial rows (gq_vec_bwd), the house form of bias_grad.h: one workgroup,
 // thread = (row group rg of 4, column); a row group adds every 4th partial row in order (eight loads in flight), the four
@@ -868,6 +818,13 @@ __device__ __forceinline__ long long gq_mix_formula(const GqeDev &G, const long 
     return f < 0 || f >= F ? -1 : f;
 }
 
+// this workgroup's stretch of P rows (mix_find_stretch): workgroup 16 k + j owns the j-th stretch of block k
+__device__ __forceinline__ bool gq_mix_stretch(const GqeDev &G, const long long *__restrict__ fo, long long B, int F,
+                                               long long &first, long long &end, int &fi) {
+    return mix_find_stretch((long long)(blockIdx.x >> 4) * GQ_ROWS, GQ_ROWS, G.Rp, blockIdx.x & 15,
+                            [&](long long r) { return gq_mix_formula(G, fo, B, F, r); }, first, end, fi);
+}
+
 // rows [0, cnt) of a tile -> rows [first, first + cnt) of a [Rp16, D] state: a stretch's own rows (the zero rows that pad
 // its tile belong to a neighbouring stretch's state)
 __device__ __forceinline__ void gq_store_rows(const float *tile, int LDX, float *g, long long first, int cnt, int D) {
@@ -903,25 +860,9 @@ __global__ __launch_bounds__(256) void gqe_fwd_mixed_kernel(GqeDev G, const GqeM
     __shared__ __attribute__((aligned(16))) float lds[3 * GQ_ROWS * GQ_LDXMAX];
     const int D = G.D, LDX = D + 4, per = D / 4;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long base = (long long)(blockIdx.x >> 4) * GQ_ROWS;
-    const int want = blockIdx.x & 15;
-    // the want-th stretch [first, end) of this block (uniform: block index and scalar loads only)
-    int cnt = -1, fi = -1;
-    long long first = base, end = base, prev = -2;
-    for (int i = 0; i < GQ_ROWS; ++i) {
-        const long long r = base + i;
-        if (r >= G.Rp) break;
-        const long long k = gq_mix_formula(G, fo, B, F, r);
-        if (k != prev) {
-            if (cnt == want) break;
-            ++cnt;
-            first = r;
-            fi = (int)k;
-            prev = k;
-        }
-        end = r + 1;
-    }
-    if (cnt != want) return;
+    long long first, end;
+    int fi;
+    if (!gq_mix_stretch(G, fo, B, F, first, end, fi)) return;
     fi = __builtin_amdgcn_readfirstlane(fi);
     if (fi < 0) {
         if (threadIdx.x == 0) flag_error(G.err, MPQE_FLAG_BAD_INDEX);

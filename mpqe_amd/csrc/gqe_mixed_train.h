@@ -21,24 +21,15 @@
 // dY and GE row is bit for bit what mpqe_gqe_bwd computes when the query's run is handed to it alone. The kernel also
 // writes the keys of the looked-up rows it owns (mpqe_gqe_bwd's gqe_keys_kernel).
 //
-// Parameter gradients (gqe_mix_param_kernel): the contributions are sorted stably by parameter index (radix_sort.h; the
-// list starts site-major, row-minor, so a parameter's segment is ordered by site, then row) and a segment is cut into
-// chunks of GQ_MIX_CHUNK consecutive contributions. Workgroup (parameter, strip of 16 gradient rows) walks the parameter's
-// chunks in order: a chunk's outer products are summed in list order on v_mfma_f32_16x16x4_f32 from a zero accumulator
-// (K = the contributions, A / B = the gathered X / dY rows, swapped for a transposed site), the chunk sums are added in
-// chunk order, and the total is added to the caller's buffer by the one workgroup that owns the strip. The chunk pass
-// and the pass over the chunk sums are ONE launch: the chunks of a segment are walked by the workgroups that own the
-// parameter, so there are no partial matrices in memory; the order of every addition is the one two launches would have.
-// A vector parameter is the same with rows in place of outer products (one workgroup, a thread per column). No float
-// atomics: every order is a function of (formula_of, programmes) alone.
+// Parameter gradients (gqe_mix_param_kernel; mix_grad_core.h's param_reduce / vec_reduce with chunks of
+// MPQE_GQE_MIX_GRAD_CHUNK): the key is the parameter index; the list starts site-major, row-minor, so a parameter's
+// segment is ordered by site, then row. A matrix contribution's A / B rows are its X / dY rows, swapped for a transposed
+// site; a vector contribution's row is its dY row (the term). Every order is a function of (formula_of, programmes) alone.
 //
-// Table rows (gqe_rows_mixed_kernel): gqe_rows_kernel's leader scan over the window's entries (branch sources in branch
-// order, then the E row of every pair): the first entry of a key sums the key's entries in entry order and adds the sum
-// to the table gradient, one writer per row.
+// Table rows (gqe_rows_mixed_kernel; rows_reduce): the entries are the branch sources in branch order, then the E row of
+// every pair, as in mpqe_gqe_bwd, with the table of every entry and the gradient buffer of every table index.
 #pragma once
 #include "radix_sort.h"
-
-#define GQ_MIX_CHUNK MPQE_GQE_MIX_GRAD_CHUNK
 
 struct GqeMixIdx {
     int tab[4];             // table index of the branch sources and of the E side (-1: slot unused)
@@ -64,34 +55,11 @@ struct GqeMixLayout {
     size_t sort_off, total;
 };
 
-// the want-th maximal stretch [first, end) of one formula in block `base` -> its formula (-1: out of range), or false
-__device__ __forceinline__ bool gq_mix_stretch(const GqeDev &G, const long long *__restrict__ fo, long long B, int F,
-                                               long long base, int want, long long &first, long long &end, int &fi) {
-    int cnt = -1;
-    long long prev = -2;
-    first = end = base;
-    fi = -1;
-    for (int i = 0; i < GQ_ROWS; ++i) {
-        const long long r = base + i;
-        if (r >= G.Rp) break;
-        const long long k = gq_mix_formula(G, fo, B, F, r);
-        if (k != prev) {
-            if (cnt == want) break;
-            ++cnt;
-            first = r;
-            fi = (int)k;
-            prev = k;
-        }
-        end = r + 1;
-    }
-    return cnt == want;
-}
-
 // the key of a looked-up row: (table index << 40) | row; -1 where the table wants no gradient or the id is bad
 __device__ __forceinline__ long long gq_mix_key(const GqeDev &G, const GqeMixTrain &Tn, int tidx, int slot, long long id) {
     float *const *gt = reinterpret_cast<float *const *>(G.ws + Tn.ptr_off);
     if (tidx < 0 || tidx >= Tn.num_tables || !gt[tidx]) return -1;
-    const long long row = gq_lookup(G.node_map, G.map_len, id, G.tab_rows[slot], nullptr);      // (flagged by the forward)
+    const long long row = lookup_row(G.node_map, G.map_len, id, G.tab_rows[slot], nullptr);      // (flagged by the forward)
     return row < 0 ? -1 : (((long long)tidx << 40) | row);
 }
 
@@ -141,7 +109,7 @@ __global__ __launch_bounds__(256) void gqe_bwd_mixed_kernel(GqeDev G, GqeMixTrai
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     long long first, end;
     int fi;
-    if (!gq_mix_stretch(G, Tn.fo, Tn.B, Tn.F, (long long)(blockIdx.x >> 4) * GQ_ROWS, blockIdx.x & 15, first, end, fi)) return;
+    if (!gq_mix_stretch(G, Tn.fo, Tn.B, Tn.F, first, end, fi)) return;
     fi = __builtin_amdgcn_readfirstlane(fi);
     if (fi < 0) {
         // (no state, no contribution, no entry: the contributions' keys and the entries' keys say so)
@@ -279,54 +247,17 @@ __global__ __launch_bounds__(256) void gqe_bwd_mixed_kernel(GqeDev G, GqeMixTrai
     }
 }
 
-// y = v / |v|: dv = (g - y (y . g)) / |v| per entry; one wave per entry, the first entry of a key sums the key's entries
-// in entry order (gqe_rows_kernel with the table of every entry and the gradient buffer of every table index)
+// mpqe_gqe_bwd's entries with the table of every entry and the gradient buffer of every table index
+struct GqeMixEntries : GqeEntries {
+    const GqeMixTrain &Tn;
+    __device__ __forceinline__ void tables(long long e, long long key, const float *&tab, float *&gtab) const {
+        tab = reinterpret_cast<const float *const *>(G.ws + Tn.etab_off)[e];
+        gtab = reinterpret_cast<float *const *>(G.ws + Tn.ptr_off)[key >> 40];
+    }
+};
+
 __global__ __launch_bounds__(256) void gqe_rows_mixed_kernel(GqeDev G, GqeMixTrain Tn, long long n_ent) {
-    const long long e = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (e >= n_ent) return;
-    const long long *keys = reinterpret_cast<const long long *>(G.ws + G.key_off);
-    const long long key = keys[e];
-    if (key < 0) return;
-    float earlier = 0.f;
-    for (long long j0 = 0; j0 < e; j0 += 64) {
-        const long long j = j0 + lane;
-        if (j < e && keys[j] == key) earlier = 1.f;
-    }
-    if (wave_sum(earlier) > 0.f) return;
-    const int D = G.D, c = lane * 4;
-    const long long row = key & ((1ll << 40) - 1);
-    const float *tab = reinterpret_cast<const float *const *>(G.ws + Tn.etab_off)[e];
-    float *gtab = reinterpret_cast<float *const *>(G.ws + Tn.ptr_off)[key >> 40];
-    const float *GE = G.ws + G.ge_off;
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (c < D) v = gload4(tab + row * D + c);
-    const float nrm = sqrtf(wave_sum(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]));
-    const float inv = 1.f / nrm;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (long long j0 = e; j0 < n_ent; j0 += 64) {
-        const long long j = j0 + lane;
-        const float mine = (j < n_ent && keys[j] == key) ? 1.f : 0.f;
-        if (!(wave_sum(mine) > 0.f)) continue;
-        for (int l = 0; l < 64; ++l) {
-            if (!(__shfl(mine, l, 64) > 0.f)) continue;
-            int slot;
-            long long pos, ger;
-            gq_entry(G, j0 + l, slot, pos, ger);
-            f32x4 g = {0.f, 0.f, 0.f, 0.f};
-            if (c < D) g = gload4(GE + ger * D + c);
-            const float ydotg = wave_sum(v[0] * g[0] + v[1] * g[1] + v[2] * g[2] + v[3] * g[3]) * inv;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) acc[u] += (g[u] - (v[u] / nrm) * ydotg) * inv;
-        }
-    }
-    if (c < D) {
-        float *o = gtab + row * D + c;
-        f32x4 old = *reinterpret_cast<const f32x4 *>(o);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) old[u] += acc[u];
-        *reinterpret_cast<f32x4 *>(o) = old;
-    }
+    rows_reduce(GqeMixEntries{{G}, Tn}, n_ent, G.D);
 }
 
 // contribution c = (slot k, P row): its parameter (num_mats: none) and (c << 1) | transposition
@@ -347,19 +278,30 @@ __global__ __launch_bounds__(256) void gqe_mix_ckeys_kernel(GqeDev G, GqeMixTrai
     reinterpret_cast<int *>(G.ws + Tn.cval_off)[c] = (int)((c << 1) | T);
 }
 
-// seg[k] = [first, end) of parameter k in the sorted list (cleared before)
 __global__ __launch_bounds__(256) void gqe_mix_seg_kernel(GqeDev G, GqeMixTrain Tn) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= Tn.NC) return;
-    const unsigned *skey = reinterpret_cast<const unsigned *>(G.ws + Tn.skey_off);
-    int *seg = reinterpret_cast<int *>(G.ws + Tn.seg_off);
-    const unsigned k = skey[i];
-    if (k >= (unsigned)Tn.num_mats) return;
-    if (i == 0 || skey[i - 1] != k) seg[2 * k] = (int)i;
-    if (i == Tn.NC - 1 || skey[i + 1] != k) seg[2 * k + 1] = (int)(i + 1);
+    mix_seg(reinterpret_cast<const unsigned *>(G.ws + Tn.skey_off), reinterpret_cast<int *>(G.ws + Tn.seg_off), Tn.NC,
+            (unsigned)Tn.num_mats);
 }
 
-// workgroup = (parameter, strip of 16 gradient rows); see the head of this file
+// sorted value = (contribution number (slot k, P row) << 1) | transposition -> its rows of X[k] and dY[k]
+struct GqeMixContrib {
+    const float *S;
+    unsigned Rp;
+    long long blk;
+    int D;
+    __device__ __forceinline__ void rows(unsigned val, const float *&A, const float *&B) const {
+        const unsigned ci = val >> 1, k = ci / Rp, row = ci % Rp;
+        const float *X = S + 2ll * k * blk + (long long)row * D, *dY = X + blk;
+        A = (val & 1u) ? dY : X;
+        B = (val & 1u) ? X : dY;
+    }
+    __device__ __forceinline__ const float *term(unsigned val) const {
+        const unsigned ci = val >> 1, k = ci / Rp, row = ci % Rp;
+        return S + (2ll * k + 1) * blk + (long long)row * D;
+    }
+};
+
+// workgroup = (parameter, strip of 16 gradient rows); a vector: the workgroup of strip 0
 __global__ __launch_bounds__(256) void gqe_mix_param_kernel(GqeDev G, GqeMixTrain Tn) {
     const int D = G.D, nstrip = D / 16;
     const int par = blockIdx.x / nstrip, rs = blockIdx.x % nstrip;
@@ -369,62 +311,12 @@ __global__ __launch_bounds__(256) void gqe_mix_param_kernel(GqeDev G, GqeMixTrai
     const int lo = seg[2 * par], hi = seg[2 * par + 1];
     if (lo >= hi) return;
     const int *sval = reinterpret_cast<const int *>(G.ws + Tn.sval_off);
-    const unsigned Rp = (unsigned)G.Rp;
-    const float *S = G.ws;
-    if ((Tn.vecmask >> (((unsigned)sval[lo] >> 1) / Rp)) & 1u) {
-        // a vector: thread = column, the rows' terms in list order
-        if (rs != 0 || (int)threadIdx.x >= D) return;
-        float tot = 0.f;
-        for (int c0 = lo; c0 < hi; c0 += GQ_MIX_CHUNK) {
-            const int ce = c0 + GQ_MIX_CHUNK < hi ? c0 + GQ_MIX_CHUNK : hi;
-            float acc = 0.f;
-            for (int c = c0; c < ce; ++c) {
-                const unsigned ci = (unsigned)sval[c] >> 1, k = ci / Rp, row = ci % Rp;
-                acc += S[(2ll * k + 1) * Tn.blk + (long long)row * D + threadIdx.x];
-            }
-            tot += acc;
-        }
-        g[threadIdx.x] += tot;
+    const GqeMixContrib C = {G.ws, (unsigned)G.Rp, Tn.blk, D};
+    if ((Tn.vecmask >> (((unsigned)sval[lo] >> 1) / C.Rp)) & 1u) {
+        if (rs == 0) vec_reduce<MPQE_GQE_MIX_GRAD_CHUNK>(lo, hi, g, D, sval, C);
         return;
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int j = lane & 15, kq = lane >> 4;
-    if (wave >= nstrip) return;
-    f32x4 tot[4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) tot[m] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int c0 = lo; c0 < hi; c0 += GQ_MIX_CHUNK) {
-        const int ce = c0 + GQ_MIX_CHUNK < hi ? c0 + GQ_MIX_CHUNK : hi;
-        f32x4 acc[4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
-        for (int c = c0; c < ce; c += 4) {
-            // lane group kq feeds contribution c + kq (past the chunk: zeros)
-            float a = 0.f, b[4] = {0.f, 0.f, 0.f, 0.f};
-            if (c + kq < ce) {
-                const unsigned val = (unsigned)sval[c + kq], ci = val >> 1, k = ci / Rp, row = ci % Rp;
-                const float *X = S + 2ll * k * Tn.blk + (long long)row * D, *dY = X + Tn.blk;
-                const float *A = (val & 1u) ? dY : X, *Bp = (val & 1u) ? X : dY;
-                a = gload1(A + 16 * rs + j);
-#pragma unroll
-                for (int m = 0; m < 4; ++m)
-                    if (wave + 4 * m < nstrip) b[m] = gload1(Bp + 16 * (wave + 4 * m) + j);
-            }
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-                if (wave + 4 * m < nstrip) acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b[m], acc[m], 0, 0, 0);
-        }
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) tot[m][r] += acc[m][r];
-    }
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        if (wave + 4 * m >= nstrip) continue;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) g[(long long)(16 * rs + 4 * kq + r) * D + 16 * (wave + 4 * m) + j] += tot[m][r];
-    }
+    param_reduce<MPQE_GQE_MIX_GRAD_CHUNK>(lo, hi, rs, g, D, sval, C);
 }
 
 // ------------------------------------------------------------------------------------------------ host side
@@ -440,29 +332,18 @@ extern "C" int mpqe_gqe_mixed_index_build(const int32_t *progs_host, int64_t num
     if (!progs_host || num_tables < 1 || num_mats < 0 || !index) return MPQE_ERR_INVALID_ARG;
     if (num_formulas < 1 || num_formulas >= ((int64_t)1 << 24)) return MPQE_ERR_INVALID_ARG;
     if ((uintptr_t)index % 256 != 0) return MPQE_ERR_INVALID_ARG;
-    GqeMixIdx *image = new (std::nothrow) GqeMixIdx[(size_t)num_formulas];
-    if (!image) return MPQE_ERR_INVALID_ARG;
-    int st = MPQE_OK;
-    for (int64_t f = 0; f < num_formulas && st == MPQE_OK; ++f) {
-        const int32_t *prog = progs_host + f * MPQE_GQE_PROG_INTS;
-        GqeHost H;
-        st = gqe_plan(prog, num_tables, num_mats, dim, 1, 1, 1, &H);
-        if (st != MPQE_OK) break;
-        if (!gqe_mixed_same_shape(progs_host, prog)) {
-            st = MPQE_ERR_INVALID_ARG;
-            break;
+    return mix_upload<GqeMixIdx>(index, (size_t)num_formulas, as_stream(stream), [&](GqeMixIdx *image) -> int {
+        for (int64_t f = 0; f < num_formulas; ++f) {
+            const int32_t *prog = progs_host + f * MPQE_GQE_PROG_INTS;
+            GqeHost H;
+            const int st = gqe_plan(prog, num_tables, num_mats, dim, 1, 1, 1, &H);
+            if (st != MPQE_OK) return st;
+            if (!gqe_mixed_same_shape(progs_host, prog)) return MPQE_ERR_INVALID_ARG;
+            for (int t = 0; t < 4; ++t) image[f].tab[t] = t < 3 && t >= H.G.nb ? -1 : H.G.tmode[t];
+            for (int s = 0; s < GQ_SITES; ++s) image[f].par[s] = H.site_mat[s];
         }
-        for (int t = 0; t < 4; ++t) image[f].tab[t] = t < 3 && t >= H.G.nb ? -1 : H.G.tmode[t];
-        for (int s = 0; s < GQ_SITES; ++s) image[f].par[s] = H.site_mat[s];
-    }
-    if (st == MPQE_OK && index_bytes < gqe_mixed_index_size(num_formulas)) st = MPQE_ERR_WORKSPACE;
-    if (st == MPQE_OK &&
-        hipMemcpyAsync(index, image, (size_t)num_formulas * sizeof(GqeMixIdx), hipMemcpyHostToDevice, as_stream(stream)) !=
-            hipSuccess)
-        st = MPQE_ERR_LAUNCH;
-    // (the copy reads pageable memory: it has left `image` when the call returns)
-    delete[] image;
-    return st;
+        return index_bytes < gqe_mixed_index_size(num_formulas) ? MPQE_ERR_WORKSPACE : MPQE_OK;
+    });
 }
 
 // the shared programme + sizes -> device record and the training workspace's layout
@@ -664,26 +545,19 @@ extern "C" int mpqe_gqe_bwd_mixed(const int32_t *prog_host, int64_t num_formulas
     GqeMixTrain &Tn = L.Tn;
     Tn.idx = reinterpret_cast<const GqeMixIdx *>(index);
     bool any_table = false, any_mat = false;
-    for (int t = 0; t < num_tables; ++t) {
-        if ((uintptr_t)grad_tables_host[t] % 16 != 0) return MPQE_ERR_INVALID_ARG;
-        any_table = any_table || grad_tables_host[t];
-    }
-    for (int m = 0; m < num_mats; ++m) {
-        if ((uintptr_t)grad_mats_host[m] % 16 != 0) return MPQE_ERR_INVALID_ARG;
-        any_mat = any_mat || grad_mats_host[m];
-    }
     hipStream_t s = as_stream(stream);
     char *wsb = reinterpret_cast<char *>(workspace);
-    // the gradient buffers' addresses: one copy from a host image
-    const size_t np = (size_t)num_tables + (size_t)num_mats;
-    float **image = new (std::nothrow) float *[np];
-    if (!image) return MPQE_ERR_INVALID_ARG;
-    for (int t = 0; t < num_tables; ++t) image[t] = grad_tables_host[t];
-    for (int m = 0; m < num_mats; ++m) image[num_tables + m] = grad_mats_host[m];
-    const hipError_t ce = hipMemcpyAsync(wsb + Tn.ptr_off * 4, image, np * sizeof(float *), hipMemcpyHostToDevice, s);
-    // (the copy reads pageable memory: it has left `image` when the call returns)
-    delete[] image;
-    if (ce != hipSuccess) return MPQE_ERR_LAUNCH;
+    st = mix_upload_grad_ptrs(wsb + Tn.ptr_off * 4, (size_t)num_tables + (size_t)num_mats, s, [&](float **image) {
+        for (int t = 0; t < num_tables; ++t) {
+            image[t] = grad_tables_host[t];
+            any_table = any_table || image[t];
+        }
+        for (int m = 0; m < num_mats; ++m) {
+            image[num_tables + m] = grad_mats_host[m];
+            any_mat = any_mat || image[num_tables + m];
+        }
+    });
+    if (st != MPQE_OK) return st;
     // (every entry a stretch of a valid formula does not own: key -1)
     if (hipMemsetAsync(wsb + G.key_off * 4, 0xFF, (size_t)L.n_ent * 8, s) != hipSuccess) return MPQE_ERR_LAUNCH;
     const dim3 grid((unsigned)(G.Rp16 / GQ_ROWS * 16));

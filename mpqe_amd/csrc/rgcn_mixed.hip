@@ -19,6 +19,7 @@
 
 #include <new>
 
+#include "mix_grad_core.h"
 #include "rgcn_template_body.h"
 
 #define RM_PASSES 4
@@ -48,26 +49,14 @@ struct RgcnMixArgs {
     int32_t *err;
 };
 
-// embed_l2norm_fwd_kernel's lookup (encoder_ops.hip)
-__device__ __forceinline__ long long rm_lookup_row(const long long *node_map, long long map_len, long long id,
-                                                   long long table_rows, int32_t *err) {
-    if (!node_map) {
-        if (id < 0 || id >= table_rows) {
-            flag_error(err, MPQE_FLAG_BAD_NODE_ID);
-            return -1;
-        }
-        return id;
-    }
-    if (id < 0 || id >= map_len) {
-        flag_error(err, MPQE_FLAG_BAD_NODE_ID);
-        return -1;
-    }
-    const long long row = node_map[id];
-    if (row < 0 || row >= table_rows) {
-        flag_error(err, MPQE_FLAG_BAD_NODE_ID);
-        return -1;
-    }
-    return row;
+// this workgroup's stretch of queries (mix_find_stretch): workgroup RM_STRETCHES k + j owns the j-th stretch of block k
+__device__ __forceinline__ bool rm_stretch(const RgcnMixArgs &G, long long &first, long long &end, int &fi) {
+    return mix_find_stretch((long long)(blockIdx.x / RM_STRETCHES) * GT_BM, GT_BM, G.Q, blockIdx.x % RM_STRETCHES,
+                            [&](long long q) {
+                                const long long k = G.fo[q];
+                                return k < 0 || k >= G.F ? -1 : k;
+                            },
+                            first, end, fi);
 }
 
 // SAVE (mpqe_rgcn_fwd_mixed_save, rgcn_mixed_train.h): every pass keeps its state -- pass p reads S[p] and writes S[p + 1],
@@ -76,26 +65,9 @@ template <int MODE, int SAVE = 0>
 __global__ __launch_bounds__(256) void rgcn_mixed_encode_kernel(RgcnMixArgs G, RgcnMixLayers W) {
     __shared__ __attribute__((aligned(16))) float smem[GT_SMEM_FLOATS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long base = (long long)(blockIdx.x / RM_STRETCHES) * GT_BM;
-    const int want = blockIdx.x % RM_STRETCHES;
-    // the want-th stretch [first, end) of this block (uniform: block index and scalar loads only)
-    int cnt = -1, fi = -1;
-    long long first = base, end = base, prev = -2;
-    for (int i = 0; i < GT_BM; ++i) {
-        const long long q = base + i;
-        if (q >= G.Q) break;
-        long long k = G.fo[q];
-        if (k < 0 || k >= G.F) k = -1;
-        if (k != prev) {
-            if (cnt == want) break;
-            ++cnt;
-            first = q;
-            fi = (int)k;
-            prev = k;
-        }
-        end = q + 1;
-    }
-    if (cnt != want) return;
+    long long first, end;
+    int fi;
+    if (!rm_stretch(G, first, end, fi)) return;
     fi = __builtin_amdgcn_readfirstlane(fi);
     const int D = G.D, N = G.tp.N, A = G.A;
     const int Bs = __builtin_amdgcn_readfirstlane((int)(end - first));
@@ -126,7 +98,7 @@ __global__ __launch_bounds__(256) void rgcn_mixed_encode_kernel(RgcnMixArgs G, R
     for (int r = wave; r < Bs * A; r += 4) {
         const int b = r / A, a = r - b * A;
         const long long rows = M->arows[a];
-        const long long row = rm_lookup_row(G.node_map, G.map_len, G.anchors[(first + b) * A + a], rows, lane == 0 ? G.err : nullptr);
+        const long long row = lookup_row(G.node_map, G.map_len, G.anchors[(first + b) * A + a], rows, lane == 0 ? G.err : nullptr);
         float *o = cur + ((long long)b * N + a) * D;
         if (row < 0) {
             for (int c = lane; c < D; c += 64) o[c] = 0.f;
@@ -185,14 +157,11 @@ __global__ __launch_bounds__(256) void rgcn_mixed_encode_kernel(RgcnMixArgs G, R
     }
 }
 
-__global__ __launch_bounds__(256) void rgcn_mixed_score_kernel(RgcnMixArgs G, const long long *__restrict__ ids,
-                                                               const long long *__restrict__ qrow, long long n, float eps,
-                                                               float *__restrict__ scores) {
-    const long long i = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= n) return;
+// pair i of query q by one wave: the cosine of q_out[q] and the id's normalised table row (pair_cosine; the final
+// expression is cosine_fwd_kernel's); a query or a formula out of range flags MPQE_FLAG_BAD_INDEX and scores 0
+__device__ __forceinline__ void rm_score_pair(const RgcnMixArgs &G, const long long *__restrict__ ids, long long i, long long q,
+                                              float eps, float *__restrict__ scores) {
     const int lane = threadIdx.x & 63;
-    const int D = G.D;
-    const long long q = qrow[i];
     long long f = -1;
     if (q >= 0 && q < G.Q) f = G.fo[q];
     if (f < 0 || f >= G.F) {
@@ -203,35 +172,17 @@ __global__ __launch_bounds__(256) void rgcn_mixed_score_kernel(RgcnMixArgs G, co
         return;
     }
     const RgcnMixDesc *M = G.desc + f;
-    const long long row = rm_lookup_row(G.node_map, G.map_len, ids[i], M->trows, lane == 0 ? G.err : nullptr);
-    const float *v = M->ttab + (row < 0 ? 0 : row) * D;
-    // row_norm_store's norm (16-byte form); a bad id's row is zeros and is not read
-    float nrm = 1.f;
-    if (row >= 0) {
-        float ss = 0.f;
-        for (int c = lane * 4; c < D; c += 256) {
-            f32x4 u = *reinterpret_cast<const f32x4 *>(v + c);
-            ss += u[0] * u[0] + u[1] * u[1] + u[2] * u[2] + u[3] * u[3];
-        }
-        ss = wave_sum(ss);
-        nrm = sqrtf(ss);
-    }
-    // cosine_fwd_kernel over the normalised row
-    const float *qi = G.q_out + q * D;
-    float dot = 0.f, qq = 0.f, tt = 0.f;
-    for (int c = lane; c < D; c += 64) {
-        const float a = qi[c];
-        float b = 0.f;
-        if (row >= 0) b = v[c] / nrm;
-        dot += a * b;
-        qq += a * a;
-        tt += b * b;
-    }
-    dot = wave_sum(dot);
-    qq = wave_sum(qq);
-    tt = wave_sum(tt);
-    const float nq = fmaxf(sqrtf(qq), eps), nt = fmaxf(sqrtf(tt), eps);
-    if (lane == 0) scores[i] = dot / (nq * nt);
+    const long long row = lookup_row(G.node_map, G.map_len, ids[i], M->trows, lane == 0 ? G.err : nullptr);
+    const PairCosine p = pair_cosine(G.q_out + q * G.D, M->ttab, row, G.D, lane);
+    const float nq = fmaxf(sqrtf(p.qq), eps), nt = fmaxf(sqrtf(p.tt), eps);
+    if (lane == 0) scores[i] = p.dot / (nq * nt);
+}
+
+__global__ __launch_bounds__(256) void rgcn_mixed_score_kernel(RgcnMixArgs G, const long long *__restrict__ ids,
+                                                               const long long *__restrict__ qrow, long long n, float eps,
+                                                               float *__restrict__ scores) {
+    const long long i = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i < n) rm_score_pair(G, ids, i, qrow[i], eps, scores);
 }
 
 // ------------------------------------------------------------------------------------ host side

@@ -1,6 +1,6 @@
 // Training on R-GCN queries of different formulas at once: mpqe_rgcn_fwd_mixed_save and mpqe_rgcn_bwd_mixed
 // (include/mpqe_amd.h). Included by rgcn_mixed.hip after the mixed forward (RgcnMixDesc, RgcnMixArgs, RgcnMixLayers,
-// rm_lookup_row and rgcn_mixed_encode_kernel<MODE, 1> are its). The structure is gqe_mixed_train.h's.
+// rm_stretch, rm_score_pair and rgcn_mixed_encode_kernel<MODE, 1> are its). The reductions are mix_grad_core.h's.
 //
 // The workspace (mpqe_rgcn_mixed_train_workspace_bytes; every block a multiple of 256 bytes), Q queries, n pairs, N node
 // slots, P passes:
@@ -20,26 +20,22 @@
 //                                 sort's scratch
 // A stretch writes only the rows of its own queries; a row of a query without qok is never read.
 //
-// State gradients (rgcn_bwd_mixed_kernel), one launch, a workgroup per stretch found as rgcn_mixed_encode_kernel finds it:
-// the cosine backward of the stretch's pairs, a pair per wave (cosine_bwd_kernel's expressions over the row normalised in
-// registers), then per query the sum of its pairs' terms in the order target, negatives in CSR order; the readout backward
-// (readout_bwd_kernel's; max: the lowest node on ties, from S[P]); per pass from the last one tmpl_bwd_x_tile call per
-// node slot and 64-column tile with B = the stretch length and b0 = 0; the keys of the entries the stretch owns.
+// State gradients (rgcn_bwd_mixed_kernel), one launch, a workgroup per stretch: the cosine backward of the stretch's pairs,
+// a pair per wave (cosine_bwd_kernel's expressions over pair_cosine's sums), then per query the sum of its pairs' terms in
+// the order target, negatives in CSR order; the readout backward (readout_bwd_kernel's; max: the lowest node on ties, from
+// S[P]); per pass from the last one tmpl_bwd_x_tile call per node slot and 64-column tile with B = the stretch length and
+// b0 = 0; the keys of the entries the stretch owns.
 //
-// Parameter gradients: contribution c = slot * Q + query, the slots per pass the template's edges in edge order then the
-// node slots (the root term), after all passes the variable slots (the mode embeddings). Keys: layer * (R + 1) + relation
-// (R: the root), then KP + mode-embedding row, then "none" (a query without qok, a slot the target-message skip left
-// out). Sorted stably (radix_sort.h), so a segment is in (pass, slot, query) order; a segment is cut into chunks of
-// RT_CHUNK consecutive contributions, a chunk is summed in list order from a zero accumulator (matrices: on
-// v_mfma_f32_16x16x4_f32 with the gathered S / G rows as A / B; vectors: a thread per column), the chunk sums are added in
-// chunk order, and the one workgroup that owns the strip adds the total to the caller's buffer. The bias of a layer is
-// the column sum of the G rows of its root segment. No float atomics.
+// Parameter gradients (param_reduce / vec_reduce with chunks of MPQE_RGCN_MIX_GRAD_CHUNK): contribution c = slot * Q +
+// query, the slots per pass the template's edges in edge order then the node slots (the root term), after all passes the
+// variable slots (the mode embeddings). Keys: layer * (R + 1) + relation (R: the root), then KP + mode-embedding row, then
+// "none" (a query without qok, a slot the target-message skip left out). The sort is stable, so a segment is in (pass,
+// slot, query) order. A matrix contribution's A / B rows are its S / G rows; the bias of a layer is the column sum of the
+// G rows of its root segment, a mode-embedding row that of the G[0] rows of its variable slots.
 //
-// Table rows (rgcn_rows_mixed_kernel): gqe_rows_mixed_kernel's leader scan and arithmetic over the entries.
+// Table rows (rgcn_rows_mixed_kernel; rows_reduce): the entries' gradient rows are the anchors' rows of G[0], then GE.
 #pragma once
 #include "radix_sort.h"
-
-#define RT_CHUNK MPQE_RGCN_MIX_GRAD_CHUNK
 
 struct RgcnMixIdx {
     int atab[3];        // table index of every anchor slot
@@ -93,54 +89,14 @@ __global__ __launch_bounds__(256) void rgcn_mixed_score_off_kernel(RgcnMixArgs G
                                                                    const long long *__restrict__ neg_off, long long n,
                                                                    float eps, float *__restrict__ scores) {
     const long long i = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= n) return;
-    const int lane = threadIdx.x & 63;
-    const int D = G.D;
-    const long long q = i < G.Q ? i : rt_query_of(neg_off, G.Q, i - G.Q);
-    long long f = -1;
-    if (q >= 0 && q < G.Q) f = G.fo[q];
-    if (f < 0 || f >= G.F) {
-        if (lane == 0) {
-            flag_error(G.err, MPQE_FLAG_BAD_INDEX);
-            scores[i] = 0.f;
-        }
-        return;
-    }
-    const RgcnMixDesc *M = G.desc + f;
-    const long long row = rm_lookup_row(G.node_map, G.map_len, ids[i], M->trows, lane == 0 ? G.err : nullptr);
-    const float *v = M->ttab + (row < 0 ? 0 : row) * D;
-    float nrm = 1.f;
-    if (row >= 0) {
-        float ss = 0.f;
-        for (int c = lane * 4; c < D; c += 256) {
-            f32x4 u = *reinterpret_cast<const f32x4 *>(v + c);
-            ss += u[0] * u[0] + u[1] * u[1] + u[2] * u[2] + u[3] * u[3];
-        }
-        ss = wave_sum(ss);
-        nrm = sqrtf(ss);
-    }
-    const float *qi = G.q_out + q * D;
-    float dot = 0.f, qq = 0.f, tt = 0.f;
-    for (int c = lane; c < D; c += 64) {
-        const float a = qi[c];
-        float b = 0.f;
-        if (row >= 0) b = v[c] / nrm;
-        dot += a * b;
-        qq += a * a;
-        tt += b * b;
-    }
-    dot = wave_sum(dot);
-    qq = wave_sum(qq);
-    tt = wave_sum(tt);
-    const float nq = fmaxf(sqrtf(qq), eps), nt = fmaxf(sqrtf(tt), eps);
-    if (lane == 0) scores[i] = dot / (nq * nt);
+    if (i < n) rm_score_pair(G, ids, i, i < G.Q ? i : rt_query_of(neg_off, G.Q, i - G.Q), eps, scores);
 }
 
 // the key of a looked-up row: (table index << 40) | row; -1 where the table wants no gradient or the id is bad
 __device__ __forceinline__ long long rt_key(const RgcnMixArgs &G, const RgcnMixTrain &Tn, int tidx, long long id,
                                             long long rows) {
     if (tidx < 0 || tidx >= Tn.T || !Tn.ptr[tidx]) return -1;
-    const long long row = rm_lookup_row(G.node_map, G.map_len, id, rows, nullptr);        // (flagged by the forward)
+    const long long row = lookup_row(G.node_map, G.map_len, id, rows, nullptr);        // (flagged by the forward)
     return row < 0 ? -1 : (((long long)tidx << 40) | row);
 }
 
@@ -148,43 +104,21 @@ __device__ __forceinline__ long long rt_key(const RgcnMixArgs &G, const RgcnMixT
 __device__ __forceinline__ void rt_pair_bwd(const RgcnMixArgs &G, const RgcnMixTrain &Tn, const RgcnMixDesc *M, int tidx,
                                             long long i, long long q, int lane) {
     const int D = G.D;
-    const long long row = rm_lookup_row(G.node_map, G.map_len, Tn.ids[i], M->trows, nullptr);
-    const float *v = M->ttab + (row < 0 ? 0 : row) * D;
-    float nrm = 1.f;
-    if (row >= 0) {
-        float ss = 0.f;
-        for (int c = lane * 4; c < D; c += 256) {
-            f32x4 u = *reinterpret_cast<const f32x4 *>(v + c);
-            ss += u[0] * u[0] + u[1] * u[1] + u[2] * u[2] + u[3] * u[3];
-        }
-        ss = wave_sum(ss);
-        nrm = sqrtf(ss);
-    }
-    const float *qi = G.q_out + q * D;
-    float dot = 0.f, qq = 0.f, tt = 0.f;
-    for (int c = lane; c < D; c += 64) {
-        const float a = qi[c];
-        float b = 0.f;
-        if (row >= 0) b = v[c] / nrm;
-        dot += a * b;
-        qq += a * a;
-        tt += b * b;
-    }
-    dot = wave_sum(dot);
-    qq = wave_sum(qq);
-    tt = wave_sum(tt);
+    const long long row = lookup_row(G.node_map, G.map_len, Tn.ids[i], M->trows, nullptr);
+    const float *qi = G.q_out + q * D, *v = M->ttab + (row < 0 ? 0 : row) * D;
+    const PairCosine p = pair_cosine(qi, M->ttab, row, D, lane);
     // cosine_bwd_kernel
-    const float rq = sqrtf(qq), rt = sqrtf(tt);
+    const float rq = sqrtf(p.qq), rt = sqrtf(p.tt);
     const float nq = fmaxf(rq, Tn.eps), nt = fmaxf(rt, Tn.eps);
     const float inv = 1.f / (nq * nt);
-    const float s = dot * inv;
+    const float s = p.dot * inv;
     const float g = Tn.gs[i];
     const float kq = rq > Tn.eps ? s / (nq * nq) : 0.f;
     const float kt = rt > Tn.eps ? s / (nt * nt) : 0.f;
     for (int c = lane; c < D; c += 64) {
-        const float a = qi[c];
+        const float a = gload1(qi + c);
         float b = 0.f;
-        if (row >= 0) b = v[c] / nrm;
+        if (row >= 0) b = gload1(v + c) / p.nrm;
         Tn.GQP[i * D + c] = g * (b * inv - kq * a);
         Tn.GE[i * D + c] = g * (a * inv - kt * b);
     }
@@ -200,26 +134,9 @@ __global__ __launch_bounds__(256) void rgcn_bwd_mixed_kernel(RgcnMixArgs G, Rgcn
     __shared__ __attribute__((aligned(16))) float smem[GT_SMEM_FLOATS];
     __shared__ int off_bad;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long base = (long long)(blockIdx.x / RM_STRETCHES) * GT_BM;
-    const int want = blockIdx.x % RM_STRETCHES;
-    // the want-th stretch [first, end) of this block, as rgcn_mixed_encode_kernel finds it
-    int cnt = -1, fi = -1;
-    long long first = base, end = base, prev = -2;
-    for (int i = 0; i < GT_BM; ++i) {
-        const long long q = base + i;
-        if (q >= G.Q) break;
-        long long k = G.fo[q];
-        if (k < 0 || k >= G.F) k = -1;
-        if (k != prev) {
-            if (cnt == want) break;
-            ++cnt;
-            first = q;
-            fi = (int)k;
-            prev = k;
-        }
-        end = q + 1;
-    }
-    if (cnt != want) return;
+    long long first, end;
+    int fi;
+    if (!rm_stretch(G, first, end, fi)) return;
     fi = __builtin_amdgcn_readfirstlane(fi);
     const int D = G.D, N = G.tp.N, A = G.A, P = G.passes;
     const int Bs = __builtin_amdgcn_readfirstlane((int)(end - first));
@@ -353,59 +270,31 @@ __global__ __launch_bounds__(256) void rgcn_bwd_mixed_kernel(RgcnMixArgs G, Rgcn
     if ((int)threadIdx.x < Bs) Tn.qok[first + threadIdx.x] = 1;
 }
 
-// entry e -> its gradient row: the anchors' rows of G[0], then GE
-__device__ __forceinline__ const float *rt_entry_row(const RgcnMixArgs &G, const RgcnMixTrain &Tn, long long e) {
-    const long long na = (long long)G.A * G.Q;
-    if (e >= na) return Tn.GE + (e - na) * G.D;
-    const long long a = e / G.Q, q = e - a * G.Q;
-    return Tn.Gd + (q * G.tp.N + a) * G.D;
-}
+// rows_reduce's entries: the anchors in (slot, query) order, then the pairs. (A record of values with ONE base pointer:
+// a choice between two pointer members of a record behind references went through scratch.)
+struct RgcnMixEntries {
+    const long long *key;
+    const float *const *etab;
+    float *const *ptr;
+    const float *G0;
+    long long ge_at, Q, na;     // GE's place from G[0], in floats (both lie in the workspace); queries; anchor entries
+    int N, D;
+    __device__ __forceinline__ const long long *keys() const { return key; }
+    __device__ __forceinline__ void tables(long long e, long long k, const float *&tab, float *&gtab) const {
+        tab = etab[e];
+        gtab = ptr[k >> 40];
+    }
+    // the anchors' rows of G[0], then GE
+    __device__ __forceinline__ const float *grad_row(long long e) const {
+        if (e >= na) return G0 + ge_at + (e - na) * D;
+        const long long a = e / Q, q = e - a * Q;
+        return G0 + (q * N + a) * D;
+    }
+};
 
-// y = v / |v|: dv = (g - y (y . g)) / |v| per entry; one wave per entry, the first entry of a key sums the key's entries
-// in entry order (gqe_rows_mixed_kernel)
 __global__ __launch_bounds__(256) void rgcn_rows_mixed_kernel(RgcnMixArgs G, RgcnMixTrain Tn, long long n_ent) {
-    const long long e = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (e >= n_ent) return;
-    const long long *keys = Tn.key;
-    const long long key = keys[e];
-    if (key < 0) return;
-    float earlier = 0.f;
-    for (long long j0 = 0; j0 < e; j0 += 64) {
-        const long long j = j0 + lane;
-        if (j < e && keys[j] == key) earlier = 1.f;
-    }
-    if (wave_sum(earlier) > 0.f) return;
-    const int D = G.D, c = lane * 4;
-    const long long row = key & ((1ll << 40) - 1);
-    const float *tab = Tn.etab[e];
-    float *gtab = Tn.ptr[key >> 40];
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (c < D) v = *reinterpret_cast<const f32x4 *>(tab + row * D + c);
-    const float nrm = sqrtf(wave_sum(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]));
-    const float inv = 1.f / nrm;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (long long j0 = e; j0 < n_ent; j0 += 64) {
-        const long long j = j0 + lane;
-        const float mine = (j < n_ent && keys[j] == key) ? 1.f : 0.f;
-        if (!(wave_sum(mine) > 0.f)) continue;
-        for (int l = 0; l < 64; ++l) {
-            if (!(__shfl(mine, l, 64) > 0.f)) continue;
-            const float *gr = rt_entry_row(G, Tn, j0 + l);
-            f32x4 g = {0.f, 0.f, 0.f, 0.f};
-            if (c < D) g = *reinterpret_cast<const f32x4 *>(gr + c);
-            const float ydotg = wave_sum(v[0] * g[0] + v[1] * g[1] + v[2] * g[2] + v[3] * g[3]) * inv;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) acc[u] += (g[u] - (v[u] / nrm) * ydotg) * inv;
-        }
-    }
-    if (c < D) {
-        float *o = gtab + row * D + c;
-        f32x4 old = *reinterpret_cast<const f32x4 *>(o);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) old[u] += acc[u];
-        *reinterpret_cast<f32x4 *>(o) = old;
-    }
+    const RgcnMixEntries E = {Tn.key, Tn.etab, Tn.ptr, Tn.Gd, Tn.GE - Tn.Gd, G.Q, (long long)G.A * G.Q, G.tp.N, G.D};
+    rows_reduce(E, n_ent, G.D);
 }
 
 // contribution c = slot * Q + query -> its key (none: KP + M); the sort numbers the contributions itself
@@ -434,29 +323,39 @@ __global__ __launch_bounds__(256) void rgcn_mix_ckeys_kernel(RgcnMixArgs G, Rgcn
     Tn.ckey[c] = (unsigned)key;
 }
 
-// seg[k] = [first, end) of key k in the sorted list (cleared before)
 __global__ __launch_bounds__(256) void rgcn_mix_seg_kernel(RgcnMixTrain Tn) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= Tn.NC) return;
-    const unsigned k = Tn.skey[i];
-    if (k >= (unsigned)(Tn.KP + Tn.M)) return;
-    if (i == 0 || Tn.skey[i - 1] != k) Tn.seg[2 * k] = (int)i;
-    if (i == Tn.NC - 1 || Tn.skey[i + 1] != k) Tn.seg[2 * k + 1] = (int)(i + 1);
+    mix_seg(Tn.skey, Tn.seg, Tn.NC, (unsigned)(Tn.KP + Tn.M));
 }
 
-// contribution c of a pass -> its S row (the A operand) and G row (the B operand)
-__device__ __forceinline__ void rt_contrib_rows(const RgcnMixArgs &G, const RgcnMixTrain &Tn, unsigned c, const float *&x,
-                                                const float *&g) {
-    const unsigned Q = (unsigned)G.Q;
-    const unsigned s = c / Q, q = c - s * Q;
-    const unsigned p = s / (unsigned)Tn.slots, j = s - p * (unsigned)Tn.slots;
-    const unsigned E = (unsigned)G.tp.E;
-    const unsigned src = j < E ? (Tn.srcs >> (2 * j)) & 3u : j - E, dst = j < E ? (Tn.dsts >> (2 * j)) & 3u : j - E;
-    x = Tn.S + (long long)p * Tn.sstride + ((long long)q * G.tp.N + src) * G.D;
-    g = Tn.Gd + (long long)(p + 1) * Tn.sstride + ((long long)q * G.tp.N + dst) * G.D;
-}
+// sorted value = contribution number
+struct RgcnMixContrib {
+    const RgcnMixArgs &G;
+    const RgcnMixTrain &Tn;
+    bool is_bias;       // (term) the vector is a bias, not a mode-embedding row
+    // a pass's contribution -> its S row (the A operand) and G row (the B operand)
+    __device__ __forceinline__ void rows(unsigned c, const float *&x, const float *&g) const {
+        const unsigned Q = (unsigned)G.Q;
+        const unsigned s = c / Q, q = c - s * Q;
+        const unsigned p = s / (unsigned)Tn.slots, j = s - p * (unsigned)Tn.slots;
+        const unsigned E = (unsigned)G.tp.E;
+        const unsigned src = j < E ? (Tn.srcs >> (2 * j)) & 3u : j - E, dst = j < E ? (Tn.dsts >> (2 * j)) & 3u : j - E;
+        x = Tn.S + (long long)p * Tn.sstride + ((long long)q * G.tp.N + src) * G.D;
+        g = Tn.Gd + (long long)(p + 1) * Tn.sstride + ((long long)q * G.tp.N + dst) * G.D;
+    }
+    // a bias: the G row of a root contribution; a mode-embedding row: the G[0] row of the variable slot
+    __device__ __forceinline__ const float *term(unsigned c) const {
+        if (is_bias) {
+            const float *x, *g;
+            rows(c, x, g);
+            return g;
+        }
+        const unsigned Q = (unsigned)G.Q;
+        const unsigned s = c / Q, q = c - s * Q;
+        return Tn.Gd + ((long long)q * G.tp.N + G.A + (s - (unsigned)(G.passes * Tn.slots))) * G.D;
+    }
+};
 
-// workgroup = (matrix key, strip of 16 gradient rows): gqe_mix_param_kernel's scheme
+// workgroup = (matrix key, strip of 16 gradient rows)
 __global__ __launch_bounds__(256) void rgcn_mix_param_kernel(RgcnMixArgs G, RgcnMixTrain Tn) {
     const int D = G.D, nstrip = D / 16;
     const int par = blockIdx.x / nstrip, rs = blockIdx.x % nstrip;
@@ -466,76 +365,20 @@ __global__ __launch_bounds__(256) void rgcn_mix_param_kernel(RgcnMixArgs G, Rgcn
     if (rel < G.R) g += (long long)rel * D * D;
     const int lo = Tn.seg[2 * par], hi = Tn.seg[2 * par + 1];
     if (lo >= hi) return;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int j = lane & 15, kq = lane >> 4;
-    if (wave >= nstrip) return;
-    f32x4 tot[4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) tot[m] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int c0 = lo; c0 < hi; c0 += RT_CHUNK) {
-        const int ce = c0 + RT_CHUNK < hi ? c0 + RT_CHUNK : hi;
-        f32x4 acc[4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
-        for (int c = c0; c < ce; c += 4) {
-            // lane group kq feeds contribution c + kq (past the chunk: zeros)
-            float a = 0.f, b[4] = {0.f, 0.f, 0.f, 0.f};
-            if (c + kq < ce) {
-                const float *X, *dY;
-                rt_contrib_rows(G, Tn, (unsigned)Tn.sval[c + kq], X, dY);
-                a = X[16 * rs + j];
-#pragma unroll
-                for (int m = 0; m < 4; ++m)
-                    if (wave + 4 * m < nstrip) b[m] = dY[16 * (wave + 4 * m) + j];
-            }
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-                if (wave + 4 * m < nstrip) acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b[m], acc[m], 0, 0, 0);
-        }
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) tot[m][r] += acc[m][r];
-    }
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-        if (wave + 4 * m >= nstrip) continue;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) g[(long long)(16 * rs + 4 * kq + r) * D + 16 * (wave + 4 * m) + j] += tot[m][r];
-    }
+    param_reduce<MPQE_RGCN_MIX_GRAD_CHUNK>(lo, hi, rs, g, D, Tn.sval, RgcnMixContrib{G, Tn, false});
 }
 
-// workgroup = one vector: the bias of layer k (k < L: the column sum of the G rows of the layer's root segment) or
-// mode-embedding row k - L (the G[0] rows of its variable slots); a thread per column, the rows in list order
+// workgroup = one vector: the bias of layer k (k < L) or mode-embedding row k - L
 __global__ __launch_bounds__(256) void rgcn_mix_vec_kernel(RgcnMixArgs G, RgcnMixTrain Tn) {
     const int D = G.D, k = blockIdx.x;
     const bool is_bias = k < Tn.L;
     float *g = is_bias ? Tn.ptr[Tn.T + 1 + 2 * Tn.L + k] : Tn.ptr[Tn.T];
-    if (!g || (int)threadIdx.x >= D) return;
+    if (!g) return;
     if (!is_bias) g += (long long)(k - Tn.L) * D;
     const int key = is_bias ? k * ((int)G.R + 1) + (int)G.R : Tn.KP + (k - Tn.L);
     const int lo = Tn.seg[2 * key], hi = Tn.seg[2 * key + 1];
     if (lo >= hi) return;
-    const unsigned Q = (unsigned)G.Q;
-    float tot = 0.f;
-    for (int c0 = lo; c0 < hi; c0 += RT_CHUNK) {
-        const int ce = c0 + RT_CHUNK < hi ? c0 + RT_CHUNK : hi;
-        float acc = 0.f;
-        for (int c = c0; c < ce; ++c) {
-            const unsigned ci = (unsigned)Tn.sval[c];
-            const float *row;
-            if (is_bias) {
-                const float *x;
-                rt_contrib_rows(G, Tn, ci, x, row);
-            } else {
-                const unsigned s = ci / Q, q = ci - s * Q;
-                row = Tn.Gd + ((long long)q * G.tp.N + G.A + (s - (unsigned)(G.passes * Tn.slots))) * D;
-            }
-            acc += row[threadIdx.x];
-        }
-        tot += acc;
-    }
-    g[threadIdx.x] += tot;
+    vec_reduce<MPQE_RGCN_MIX_GRAD_CHUNK>(lo, hi, g, D, Tn.sval, RgcnMixContrib{G, Tn, is_bias});
 }
 
 // ------------------------------------------------------------------------------------------------ host side
@@ -550,36 +393,24 @@ extern "C" int mpqe_rgcn_mixed_index_build(int query_type, const int32_t *recs_h
     if (query_type < 0 || query_type >= MPQE_Q_COUNT || !recs_host || !index) return MPQE_ERR_INVALID_ARG;
     if (!rm_formulas_ok(num_formulas) || (uintptr_t)index % 256 != 0) return MPQE_ERR_INVALID_ARG;
     const TemplateDesc &d = kTemplates[query_type];
-    RgcnMixIdx *image = new (std::nothrow) RgcnMixIdx[(size_t)num_formulas];
-    if (!image) return MPQE_ERR_INVALID_ARG;
-    memset(image, 0, (size_t)num_formulas * sizeof(RgcnMixIdx));
-    int st = MPQE_OK;
-    for (int64_t f = 0; f < num_formulas && st == MPQE_OK; ++f) {
-        const int32_t *rec = recs_host + f * MPQE_RGCN_MIX_REC_INTS;
-        RgcnMixIdx &I = image[f];
-        for (int e = 0; e < d.E; ++e) {
-            if (rec[e] < 0) st = MPQE_ERR_INVALID_ARG;
-            I.rel[e] = rec[e];
+    return mix_upload<RgcnMixIdx>(index, (size_t)num_formulas, as_stream(stream), [&](RgcnMixIdx *image) -> int {
+        memset(image, 0, (size_t)num_formulas * sizeof(RgcnMixIdx));
+        for (int64_t f = 0; f < num_formulas; ++f) {
+            const int32_t *rec = recs_host + f * MPQE_RGCN_MIX_REC_INTS;
+            RgcnMixIdx &I = image[f];
+            bool bad = false;
+            auto take = [&](int32_t v) {
+                bad = bad || v < 0;
+                return v;
+            };
+            for (int e = 0; e < d.E; ++e) I.rel[e] = take(rec[e]);
+            for (int a = 0; a < d.A; ++a) I.atab[a] = take(rec[3 + a]);
+            for (int k = 0; k < d.V; ++k) I.var[k] = take(rec[6 + k]);
+            I.ttab = take(rec[9]);
+            if (bad) return MPQE_ERR_INVALID_ARG;
         }
-        for (int a = 0; a < d.A; ++a) {
-            if (rec[3 + a] < 0) st = MPQE_ERR_INVALID_ARG;
-            I.atab[a] = rec[3 + a];
-        }
-        for (int k = 0; k < d.V; ++k) {
-            if (rec[6 + k] < 0) st = MPQE_ERR_INVALID_ARG;
-            I.var[k] = rec[6 + k];
-        }
-        if (rec[9] < 0) st = MPQE_ERR_INVALID_ARG;
-        I.ttab = rec[9];
-    }
-    if (st == MPQE_OK && index_bytes < rt_index_size(num_formulas)) st = MPQE_ERR_WORKSPACE;
-    if (st == MPQE_OK &&
-        hipMemcpyAsync(index, image, (size_t)num_formulas * sizeof(RgcnMixIdx), hipMemcpyHostToDevice, as_stream(stream)) !=
-            hipSuccess)
-        st = MPQE_ERR_LAUNCH;
-    // (the copy reads pageable memory: it has left `image` when the call returns)
-    delete[] image;
-    return st;
+        return index_bytes < rt_index_size(num_formulas) ? MPQE_ERR_WORKSPACE : MPQE_OK;
+    });
 }
 
 // the shapes the training entries cover
@@ -778,34 +609,24 @@ extern "C" int mpqe_rgcn_bwd_mixed(int query_type, int64_t num_formulas, const v
         if (layer_of_pass_host[p] < 0 || layer_of_pass_host[p] >= L) return MPQE_ERR_INVALID_ARG;
         Tn.lop[p] = layer_of_pass_host[p];
     }
-    const size_t np = (size_t)T + 1 + 3 * (size_t)L;
-    float **image = new (std::nothrow) float *[np];
-    if (!image) return MPQE_ERR_INVALID_ARG;
     bool any_table = false, any_mat = false, any_vec = grad_mode_emb != nullptr;
-    for (int t = 0; t < T; ++t) {
-        image[t] = grad_tables_host ? grad_tables_host[t] : nullptr;
-        any_table = any_table || image[t];
-    }
-    image[T] = grad_mode_emb;
-    for (int l = 0; l < L; ++l) {
-        image[T + 1 + l] = grad_basis_host ? grad_basis_host[l] : nullptr;
-        image[T + 1 + L + l] = grad_root_host ? grad_root_host[l] : nullptr;
-        image[T + 1 + 2 * L + l] = grad_bias_host ? grad_bias_host[l] : nullptr;
-        any_mat = any_mat || image[T + 1 + l] || image[T + 1 + L + l];
-        any_vec = any_vec || image[T + 1 + 2 * L + l];
-    }
-    for (size_t k = 0; k < np; ++k)
-        if ((uintptr_t)image[k] % 16 != 0) {
-            delete[] image;
-            return MPQE_ERR_INVALID_ARG;
-        }
     hipStream_t s = as_stream(stream);
     char *wb = reinterpret_cast<char *>(workspace);
-    // the gradient buffers' addresses: one copy from a host image
-    const hipError_t ce = hipMemcpyAsync(wb + Y.ptr_off, image, np * sizeof(float *), hipMemcpyHostToDevice, s);
-    // (the copy reads pageable memory: it has left `image` when the call returns)
-    delete[] image;
-    if (ce != hipSuccess) return MPQE_ERR_LAUNCH;
+    st = mix_upload_grad_ptrs(wb + Y.ptr_off, (size_t)T + 1 + 3 * (size_t)L, s, [&](float **image) {
+        for (int t = 0; t < T; ++t) {
+            image[t] = grad_tables_host ? grad_tables_host[t] : nullptr;
+            any_table = any_table || image[t];
+        }
+        image[T] = grad_mode_emb;
+        for (int l = 0; l < L; ++l) {
+            image[T + 1 + l] = grad_basis_host ? grad_basis_host[l] : nullptr;
+            image[T + 1 + L + l] = grad_root_host ? grad_root_host[l] : nullptr;
+            image[T + 1 + 2 * L + l] = grad_bias_host ? grad_bias_host[l] : nullptr;
+            any_mat = any_mat || image[T + 1 + l] || image[T + 1 + L + l];
+            any_vec = any_vec || image[T + 1 + 2 * L + l];
+        }
+    });
+    if (st != MPQE_OK) return st;
     Tn.idx = reinterpret_cast<const RgcnMixIdx *>(index);
     Tn.ids = reinterpret_cast<const long long *>(ids);
     Tn.neg_off = reinterpret_cast<const long long *>(neg_off);

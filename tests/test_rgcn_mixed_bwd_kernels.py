@@ -29,6 +29,7 @@ from tests.test_gqe_kernels import INVALID, OK, TYPES, UNSUPPORTED, WORKSPACE, b
 RUNS = ((0, 1), (1, 63), (2, 64), (3, 65), (4, 1), (5, 1), (0, 3))
 NEGS = (0, 1, 2, 65)
 F = 6
+C = _capi.RGCN_MIX_GRAD_CHUNK
 MODES, RELS = mk.MODES, mk.RELS
 FLAG_BAD_NODE_ID, FLAG_BAD_RELATION, FLAG_BAD_INDEX = 1, 4, 8
 
@@ -97,12 +98,8 @@ def settled(qt, D, readout='mp', layers=3, bias=True, passes=None):
     raise AssertionError('no seed without near-ties')
 
 
-def exact_problem(qt, readout='mp', layers=3, passes=None, seed=5):
-    """one-hot +-2^k table rows, small integer mode embeddings, weights and grad_q, D 16"""
-    key = ('exact', qt, readout, layers, passes, seed)
-    if key in _SETTLED:
-        return _SETTLED[key]
-    prob = make(qt, 16, seed, readout=readout, layers=layers, passes=passes)
+def make_exact(prob, seed):
+    """one-hot +-2^k table rows, small integer mode embeddings, weights and grad_q (D 16) -> (problem, float64 oracle)"""
     rng = np.random.RandomState(seed + 11)
     for t in prob.tables:
         t[...] = 0
@@ -121,7 +118,13 @@ def exact_problem(qt, readout='mp', layers=3, passes=None, seed=5):
     for k in o.grads:
         np.testing.assert_array_equal(o32.grads[k].astype(np.float64), o.grads[k], err_msg=k)
     assert any(g.any() for g in o.grads.values())
-    _SETTLED[key] = (prob, o)
+    return prob, o
+
+
+def exact_problem(qt, readout='mp', layers=3, passes=None, seed=5):
+    key = ('exact', qt, readout, layers, passes, seed)
+    if key not in _SETTLED:
+        _SETTLED[key] = make_exact(make(qt, 16, seed, readout=readout, layers=layers, passes=passes), seed)
     return _SETTLED[key]
 
 
@@ -326,6 +329,26 @@ def test_exact_gradients(be, qt, readout, layers):
     dev, grads = run_exact(be, prob)
     assert int(be.get(dev.err)[0]) == 0
     np.testing.assert_array_equal(be.get(dev.q_out).astype(np.float64), o.q)
+    assert sorted(grads) == sorted(o.grads)
+    for k in grads:
+        np.testing.assert_array_equal(grads[k].astype(np.float64), o.grads[k], err_msg=k)
+
+
+@pytest.mark.parametrize('count', [C - 1, C, C + 1, 2 * C + 1])
+def test_one_relation_at_the_chunk_edges(be, count):
+    """a 1-chain under the target-message readout is one pass of one layer with one edge into the target slot: `count`
+    queries of one relation (two formulas, in two runs, so that the window is not one run) give that relation's basis
+    matrix, the root matrix and the bias exactly `count` contributions each -- one 16-row strip, one wave at D 16"""
+    key = ('edge', count)
+    if key not in _SETTLED:
+        prob = mk.Problem('1-chain', 16, 2, ((0, count - 3), (1, 3)), 5, readout='mp', layers=1, neg_counts=(0,))
+        prob.recs[:, 0] = prob.recs[0, 0]
+        _SETTLED[key] = make_exact(prob, 5)
+    prob, o = _SETTLED[key]
+    assert prob.Q == count and prob.passes == 1 and len(prob.layers) == 1
+    assert o.grads['basis0'].reshape(RELS, -1).any(axis=1).sum() == 1 and o.grads['root0'].any() and o.grads['bias0'].any()
+    dev, grads = run_exact(be, prob)
+    assert int(be.get(dev.err)[0]) == 0
     assert sorted(grads) == sorted(o.grads)
     for k in grads:
         np.testing.assert_array_equal(grads[k].astype(np.float64), o.grads[k], err_msg=k)
