@@ -1,7 +1,10 @@
 // Ranking the queries of ONE call against DIFFERENT tables: query i is ranked against candidate set
 // set_of_group[group_of[i]] (the entities of its formula's target mode), with the score, the total order, the integer
-// counters and the strip lists of rank.hip (rank_core.h holds what both files run). Every rank, top-k row and score and
-// target score equals bit for bit what mpqe_rank_entities_scored gives the queries of one set handed to it alone.
+// counters and the strip lists of rank.hip. Every rank, top-k row and score and target score equals bit for bit what
+// mpqe_rank_entities_scored gives the queries of one set handed to it alone: the pre-pass's query branch, the pair tile,
+// the strip walk, the finishing wave and the strip rule are rank_core.h's one definition each, and the kernels below are
+// wrappers that read the block and set records, fill in the walk's view (RmxStrip: the permutation and the two bitmaps)
+// and call them.
 //
 // The sets live in a descriptor block the caller keeps (mpqe_rank_mixed_desc_build: addresses, sizes, score kinds and the
 // group -> set table; nothing per call). Five launches, none waits for a workgroup of its own launch:
@@ -131,12 +134,7 @@ __global__ __launch_bounds__(256) void rmx_prep_kernel(const void *__restrict__ 
         const long long j = i - total_rows;
         const int s = qset[j];
         const int kind = s < num_sets ? sets[s].kind : 1;       // (a query without a set: nothing reads its factor)
-        const float ss = rank_sumsq(q + j * D, D, lane, kind);
-        if (lane != 0) return;
-        qinv[j] = rank_query_inv(sqrtf(ss), eps, kind);
-        tsc[j] = -INFINITY;
-        trow[j] = -1;
-        cnt[j] = 0;
+        rank_prep_query(q + j * D, D, lane, eps, kind, j, qinv, tsc, trow, cnt, nullptr);
         return;
     }
     if (!rmx_desc_matches(desc, num_sets, num_groups, max_rows, total_rows)) return;
@@ -155,18 +153,6 @@ __global__ __launch_bounds__(256) void rmx_prep_kernel(const void *__restrict__ 
 
 // ---------------------------------------------------------------------------------------------- targets
 // Pair j of block b = (the query at position first + j, its target row) against the block's set.
-__device__ __forceinline__ bool rmx_pair(const RmxBlock &B, long long N, int j, const int *__restrict__ perm,
-                                         const long long *__restrict__ target_rows, long long &qi, long long &r,
-                                         bool &listed) {
-    listed = j < B.count;
-    qi = 0;
-    r = 0;
-    if (!listed) return false;
-    qi = perm[B.first + j];
-    r = target_rows[qi];
-    return r >= 0 && r < N;
-}
-
 template <int MODE>
 __global__ __launch_bounds__(256) void rmx_pair_kernel(const void *__restrict__ desc, const RmxBlock *__restrict__ blocks,
                                                        const RmxState *__restrict__ state, const int *__restrict__ perm,
@@ -178,51 +164,45 @@ __global__ __launch_bounds__(256) void rmx_pair_kernel(const void *__restrict__ 
     if ((int)blockIdx.x >= state->nblocks) return;
     const RmxBlock B = blocks[blockIdx.x];
     const RmxSet S = rmx_sets(desc)[B.set];
-    const long long N = S.rows;
-    RankLoader<MODE> L;
-    L.init(q, S.table, D);
-    {
-        long long qi, r;
-        bool listed;
-        bool ok = rmx_pair(B, N, stage_row(false, 0), perm, target_rows, qi, r, listed);
-        L.a0 = L.b0 = ok;
-        L.pa0 = q + (ok ? qi : 0) * D;
-        L.pb0 = S.table + (ok ? r : 0) * D;
-        ok = rmx_pair(B, N, stage_row(false, 1), perm, target_rows, qi, r, listed);
-        L.a1 = L.b1 = ok;
-        L.pa1 = q + (ok ? qi : 0) * D;
-        L.pb1 = S.table + (ok ? r : 0) * D;
-    }
-    f32x16 acc;
-#pragma unroll
-    for (int g = 0; g < 16; ++g) acc[g] = 0.f;
-    gemm_block<false, false>(acc, L, L.left, smem);
-
-    const int col = acc_col();
-    float dot = 0.f;
-    bool mine = false;
-#pragma unroll
-    for (int g = 0; g < 16; ++g)
-        if (acc_row(g) == col) {
-            dot = acc[g];
-            mine = true;
-        }
-    if (!mine) return;
-    long long qi, r;
-    bool listed;
-    const bool ok = rmx_pair(B, N, col, perm, target_rows, qi, r, listed);
-    if (!listed) return;
-    if (!ok) {
-        flag_error(err, MPQE_FLAG_BAD_INDEX);       // (the pre-pass left "no target" for this query)
-        return;
-    }
-    tsc[qi] = rank_score(dot, rinv[S.first + r], qinv[qi]);
-    trow[qi] = (int)r;
+    const RankPairDot d = rank_pair_tile<MODE>(
+        q, S.table, D,
+        [=](int j) {
+            RankPair P = {j < B.count, false, 0, 0};
+            if (!P.listed) return P;
+            P.qi = perm[B.first + j];
+            P.r = target_rows[P.qi];
+            P.ok = P.r >= 0 && P.r < S.rows;
+            return P;
+        },
+        smem, err);
+    if (!d.mine) return;
+    tsc[d.qi] = rank_score(d.dot, rinv[S.first + d.r], qinv[d.qi]);
+    trow[d.qi] = (int)d.r;
 }
 
 // ---------------------------------------------------------------------------------------------- all rows
-// Grid: blockIdx.x = block * S + strip. As rank_tile_kernel: a workgroup meets its rows in increasing order, so of two
-// equal scores the one already in a list is the smaller row and stays ahead.
+// The mixed view of the strip walk: block row j is the query at sorted position first + j; this thread's 16 columns lie
+// in one 32-bit word of either bitmap, so a row that is not eligible is left out of the count as it passes and nothing
+// is left to ask at insertion time.
+struct RmxStrip : RankStrip {
+    const int *perm;
+    const uint32_t *valid, *xbits, *xw;
+    long long W;
+
+    __device__ __forceinline__ long long query(int j) const { return perm[first + j]; }
+    __device__ __forceinline__ void bind(bool ok, long long sq) { xw = ok && xbits ? xbits + sq * W : nullptr; }
+    __device__ __forceinline__ unsigned out_mask(long long cq) const {
+        const long long word = cq >> 5;
+        const int shift = (int)(cq & 31);
+        unsigned out = 0;
+        if (xw && word < W) out |= xw[word] >> shift;
+        if (valid && cq < N) out |= ~(valid[word] >> shift);
+        return out & 0xffffu;
+    }
+    __device__ __forceinline__ bool excluded(long long) const { return false; }
+};
+
+// Grid: blockIdx.x = block * S + strip.
 template <int MODE, int KL>
 __global__ __launch_bounds__(256) void rmx_tile_kernel(const void *__restrict__ desc, const RmxBlock *__restrict__ blocks,
                                                        const RmxState *__restrict__ state, const int *__restrict__ perm,
@@ -236,125 +216,33 @@ __global__ __launch_bounds__(256) void rmx_tile_kernel(const void *__restrict__ 
     __shared__ float ls[GT_BM * KL];
     __shared__ int lr[GT_BM * KL];
     __shared__ int llen[GT_BM];
-    const int t = threadIdx.x;
-    const int strip = (int)(blockIdx.x % (unsigned)S);
     const int block = (int)(blockIdx.x / (unsigned)S);
     if (block >= state->nblocks) return;
     const RmxBlock B = blocks[block];
     const RmxSet St = rmx_sets(desc)[B.set];
-    const long long N = St.rows;
-    const float *table = St.table;
-    const float *rinv = rinv_all + St.first;
-    const int tiles = (int)((N + GT_BN - 1) / GT_BN);
-    const int tiles_per_strip = (tiles + S - 1) / S;
-    if (t < GT_BM) llen[t] = 0;
-
-    // the scan's view: 4 threads per query, 16 columns of the tile each
-    const int srow = t >> 2, quarter = t & 3;
-    const bool svalid = srow < B.count;
-    const long long sq = svalid ? perm[B.first + srow] : 0;
-    const int tr = svalid ? trow[sq] : -1;
-    const float ts = svalid ? tsc[sq] : 0.f;
-    const uint32_t *xw = svalid && excl_bits ? reinterpret_cast<const uint32_t *>(excl_bits) + sq * W : nullptr;
-    // the epilogue's view: one column, 16 query rows
-    float qv[16];
-#pragma unroll
-    for (int g = 0; g < 16; ++g) {
-        const int row = acc_row(g);
-        qv[g] = row < B.count ? qinv[perm[B.first + row]] : 0.f;
-    }
-    const int a0 = stage_row(false, 0), a1 = stage_row(false, 1);
-    const long long ar0 = perm[B.first + (a0 < B.count ? a0 : 0)], ar1 = perm[B.first + (a1 < B.count ? a1 : 0)];
-    int count = 0;
-    __syncthreads();
-
-    for (int tile = 0; tile < tiles_per_strip; ++tile) {
-        const long long c0 = ((long long)strip * tiles_per_strip + tile) * GT_BN;
-        if (c0 >= N) break;
-        RankLoader<MODE> L;
-        L.init(q, table, D);
-        const long long br0 = c0 + stage_row(false, 0), br1 = c0 + stage_row(false, 1);
-        L.a0 = a0 < B.count;
-        L.a1 = a1 < B.count;
-        L.b0 = br0 < N;
-        L.b1 = br1 < N;
-        L.pa0 = q + ar0 * D;                // (a row past the block: the block's first query, its result is not used)
-        L.pa1 = q + ar1 * D;
-        L.pb0 = table + (L.b0 ? br0 : N - 1) * D;
-        L.pb1 = table + (L.b1 ? br1 : N - 1) * D;
-        f32x16 acc;
-#pragma unroll
-        for (int g = 0; g < 16; ++g) acc[g] = 0.f;
-        gemm_block<false, false>(acc, L, L.left, smem);         // (ends on a barrier: the LDS images are free)
-
-        {
-            const long long col = c0 + acc_col();
-            const float rv = col < N ? rinv[col] : 0.f;
-#pragma unroll
-            for (int g = 0; g < 16; ++g) smem[acc_row(g) * RANK_TILE_LD + acc_col()] = rank_score(acc[g], rv, qv[g]);
-        }
-        __syncthreads();
-
-        // this thread's 16 columns lie in one 32-bit word of either bitmap: bit j of `out` set = column j not eligible
-        unsigned out = 0;
-        {
-            const long long cq = c0 + quarter * 16;
-            const long long word = cq >> 5;
-            const int shift = (int)(cq & 31);
-            if (xw && word < W) out |= xw[word] >> shift;
-            if (St.valid && cq < N) out |= ~(St.valid[word] >> shift);
-            out &= 0xffffu;
-        }
-        unsigned pass = 0;
-        float sc[16];
-        {
-            const int len = llen[srow];
-            const bool full = len >= k;
-            const float thr = full && k > 0 ? ls[srow * KL + k - 1] : 0.f;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const long long col = c0 + quarter * 16 + j;
-                const float s = smem[srow * RANK_TILE_LD + quarter * 16 + j];
-                sc[j] = s;
-                const bool in = svalid && col < N && !(out & (1u << j));
-                if (svalid && col < N && tr >= 0 && col != tr && !(out & (1u << j)) &&
-                    (s > ts || (s == ts && col < tr)))
-                    ++count;
-                if (in && k > 0 && (!full || s > thr)) pass |= 1u << j;
-            }
-        }
-        if (k > 0) {
-            for (int turn = 0; turn < 4; ++turn) {
-                if (turn == quarter && pass) {
-                    float *S_ = ls + srow * KL;
-                    int *R_ = lr + srow * KL;
-#pragma unroll
-                    for (int j = 0; j < 16; ++j) {
-                        if (!(pass & (1u << j))) continue;
-                        const float s = sc[j];
-                        const int len = llen[srow];
-                        if (len >= k && !(s > S_[k - 1])) continue;
-                        llen[srow] = rank_list_insert(S_, R_, len, k, s, (int)(c0 + quarter * 16 + j));
-                    }
-                }
-                __syncthreads();
-            }
-        } else {
-            __syncthreads();        // (the next tile's operands overwrite the score tile)
-        }
-    }
-
-    count += __shfl_xor(count, 1, 64);
-    count += __shfl_xor(count, 2, 64);
-    if (quarter == 0 && svalid && tr >= 0 && count) atomicAdd(&cnt[sq], count);
-    for (int idx = t; idx < GT_BM * k; idx += 256) {
-        const int row = idx / k, j = idx % k;
-        if (row >= B.count) break;
-        const bool have = j < llen[row];
-        const long long dst = ((long long)(B.first + row) * S + strip) * k + j;
-        cand_s[dst] = have ? ls[row * KL + j] : -INFINITY;
-        cand_r[dst] = have ? lr[row * KL + j] : -1;
-    }
+    RmxStrip V;
+    V.q = q;
+    V.table = St.table;
+    V.rinv = rinv_all + St.first;
+    V.qinv = qinv;
+    V.tsc = tsc;
+    V.trow = trow;
+    V.cnt = cnt;
+    V.cand_s = cand_s;
+    V.cand_r = cand_r;
+    V.N = St.rows;
+    V.first = B.first;
+    V.D = D;
+    V.k = k;
+    V.live = B.count;
+    V.S = S;
+    V.tiles_per_strip = ((int)((St.rows + GT_BN - 1) / GT_BN) + S - 1) / S;
+    V.strip = (int)(blockIdx.x % (unsigned)S);
+    V.perm = perm;
+    V.valid = St.valid;
+    V.xbits = reinterpret_cast<const uint32_t *>(excl_bits);
+    V.W = W;
+    rank_strip_walk<MODE, KL>(V, smem, ls, lr, llen);
 }
 
 // ---------------------------------------------------------------------------------------------- merge
@@ -371,14 +259,8 @@ __global__ __launch_bounds__(256) void rmx_finish_kernel(long long Q, int k, int
     const int lane = threadIdx.x & 63;
     const bool live = p < Q;            // (no early return: every lane of the workgroup's waves meets the shuffles)
     const bool good = live && p < state->ngood;
-    const long long i = live ? perm[p] : 0;
-    if (live && lane == 0) {
-        const int tr = good ? trow[i] : -1;
-        if (rank) rank[i] = tr >= 0 ? 1 + (long long)cnt[i] : -1;
-        if (target_scores) target_scores[i] = tr >= 0 ? tsc[i] : NAN;
-    }
-    const long long base = good && lane < S ? (p * S + lane) * k : -1;
-    rank_merge_lists(live, lane, base, k, cand_s, cand_r, topk_rows + i * k, topk_scores + i * k);
+    rank_finish_wave(live, good, live ? perm[p] : 0, lane, good && lane < S ? (p * S + lane) * k : -1, k, cand_s, cand_r,
+                     tsc, trow, cnt, nullptr, topk_rows, topk_scores, rank, target_scores);
 }
 
 // ---------------------------------------------------------------------------------------------- host
@@ -447,17 +329,12 @@ struct RmxPlan {
     size_t o_state, o_qset, o_perm, o_blocks, o_rinv, o_qinv, o_tsc, o_trow, o_cnt, o_cs, o_cr, bytes;
 };
 
-// rank.hip's rule for the strip count, on the bound of the block count and the widest set's tiles.
+// The strip rule on the bound of the block count and the widest set's tiles.
 static RmxPlan rmx_plan(int64_t Q, int64_t num_sets, int64_t max_rows, int64_t total_rows, int k) {
     RmxPlan p;
     p.max_blocks = Q / GT_BM + num_sets;
-    const long long tiles = (max_rows + GT_BN - 1) / GT_BN;
-    long long want = (768 + p.max_blocks - 1) / p.max_blocks;
-    if (want > RANK_MAX_STRIPS) want = RANK_MAX_STRIPS;
-    if (want > tiles) want = tiles;
-    if (want < 1) want = 1;
-    const long long tps = (tiles + want - 1) / want;
-    p.S = (int)((tiles + tps - 1) / tps);
+    int widest_tiles_per_strip;         // (a kernel derives its own set's)
+    rank_strip_rule(p.max_blocks, (max_rows + GT_BN - 1) / GT_BN, p.S, widest_tiles_per_strip);
     size_t o = 0;
     p.o_state = o;  o += 256;
     p.o_qset = o;   o += align_up((size_t)Q * 4, 256);
@@ -512,19 +389,12 @@ static void rmx_launch(const RmxPlan &pl, const RmxArgs &a, hipStream_t s) {
         hipLaunchKernelGGL(rmx_pair_kernel<MODE>, dim3((unsigned)pl.max_blocks), dim3(256), 0, s, a.desc, a.blocks,
                            a.state, a.perm, a.q, a.D, (const float *)a.rinv, (const float *)a.qinv,
                            (const long long *)a.target_rows, a.tsc, a.trow, a.err);
-    const dim3 grid((unsigned)(pl.max_blocks * pl.S));
-    if (a.k <= RANK_SMALL_K)
-        hipLaunchKernelGGL((rmx_tile_kernel<MODE, RANK_SMALL_K>), grid, dim3(256), 0, s, a.desc, a.blocks, a.state, a.perm,
-                           a.q, a.D, (const float *)a.rinv, (const float *)a.qinv, (const float *)a.tsc,
-                           (const int *)a.trow, a.excl_bits, (long long)a.W, a.k, pl.S, a.cnt, a.cs, a.cr);
-    else if (a.k <= RANK_MID_K)
-        hipLaunchKernelGGL((rmx_tile_kernel<MODE, RANK_MID_K>), grid, dim3(256), 0, s, a.desc, a.blocks, a.state, a.perm,
-                           a.q, a.D, (const float *)a.rinv, (const float *)a.qinv, (const float *)a.tsc,
-                           (const int *)a.trow, a.excl_bits, (long long)a.W, a.k, pl.S, a.cnt, a.cs, a.cr);
-    else
-        hipLaunchKernelGGL((rmx_tile_kernel<MODE, RANK_MAX_K>), grid, dim3(256), 0, s, a.desc, a.blocks, a.state, a.perm,
-                           a.q, a.D, (const float *)a.rinv, (const float *)a.qinv, (const float *)a.tsc,
-                           (const int *)a.trow, a.excl_bits, (long long)a.W, a.k, pl.S, a.cnt, a.cs, a.cr);
+    rank_for_capacity(a.k, [&](auto kl) {
+        hipLaunchKernelGGL((rmx_tile_kernel<MODE, decltype(kl)::value>), dim3((unsigned)(pl.max_blocks * pl.S)), dim3(256),
+                           0, s, a.desc, a.blocks, a.state, a.perm, a.q, a.D, (const float *)a.rinv, (const float *)a.qinv,
+                           (const float *)a.tsc, (const int *)a.trow, a.excl_bits, (long long)a.W, a.k, pl.S, a.cnt, a.cs,
+                           a.cr);
+    });
 }
 
 extern "C" int mpqe_rank_entities_mixed(const float *q, int64_t num_queries, int64_t dim, float eps, const void *desc,
@@ -581,13 +451,7 @@ extern "C" int mpqe_rank_entities_mixed(const float *q, int64_t num_queries, int
                        (int)num_groups, (long long)max_rows, (long long)total_rows, q, (long long)Q, a.D, eps,
                        (const int *)qset, a.rinv, a.qinv, a.tsc, a.trow, a.cnt);
     // (the tables' rows are 16-byte aligned by the descriptor's build: the load mode hangs on q and dim alone)
-    const bool vec = ptr_vec_ok(q, dim);
-    if (vec && dim % GT_BK == 0)
-        rmx_launch<LD_FAST>(pl, a, s);
-    else if (vec)
-        rmx_launch<LD_PRED>(pl, a, s);
-    else
-        rmx_launch<LD_SCALAR>(pl, a, s);
+    rank_for_load_mode(ptr_vec_ok(q, dim), dim, [&](auto mode) { rmx_launch<decltype(mode)::value>(pl, a, s); });
     if (k > 0 || rank || target_scores)
         hipLaunchKernelGGL(rmx_finish_kernel, dim3((unsigned)((Q + 3) / 4)), dim3(256), 0, s, (long long)Q, k, pl.S,
                            (const RmxState *)state, (const int *)perm, (const float *)a.cs, (const int *)a.cr,

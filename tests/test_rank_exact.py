@@ -55,7 +55,8 @@ def align_up(v, a=256):
 
 
 def plan(qblocks, tiles):
-    """csrc/rank.hip: rank_plan, csrc/rank_mixed.hip: rmx_plan -> (S, tiles per strip of the widest table)"""
+    """csrc/rank_core.h: rank_strip_rule, the one rule behind rank_plan (csrc/rank.hip) and rmx_plan (csrc/rank_mixed.hip)
+    -> (S, tiles per strip of the widest table)"""
     want = max(1, min(ceil_div(768, qblocks), MAX_STRIPS, tiles))
     tps = ceil_div(tiles, want)
     return ceil_div(tiles, tps), tps

@@ -10,7 +10,7 @@ bitmaps included, against an int64 oracle that shares nothing with the library.
 
 The main shape: five sets of 1, 63, 64, 65 and 700 rows, Q = 150 interleaved so that the sets get 0, 1, 64, 65 and 20
 queries (an empty set, a one-query block, a full block, a block and a query, a partial block). The block bound is
-150 / 64 + 5 = 7, so the strip rule of rank.hip gives S = 11 strips of one tile for the 700-row set and the narrower sets
+150 / 64 + 5 = 7, so the strip rule of rank_core.h gives S = 11 strips of one tile for the 700-row set and the narrower sets
 leave most strips empty; test_a_wide_set_several_tiles_per_strip widens a set until a strip of it holds two tiles. Operands
 sit between NaN fences; the descriptor block and the workspace are exactly as large as the size functions say and hold
 garbage.
@@ -113,8 +113,9 @@ def build(seed, dim, rows=ROWS, counts=COUNTS, kinds=None, with_bits=True, with_
     return Problem(q, tables, kinds, valid, set_of_group, group_of, target, bits)
 
 
-def run_mixed(be, pb, k, fill='noise', status=0, ws_short=0, want_rank=True, keep=None):
-    """One mixed call on fenced operands with a descriptor block and a workspace of exactly the named sizes."""
+def run_mixed(be, pb, k, fill='noise', status=0, ws_short=0, want_rank=True, keep=None, mis_q=0):
+    """One mixed call on fenced operands with a descriptor block and a workspace of exactly the named sizes; the query
+    matrix `mis_q` floats off 16 bytes."""
     lib = be.lib
     Q, D = pb.q.shape
     num_sets, num_groups = len(pb.tables), len(pb.set_of_group)
@@ -131,7 +132,7 @@ def run_mixed(be, pb, k, fill='noise', status=0, ws_short=0, want_rank=True, kee
                                         pb.set_of_group.ctypes.data, num_groups, be.ptr(desc), need_d, be.stream)
     assert st == 0, 'descriptor build: %d' % st
     max_rows, total_rows = int(rows.max()), int(rows.sum())
-    dq = fenced(be, pb.q)
+    dq = fenced(be, pb.q, mis_q)
     dg = fenced(be, pb.group_of)
     dtg = None if pb.target is None else fenced(be, pb.target)
     W = 0 if pb.bits is None else pb.bits.shape[1]
@@ -222,6 +223,26 @@ def test_plain_call_without_bitmaps_and_unaligned_dim(be):
         out = run_mixed(be, pb, 5)
         assert out['err'] == 0
         same_bits(out, run_per_set(be, pb, 5), 5)
+
+
+def test_a_misaligned_query_matrix_and_partial_blocks(be):
+    """Sets of 65 and 130 rows (2 and 3 column tiles, the last one and two rows wide) with 1 and 65 queries: blocks of 1,
+    64 and 1 live rows, so the tile core's staging rows past a block stand in for queries that are not there. dim 32 with q
+    one float off 16 bytes takes the element-wise loads by the pointer, dim 20 the predicated ones; `valid` and exclusion
+    words are present. Every operand sits between fences (run_mixed checks them)."""
+    k = 5
+    shape = dict(rows=(65, 130), counts=(1, 65))
+    pb = build(21, 32, **shape)
+    per_set, aligned = run_per_set(be, pb, k), run_mixed(be, pb, k)
+    off = run_mixed(be, pb, k, mis_q=1)
+    assert aligned['err'] == 0 and off['err'] == 0
+    same_bits(aligned, per_set, k, what='dim 32')
+    same_bits(off, per_set, k, what='dim 32, q 4 bytes off')
+    same_bits(off, aligned, k, what='dim 32, q 4 bytes off against aligned')
+    pb = build(22, 20, **shape)
+    out = run_mixed(be, pb, k)
+    assert out['err'] == 0
+    same_bits(out, run_per_set(be, pb, k), k, what='dim 20')
 
 
 def test_against_float64(be):
